@@ -22,9 +22,16 @@ gradient + a MAX all-reduce of the radii, opengaussian_amd/dp.py -- by default o
 render (--exchange pipelined; every exchange still completes inside the timed region), --exchange sync waits for
 each step's own exchange).
 
-One JSON line on rank 0, with `roofline` (dominant kernel, HIP events on the launch stream, algorithmic
-bytes of SURVEY.md section 8(d)) and `cpu_baseline` (the CPU oracle = pure-PyTorch per-tile alpha blend,
-bounded sample, rank 0 at N = 1 only).
+One JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline (`value`,
+`ms_per_step`, the scene and how the render phase was sized).  Everything else is measured only with --full, each
+leg switchable with the --no-* options: `roofline` (dominant kernel, HIP events on the launch stream, algorithmic
+bytes of SURVEY.md section 8(d)) and the per-kernel breakdown pass, `cpu_baseline` (the CPU oracle = pure-PyTorch
+per-tile alpha blend, bounded sample, rank 0 at N = 1 only), `kmeans`, `stage1_pass`, `frozen_rgb_call`, the
+`extras` workloads (child runs) and, for N > 1, the exchange modes, the collectives alone and the other training step.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0): the rasterizer's outputs and every gradient
+the step produced, one DIR/<name>.npy each (see dump_outputs()).  The inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -84,7 +91,16 @@ def parse():
     ap.add_argument("--separate-passes", action="store_true",
                     help="render RGB and the 6-ch ins_feat map as two rasterizer passes (reference structure) "
                          "instead of the single fused 9-channel pass")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (roofline + per-kernel breakdown, CPU baselines, "
+                         "k-means, stage-1 and frozen-geometry steps, the other workloads, N > 1 exchange figures); the "
+                         "--no-* options switch single legs off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs and gradients of the last timed step as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 WORKLOADS = {
@@ -402,7 +418,7 @@ def extra_workloads(args):
     for wl, key in (("C2-100k-800", "C2"), ("C3-500k-988", "C3"), ("C4-2M-648", "C4"), ("C4-2M-648-inside", "C4_inside")):
         log(f"extra workload {wl}")
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", wl, "--steps", "100", "--warmup", "10",
-               "--views", str(args.views), "--no-cpu-baseline", "--no-kmeans", "--no-extra-workloads"]
+               "--views", str(args.views), "--full", "--no-cpu-baseline", "--no-kmeans", "--no-extra-workloads"]
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, timeout=600)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -419,6 +435,108 @@ def extra_workloads(args):
         except Exception as e:          # an extra line never takes the headline down
             res[key] = {"error": repr(e)}
     return res
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one out_dir/<name>.npy per array, float32 (float64 stays float64; integer outputs such as the radii
+    are exact in float32).  An array within its share of the 64 MB budget is written whole, in its shape; a larger one as a
+    fixed sample: the flat elements at the sorted indices numpy.random.default_rng(zlib.crc32(name)).choice(numel, n,
+    replace=False) draws, n = its share -- the same elements in every run with the same arguments."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // max(len(arrays), 1)     # 4 KiB per file for the .npy header
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = share // (8 if dt == torch.float64 else 4)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(dt).cpu().numpy())
+    log(f"outputs of the last timed step: {', '.join(arrays)} -> {out_dir}")
+
+
+def kernel_figures(prof, args, fused, P, D, npx):
+    """--full: per-kernel times of the timed region (dominant kernel) and of the breakdown pass, the roofline of the
+    dominant kernel and the counter-derived figures committed under profiles/."""
+    from opengaussian_amd import _lib
+    per_kernel = {k: {"calls": v["calls"], "avg_ms": v["total_ms"] / max(v["calls"], 1), "total_ms": v["total_ms"],
+                      "ms_per_step": v["total_ms"] / max(v["steps"], 1)} for k, v in prof.items()}
+    known = set(algorithmic_bytes(P, D, npx, 9, 54))
+    cands = [k for k in per_kernel if k.split("<")[0] in known] or list(per_kernel)
+    dom = max(cands, key=lambda k: per_kernel[k]["ms_per_step"])       # the dominant kernel (among those SURVEY 8(d) prices)
+    dom_base = dom.split("<")[0]
+    dom_C = int(dom.split("<")[1].rstrip(">")) if "<" in dom and dom.split("<")[1].rstrip(">").isdigit() else 3
+    ab = algorithmic_bytes(P, D, npx, dom_C, {3: 48, 9: 54}.get(dom_C, dom_C))
+    dom_bytes = ab.get(dom_base)
+    # Counter-derived figures are OFFLINE: collected by separate `rocprofv3 --pmc` passes of this same command
+    # (scripts/profile_round.sh -> scripts/collect_rocpd.py -- a timed run cannot carry counters) and committed under
+    # profiles/ together with the kernel version they were taken on; they are attached only when that version
+    # is the library's (ogs_version()) and the workload is the one profiled.
+    traffic, traffic_src, hbm_kernels, valu = None, None, None, None
+    pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json" if args.workload == "S1M-1080p"
+                            else f"pmc_traffic_{args.workload}.json")
+    sq_file = os.path.join(ROOT, "profiles", "sq_valu.json")
+    libver = int(_lib.lib().ogs_version())
+    profiled = fused and args.views == 8 and not args.stage1
+    if os.path.exists(pmc_file) and profiled:
+        try:
+            pmc = json.load(open(pmc_file))
+            if int(pmc.get("_ogs_version", -1)) == libver:
+                traffic = pmc.get(dom)
+                traffic_src = pmc.get("_source")
+                # measured HBM bytes per launch (PMC) / live launch duration, for every kernel of the step
+                hbm_kernels = {k: {"GBps": pmc[k] / (v["avg_ms"] * 1e-3) / 1e9,
+                                   "frac_of_peak": pmc[k] / (v["avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+                               for k, v in per_kernel.items() if k in pmc and v["avg_ms"] > 0}
+        except Exception:
+            traffic, hbm_kernels = None, None
+    if os.path.exists(sq_file) and profiled and args.workload == "S1M-1080p":
+        try:
+            sq = json.load(open(sq_file))
+            if int(sq.get("_ogs_version", -1)) == libver and dom in sq:
+                n_valu = float(sq[dom]["SQ_INSTS_VALU"])          # VALU wave-instructions per launch
+                rate = n_valu / (per_kernel[dom]["avg_ms"] * 1e-3) / 1e9
+                valu = {"bound": "valu", "kernel": dom, "achieved": rate, "peak": VALU_PEAK_GINST, "unit": "G wave-instr/s",
+                        "frac": rate / VALU_PEAK_GINST, "valu_wave_instructions_per_launch": n_valu,
+                        "peak_note": "2 cycles per wave64 instruction per SIMD (all-VGPR forms, measured); forms with an SGPR "
+                                     "operand, DPP, compares / selects, min / max issue at 4",
+                        "source": sq.get("_source")}
+                mix_file = os.path.join(ROOT, "profiles", "r04_issue_mix.json")
+                if os.path.exists(mix_file):
+                    mix = json.load(open(mix_file)).get(dom.split("<")[0])
+                    if mix:
+                        cyc = float(mix["modelled_issue_cycles_per_valu"])
+                        mix_peak = 256 * 4 * 2.4 / cyc
+                        valu["issue_model"] = {"modelled_cycles_per_valu_instruction": cyc,
+                                               "share_of_half_rate_or_slower_forms": mix["share_half_rate_or_slower"],
+                                               "peak_for_this_mix": mix_peak, "frac_of_mix_peak": rate / mix_peak,
+                                               "source": "scripts/isa_issue_mix.py (static mix of the kernel's vector "
+                                                         "instructions x the measured price list)"}
+        except Exception:
+            valu = None
+    roofline = None
+    if dom_bytes is not None:
+        achieved = dom_bytes / (per_kernel[dom]["avg_ms"] * 1e-3) / 1e9
+        # `bound` names the ruler of this object (HBM bytes, as the bench contract asks); the kernel's actual
+        # limiter is VALU issue -- see `limiter` and the sibling `roofline_valu`
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
+                    "limiter": {"blend_backward_kernel": "the L2's fp64 atomic path (sensitivity probes, DESIGN.md section 3b: every atomic "
+                                                         "issued twice 0.62 -> 1.12 ms, none 0.47 ms; +8 VALU per entry or one "
+                                                         "workgroup less per CU: no change) -- not HBM bytes, not vector issue",
+                                "pack_blend_chunked_kernel": "vector issue and occupancy (probes, DESIGN.md section 3b) -- not HBM bytes",
+                                "blend_backward_feat_lds_kernel": "vector issue of the walk (its atomics cost 0.02 of 0.36 ms)",
+                                "preprocess_backward_kernel": "HBM at the part's mixed read / write rate (4.6 TB/s for a 1 : 1 copy)",
+                                "preprocess_kernel": "HBM at the part's mixed read / write rate"}.get(dom_base, "see DESIGN.md section 4"),
+                    "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_ms": per_kernel[dom]["avg_ms"]}
+    return {"roofline": roofline, "roofline_valu": valu, "pmc_hbm_rate_per_kernel": hbm_kernels,
+            "kernels_ms_per_step": {k: v["ms_per_step"] for k, v in sorted(per_kernel.items(), key=lambda kv: -kv[1]["ms_per_step"])}}
 
 
 _T0 = time.time()
@@ -508,7 +626,7 @@ def main():
     all_settings = [settings_of(c) for c in cams_cpu]
     campos_views = torch.stack([c.camera_center for c in cams_cpu]).to(device)
     dist_on = world > 1 or dp.FORCE_COLLECTIVES
-    info = {"i": 0, "D_seen": [], "xmode": args.exchange}
+    info = {"i": 0, "D_seen": [], "xmode": args.exchange, "keep": False}
 
     def view_of(step_index, r):
         return (step_index * world + r) % V
@@ -570,6 +688,9 @@ def main():
         info["D"] = color.grad_fn.num_rendered
         info["D_seen"].append(info["D"])
         torch.autograd.backward([color, alpha], [gCF, gA])
+        if info["keep"]:
+            info["last"] = dict(color=color.detach(), depth=depth.detach(), alpha=alpha.detach(), radii=radii,
+                                grad_means2D=m2.grad, **{"grad_" + n: leaves[n].grad for n in names_f})
         xmode = info["xmode"]
         if sets and xmode != "none":
             st = sets[i % nsets] if xmode == "pipelined" else sets[0]
@@ -603,6 +724,9 @@ def main():
         info["D"] = color.grad_fn.num_rendered
         info["D_seen"].append(info["D"])
         torch.autograd.backward([color, alpha], [gC, gA])
+        if info["keep"]:
+            info["last"] = dict(color=color.detach(), depth=depth.detach(), alpha=alpha.detach(), radii=radii,
+                                grad_means2D=m2a.grad, **{"grad_" + n: leaves[n].grad for n in names_a})
         if bucket_a is not None:
             bucket_a.pack([leaves[n].grad for n in names_a])
             bucket_a.allreduce_async()
@@ -612,6 +736,9 @@ def main():
                                  colors_precomp=leaves["ins_feat"], scales=leaves["scales"].detach(),
                                  rotations=leaves["rotations"].detach())
             torch.autograd.backward([feat], [gF])
+            if info["keep"]:
+                info["last"]["feat"] = feat.detach()
+                info["last"]["grad_ins_feat"] = leaves["ins_feat"].grad
             if bucket_b is not None:
                 bucket_b.pack([leaves["ins_feat"].grad])
                 bucket_b.allreduce_async()
@@ -648,6 +775,9 @@ def main():
         info["D_seen"].append(info["D"])
         feat.grad = None
         color.backward(s1["gC9"])
+        if info["keep"]:
+            info["last"] = dict(color=color.detach(), depth=depth.detach(), alpha=alpha.detach(), radii=radii,
+                                grad_ins_feat=feat.grad)
         if s1["buckets"] and s1["mode"] != "none":
             b = s1["buckets"][i % 2] if s1["mode"] == "pipelined" else s1["buckets"][0]
             b.pack([feat.grad])
@@ -671,40 +801,51 @@ def main():
         step_all, drain_all = step, drain              # keep the all-gradient step for the extras
         step, drain = step_stage1, drain_stage1
 
-    # the warm-up steps bracket both blend kernels (mode 2, prefix "blend_") to learn which one dominates the step
-    _lib.prof_filter("blend_")
-    _lib.prof_enable(2)
+    full = args.full
+    extras = full and not args.no_extras
+    # --full: the warm-up steps bracket both blend kernels (mode 2, prefix "blend_") to learn which one dominates the step
+    if full:
+        _lib.prof_filter("blend_")
+        _lib.prof_enable(2)
     for i in range(args.warmup):
         radii = step()
         drain()
         torch.cuda.synchronize()
         log(f"warmup step {i} done (D={info.get('D')})")
-    warm = _lib.prof_collect()
-    dominant = max(warm, key=lambda k: warm[k]["total_ms"]).split("<")[0] if warm else "blend_"
+    if full:
+        warm = _lib.prof_collect()
+        dominant = max(warm, key=lambda k: warm[k]["total_ms"]).split("<")[0] if warm else "blend_"
     barrier()
-    # Timed region.  HIP events on the launch stream bracket ONLY the dominant kernel here (the roofline's kernel:
+    # Timed region.  --full: HIP events on the launch stream bracket ONLY the dominant kernel here (the roofline's kernel:
     # its launch duration has to come from the timed region): an event pair serialises the queue for ~10 us per
     # launch, and a step issues ~35 launches, so bracketing every kernel inside the timed region would cost
-    # ~0.35 ms/step; the other kernels are timed by the untimed pass below.
-    _lib.prof_filter(dominant)
-    _lib.prof_enable(2)
+    # ~0.35 ms/step; the other kernels are timed by the untimed pass below.  A plain run brackets nothing.
+    if full:
+        _lib.prof_filter(dominant)
+        _lib.prof_enable(2)
     stats0 = dict(R.PASS_STATS)
     info["D_seen"] = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for s in range(args.steps):
+        info["keep"] = args.dump_outputs is not None and s == args.steps - 1
         radii = step()
     drain()                                   # the last exchange(s) complete inside the timed region
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
     log(f"timed region done: {elapsed / args.steps * 1e3:.3f} ms/step")
-    prof = _lib.prof_collect()
-    for v in prof.values():
-        v["steps"] = args.steps
+    info["keep"] = False
     stats_timed = dict(R.PASS_STATS)
-    # second, untimed pass with every launch bracketed: the per-kernel breakdown
-    _lib.prof_filter("blend_")
-    if not args.no_extras:
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, info.pop("last"))
+    prof = {}
+    if full:
+        prof = _lib.prof_collect()
+        for v in prof.values():
+            v["steps"] = args.steps
+        # second, untimed pass with every launch bracketed: the per-kernel breakdown
+        _lib.prof_filter("blend_")
+    if extras:
         _lib.prof_enable(1)
         nb = min(args.steps, 40)
         for _ in range(nb):
@@ -726,7 +867,7 @@ def main():
     # N > 1, untimed extras: the same steps with each step waiting for its own exchange ('sync') and with no exchange at
     # all ('none') -> how much of the exchange the pipelined mode leaves exposed (barrier + max over ranks, as above)
     xtimes = {}
-    if dist_on and fused and not args.no_extras:
+    if dist_on and fused and extras:
         nb = max(2, min(args.steps, 20))
         for mode in [m for m in ("pipelined", "sync", "none") if m != args.exchange]:
             info["xmode"] = mode
@@ -760,7 +901,7 @@ def main():
     # line can tell link time from compute time; (b) the other training step (stage 1 when the all-gradient step was
     # timed, and vice versa) through the same pipelined exchange: both scaling curves out of the driver's one command.
     coll, other_step = None, None
-    if dist_on and fused and not args.no_extras:
+    if dist_on and fused and extras:
         def time_collective(fn, reps=6):
             fn()
             barrier()
@@ -857,76 +998,6 @@ def main():
         npx = W * H
         p_vis = int((radii > 0).sum().item())
         gxy = ((W + 15) // 16) * ((H + 15) // 16)
-        per_kernel = {k: {"calls": v["calls"], "avg_ms": v["total_ms"] / max(v["calls"], 1), "total_ms": v["total_ms"],
-                          "ms_per_step": v["total_ms"] / max(v["steps"], 1)} for k, v in prof.items()}
-        known = set(algorithmic_bytes(P, D, npx, 9, 54))
-        cands = [k for k in per_kernel if k.split("<")[0] in known] or list(per_kernel)
-        dom = max(cands, key=lambda k: per_kernel[k]["ms_per_step"])       # the dominant kernel (among those SURVEY 8(d) prices)
-        dom_base = dom.split("<")[0]
-        dom_C = int(dom.split("<")[1].rstrip(">")) if "<" in dom and dom.split("<")[1].rstrip(">").isdigit() else 3
-        ab = algorithmic_bytes(P, D, npx, dom_C, {3: 48, 9: 54}.get(dom_C, dom_C))
-        dom_bytes = ab.get(dom_base)
-        # Counter-derived figures are OFFLINE: collected by separate `rocprofv3 --pmc` passes of this same command
-        # (scripts/collect_pmc.py, scripts/collect_sq.py -- a timed run cannot carry counters) and committed under
-        # profiles/ together with the kernel version they were taken on; they are attached only when that version
-        # is the library's (ogs_version()) and the workload is the one profiled.
-        traffic, traffic_src, hbm_kernels, valu = None, None, None, None
-        pmc_file = os.path.join(ROOT, "profiles", "pmc_traffic.json" if args.workload == "S1M-1080p"
-                                else f"pmc_traffic_{args.workload}.json")
-        sq_file = os.path.join(ROOT, "profiles", "sq_valu.json")
-        libver = int(_lib.lib().ogs_version())
-        profiled = fused and args.views == 8 and not args.stage1
-        if os.path.exists(pmc_file) and profiled:
-            try:
-                pmc = json.load(open(pmc_file))
-                if int(pmc.get("_ogs_version", -1)) == libver:
-                    traffic = pmc.get(dom)
-                    traffic_src = pmc.get("_source")
-                    # measured HBM bytes per launch (PMC) / live launch duration, for every kernel of the step
-                    hbm_kernels = {k: {"GBps": pmc[k] / (v["avg_ms"] * 1e-3) / 1e9,
-                                       "frac_of_peak": pmc[k] / (v["avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS}
-                                   for k, v in per_kernel.items() if k in pmc and v["avg_ms"] > 0}
-            except Exception:
-                traffic, hbm_kernels = None, None
-        if os.path.exists(sq_file) and profiled and args.workload == "S1M-1080p":
-            try:
-                sq = json.load(open(sq_file))
-                if int(sq.get("_ogs_version", -1)) == libver and dom in sq:
-                    n_valu = float(sq[dom]["SQ_INSTS_VALU"])          # VALU wave-instructions per launch
-                    rate = n_valu / (per_kernel[dom]["avg_ms"] * 1e-3) / 1e9
-                    valu = {"bound": "valu", "kernel": dom, "achieved": rate, "peak": VALU_PEAK_GINST, "unit": "G wave-instr/s",
-                            "frac": rate / VALU_PEAK_GINST, "valu_wave_instructions_per_launch": n_valu,
-                            "peak_note": "2 cycles per wave64 instruction per SIMD (all-VGPR forms, measured); forms with an SGPR "
-                                         "operand, DPP, compares / selects, min / max issue at 4",
-                            "source": sq.get("_source")}
-                    mix_file = os.path.join(ROOT, "profiles", "r04_issue_mix.json")
-                    if os.path.exists(mix_file):
-                        mix = json.load(open(mix_file)).get(dom.split("<")[0])
-                        if mix:
-                            cyc = float(mix["modelled_issue_cycles_per_valu"])
-                            mix_peak = 256 * 4 * 2.4 / cyc
-                            valu["issue_model"] = {"modelled_cycles_per_valu_instruction": cyc,
-                                                   "share_of_half_rate_or_slower_forms": mix["share_half_rate_or_slower"],
-                                                   "peak_for_this_mix": mix_peak, "frac_of_mix_peak": rate / mix_peak,
-                                                   "source": "scripts/isa_issue_mix.py (static mix of the kernel's vector "
-                                                             "instructions x the measured price list)"}
-            except Exception:
-                valu = None
-        roofline = None
-        if dom_bytes is not None:
-            achieved = dom_bytes / (per_kernel[dom]["avg_ms"] * 1e-3) / 1e9
-            # `bound` names the ruler of this object (HBM bytes, as the bench contract asks); the kernel's actual
-            # limiter is VALU issue -- see `limiter` and the sibling `roofline_valu`
-            roofline = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                        "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
-                        "limiter": {"blend_backward_kernel": "the L2's fp64 atomic path (sensitivity probes, DESIGN.md section 3b: every atomic "
-                                                             "issued twice 0.62 -> 1.12 ms, none 0.47 ms; +8 VALU per entry or one "
-                                                             "workgroup less per CU: no change) -- not HBM bytes, not vector issue",
-                                    "pack_blend_chunked_kernel": "vector issue and occupancy (probes, DESIGN.md section 3b) -- not HBM bytes",
-                                    "blend_backward_feat_lds_kernel": "vector issue of the walk (its atomics cost 0.02 of 0.36 ms)",
-                                    "preprocess_backward_kernel": "HBM at the part's mixed read / write rate (4.6 TB/s for a 1 : 1 copy)",
-                                    "preprocess_kernel": "HBM at the part's mixed read / write rate"}.get(dom_base, "see DESIGN.md section 4"),
-                        "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_ms": per_kernel[dom]["avg_ms"]}
         step_bytes = sum(algorithmic_bytes(P, D, npx, 3, 48)[k] for k in ("fwd", "bwd"))
         if fused:
             step_bytes = sum(algorithmic_bytes(P, D, npx, 9, 54)[k] for k in ("fwd", "bwd"))
@@ -958,13 +1029,15 @@ def main():
             "render_phase_sizing_timed": {k: stats_timed[k] - stats0[k] for k in stats_timed},
             "host": {"autograd_multithreading": autograd_mt},
             "dist": dist_info,
-            "roofline": roofline,
-            "roofline_valu": valu,
-            "pmc_hbm_rate_per_kernel": hbm_kernels,
-            "step_algorithmic_GBps": step_bytes / (ms_per_step * 1e-3) / 1e9,
-            "kernels_ms_per_step": {k: v["ms_per_step"] for k, v in sorted(per_kernel.items(), key=lambda kv: -kv[1]["ms_per_step"])},
         }
-        if world == 1 and not args.no_kmeans:
+        figs = kernel_figures(prof, args, fused, P, D, npx) if full else None
+        if figs:
+            out.update(roofline=figs["roofline"], roofline_valu=figs["roofline_valu"],
+                       pmc_hbm_rate_per_kernel=figs["pmc_hbm_rate_per_kernel"])
+        out["step_algorithmic_GBps"] = step_bytes / (ms_per_step * 1e-3) / 1e9
+        if figs:
+            out["kernels_ms_per_step"] = figs["kernels_ms_per_step"]
+        if world == 1 and full and not args.no_kmeans:
             try:
                 log("k-means bench")
                 out["kmeans"] = kmeans_bench(device)
@@ -974,7 +1047,7 @@ def main():
                     out["kmeans"]["leaf"] = {"error": repr(e)}
             except Exception as e:   # k-means is the second half of the metric, never the headline value
                 out["kmeans"] = {"error": repr(e)}
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             try:
                 log("stage-1 pass (features-only backward)")
                 out["stage1_pass"] = stage1_bench(leaves, all_settings, gF, P, device)
@@ -984,12 +1057,12 @@ def main():
                 out["frozen_rgb_call"] = frozen_rgb_bench(scene, cams_cpu, W, H, device)
             except Exception as e:
                 out["frozen_rgb_call"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and full and not args.no_cpu_baseline:
             log("cpu baseline (oracle)")
             out["cpu_baseline"] = cpu_baseline(scene_cpu, cam_cpu, W, H, f, args.cpu_tile_stride, args.rgb_only)
             if "kmeans" in out and "error" not in out["kmeans"]:
                 out["kmeans"]["cpu_baseline"] = kmeans_cpu_baseline()
-        if world == 1 and args.workload == "S1M-1080p" and not args.no_extras and not args.no_extra_workloads:
+        if world == 1 and args.workload == "S1M-1080p" and extras and not args.no_extra_workloads:
             out["extras"] = extra_workloads(args)
         print(json.dumps(out))
     if world > 1:

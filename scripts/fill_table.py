@@ -5,7 +5,7 @@ sys.path.insert(0, ".")
 rows = {}
 for name, args in (("S1M_rgb", ["--rgb-only"]), ("C2_rgb", ["--workload", "C2-100k-800", "--rgb-only"]),
                    ("C2_fused", ["--workload", "C2-100k-800"])):
-    out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--no-kmeans", *args], capture_output=True, text=True)
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-kmeans", *args], capture_output=True, text=True)
     d = json.loads(out.stdout.strip().splitlines()[-1])
     k = d["kernels_ms_per_step"]
     bwd = sum(v for n, v in k.items() if "backward" in n)

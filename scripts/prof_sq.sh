@@ -3,7 +3,7 @@ export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 TAG=$1; shift
 for kv in "$@"; do export "$kv"; done
-B="python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra-workloads ${PROF_BENCH_FLAGS---no-kmeans}"
+B="python3 bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-extra-workloads ${PROF_BENCH_FLAGS---no-kmeans}"
 rm -rf gpurun_out/sq_$TAG; mkdir -p gpurun_out/sq_$TAG
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_INSTS_SMEM -d gpurun_out/sq_$TAG/a -o s -- $B > gpurun_out/sq_$TAG/a.log 2>&1 &&
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS -d gpurun_out/sq_$TAG/b -o s -- $B > gpurun_out/sq_$TAG/b.log 2>&1 &&
