@@ -1,4 +1,4 @@
-// Backward alpha blend for gfx950 -- scalar-path design (see blend_fwd.hip).
+// Backward alpha blend for gfx950 -- scalar-path design.
 //
 // One workgroup per 16x16 tile, each wave64 owns an 8x8 quadrant and walks ITS index stream (blend_fwd.hip)
 // BACK-TO-FRONT from its own last contributor, indices and records fetched with wave-uniform scalar loads:
@@ -22,8 +22,6 @@
 // i.e. the geometry / opacity gradients; channels beyond it only receive their own dL/dfeature.  This is
 // what lets ONE fused pass reproduce "RGB loss reaches geometry, ins_feat loss is detached from it"
 // (train.py:431-436) exactly as two separate reference passes would.
-#include <string.h>
-
 #include "ogs_common.h"
 #include "wave_fold.h"
 
@@ -152,26 +150,11 @@ struct RankOneFold {
 // rows of entries 2 k, 2 k + 1 -- ONE atomic instruction per register pair adds four entries' complete records (lane
 // group k = entry, lane n = slot).
 //
-// Round 4, two changes to what follows an accepted entry (0.26 of the kernel's 0.64 ms):
-//  (a) the product runs on the bf16 path, v_mfma_f32_16x16x32_bf16 (16 SIMD cycles per instruction, 8 of them blocking
-//      the vector issue; the exact-fp32 v_mfma_f32_16x16x4_f32 holds it for all of its 32).  Every fp32 operand is split
-//      into two bf16 terms, x = hi + mid + eps: hi = the upper 16 bits of x (truncation: the residual x - hi is exact in
-//      fp32), mid = the residual rounded to nearest bf16, so |eps| <= 2^-16 |x| and unbiased.  All four cross products are
-//      kept (hi.hi, mid.hi, hi.mid, mid.mid; with a truncated hi the last one is up to 2^-14 of the product and cannot be
-//      dropped), accumulated in fp32 from the smallest to the largest: 8 instructions per eight entries instead of 16,
-//      ~128 instead of 512 cycles.  A side: the lane of pixel p stores the two terms of w and of q as 16-bit words into
-//      two planes of the entry's rows (ds_write_b16_d16_hi takes the upper half of a VGPR: the hi term costs no VALU
-//      instruction at all, the mid term and / sub / add); the flush reads one plane of one 32-pixel half of a row with
-//      ONE ds_read_b128 -- eight consecutive pixels = eight K slots, exactly the operand of the instruction.  B side:
-//      loop invariant, split once per kernel into two planes of 8 VGPRs (the 16 VGPRs the fp32 operand took); the moment
-//      basis (values k/4, |.| <= 12.25) is exact in ONE bf16 term.  Product error <= 2^-15 |w g| (q likewise), unbiased:
-//      measured against the float64 oracle in tests/test_10 / test_12 (same 2e-4 bar as before).
-//      NOT the default any more (end of round 4): the kernel is bound by the atomic path, the two products time the same
-//      (0.617 / 0.626 against 0.620 / 0.620 ms, A-B on one box) -- and a randomised soak (scripts/fuzz_parity.py) found what
-//      2^-15 per product costs when a Gaussian's sum cancels: a one-Gaussian scene of 20 pixels with dL/dopacity 3.5e-4 off
-//      (every seeded test scales errors by the maximum over many Gaussians).  The exact-fp32 product is the default;
-//      OGS_BLEND_FOLD=bf16 selects this one (alternative-kernel test, A-B timing).
-//  (b) the moments leave the wave about a GLOBAL origin -- the image's pixel (0, 0) -- instead of the Gaussian's own
+// The product runs in exact fp32 on v_mfma_f32_16x16x4_f32, sixteen instructions per eight entries.  (A two-term bf16
+// split on v_mfma_f32_16x16x32_bf16 timed the same -- the kernel is bound by the atomic path -- and its 2^-15 per product
+// showed on a one-Gaussian scene whose sum cancels: DESIGN.md section 3.)
+// Round 4 changed what follows an accepted entry (0.26 of the kernel's 0.64 ms):
+//      the moments leave the wave about a GLOBAL origin -- the image's pixel (0, 0) -- instead of the Gaussian's own
 //      centre: with X = x0 + u (x0 the quadrant centre) every record slot is  own + cA m0 + cB mu + cC mv  with three
 //      per-LANE constants that do not depend on the entry (slot MX: cA = x0; MXX: cA = x0^2, cB = 2 x0; MXY: cA = x0 y0,
 //      cB = y0, cC = x0; feature slots: zeros) -- three DPP row broadcasts and three fp64 FMAs per register instead of
@@ -180,8 +163,7 @@ struct RankOneFold {
 //      its atomics take anyway; preprocess_bwd.hip re-centres the six sums on the Gaussian's pixel centre ONCE per
 //      Gaussian, in fp64 (cancellation there: |X|^2 / sigma^2 <= ~1e7 of 1e16).  The fp32 inputs of the shift (the MFMA
 //      results) are the same as before, and so is the conditioning of what comes out.
-// LDS: 16 rows x 68 dwords per wave.  bf16 layout: halfwords [0, 64) = hi plane (pixel = lane), [64, 128) = mid plane,
-// dwords 64..67 spare; fp32 layout: 64 floats + the same spare dwords.  Row stride 68 dwords: 16-byte aligned rows for the
+// LDS: 16 rows x 68 dwords per wave: 64 floats (pixel = lane) + 4 spare dwords.  Row stride 68 dwords: 16-byte aligned rows for the
 // ds_read_b128 of the flush, the sixteen rows of a lane group in distinct bank groups.  The Gaussian ids of the batch
 // live in ONE VGPR (entry e in lane e, v_writelane); the flush parks them in the rows' spare dword and each lane group
 // reads the two it owns.
@@ -189,26 +171,17 @@ constexpr int kPairStride = 68;
 struct PairFoldLds {
     float t[16 * kPairStride];
 };
-typedef __bf16 bf16x8_bw __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4_bw __attribute__((ext_vector_type(4)));
 
 template <int N>
 __device__ __forceinline__ float row_bcast(float v) {     // lane n of every row of 16 lanes -> the whole row
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x150 + N, 0xF, 0xF, false));
 }
 
-// two-term bf16 split of an fp32 value: hi = upper half of x (truncated), mid = upper half of the returned word
-// (the exact residual x - hi, rounded to nearest bf16 by adding half an ulp before the truncating 16-bit store)
-__device__ __forceinline__ uint32_t bf16_mid_word(float x) {
-    const float r = x - __uint_as_float(__float_as_uint(x) & 0xFFFF0000u);
-    return __float_as_uint(r) + 0x8000u;
-}
-
-template <int C, bool DEPTH, bool BF16>
+template <int C, bool DEPTH>
 struct PairFold {
     float* t;
     uint32_t gidv;      // lane e: Gaussian id of staged entry e
-    uint32_t Bw[16];    // BF16: [0..7] hi plane, [8..15] mid plane (two bf16 per dword); fp32: the sixteen B operands
+    float B[16];        // the sixteen B operands of this lane
     double cA, cB, cC;  // this lane's slot: record value = own + cA m0 + cB mu + cC mv   (zeros on the feature slots)
     int cnt;            // wave-uniform: entries staged
     bool skip_atomics = false;   // timing experiment (-DOGS_EXPERIMENTS only)
@@ -240,51 +213,24 @@ struct PairFold {
             b = n == kSlotMoments + 5 ? v * v : b;
             return b;
         };
-        if constexpr (BF16) {
-            // instruction (half h): K slot 8 kq + i <-> pixel 32 h + 8 kq + i = row 4 h + kq of the quadrant, column i
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                for (int i2 = 0; i2 < 4; ++i2) {
-                    const float b0 = bval(32 * h + 8 * kq + 2 * i2), b1 = bval(32 * h + 8 * kq + 2 * i2 + 1);
-                    Bw[4 * h + i2] = (__float_as_uint(b0) >> 16) | (__float_as_uint(b1) & 0xFFFF0000u);
-                    Bw[8 + 4 * h + i2] = (bf16_mid_word(b0) >> 16) | (bf16_mid_word(b1) & 0xFFFF0000u);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) Bw[j] = __float_as_uint(bval(16 * (j >> 2) + 4 * kq + (j & 3)));   // pixel fed to MFMA j by this lane group
-        }
+        for (int j = 0; j < 16; ++j) B[j] = bval(16 * (j >> 2) + 4 * kq + (j & 3));   // pixel fed to MFMA j by this lane group
     }
     __device__ __forceinline__ void flush(double* __restrict__ grad_rec, int lane) {
         const int m = lane & 15, kq = lane >> 4;
         floatx4 d = {0.f, 0.f, 0.f, 0.f};
         // rows beyond the staged entries hold stale weights: a row of A only reaches the same row of D, which is
         // never written out
-        if constexpr (BF16) {
-            const u32x4_bw* rowp = reinterpret_cast<const u32x4_bw*>(t + m * kPairStride);       // 16-byte units of row m
-            const u32x4_bw ah0 = rowp[kq], ah1 = rowp[4 + kq], am0 = rowp[8 + kq], am1 = rowp[12 + kq];
-            const u32x4_bw bh0 = {Bw[0], Bw[1], Bw[2], Bw[3]}, bh1 = {Bw[4], Bw[5], Bw[6], Bw[7]};
-            const u32x4_bw bm0 = {Bw[8], Bw[9], Bw[10], Bw[11]}, bm1 = {Bw[12], Bw[13], Bw[14], Bw[15]};
-            auto mm = [](const u32x4_bw& a, const u32x4_bw& b, floatx4 c) {
-                return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_bw, a), __builtin_bit_cast(bf16x8_bw, b), c, 0, 0, 0);
-            };
-            d = mm(am0, bm0, d); d = mm(am1, bm1, d);        // mid x mid  (<= 2^-14 of the product)
-            d = mm(am0, bh0, d); d = mm(am1, bh1, d);        // mid x hi
-            d = mm(ah0, bm0, d); d = mm(ah1, bm1, d);        // hi  x mid
-            d = mm(ah0, bh0, d); d = mm(ah1, bh1, d);        // hi  x hi
-        } else {
-            floatx4 d1 = d;
+        floatx4 d1 = d;
 #pragma unroll
-            for (int J = 0; J < 4; ++J) {
-                const float4 a = *reinterpret_cast<const float4*>(t + m * kPairStride + 16 * J + 4 * kq);
-                d = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, __uint_as_float(Bw[4 * J]), d, 0, 0, 0);
-                d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, __uint_as_float(Bw[4 * J + 1]), d1, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, __uint_as_float(Bw[4 * J + 2]), d, 0, 0, 0);
-                d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, __uint_as_float(Bw[4 * J + 3]), d1, 0, 0, 0);
-            }
-            d = d + d1;
+        for (int J = 0; J < 4; ++J) {
+            const float4 a = *reinterpret_cast<const float4*>(t + m * kPairStride + 16 * J + 4 * kq);
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, B[4 * J], d, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, B[4 * J + 1], d1, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, B[4 * J + 2], d, 0, 0, 0);
+            d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, B[4 * J + 3], d1, 0, 0, 0);
         }
+        d = d + d1;
         const bool column_used = m < C || (DEPTH && m == kSlotDepth) || m >= kSlotMoments;
         // ids of the batch's eight entries: lane e of the stash register -> the spare dword 64 of row e -> each lane group
         // reads the two it owns
@@ -312,17 +258,9 @@ struct PairFold {
     // one accepted entry: this lane's blend weight and q, the entry's Gaussian id (wave-uniform)
     __device__ __forceinline__ void push(float wl, float ql, uint32_t g, double* __restrict__ grad_rec, int lane) {
         const int rw = ((cnt >> 1) << 2) | (cnt & 1);
-        if constexpr (BF16) {
-            uint16_t* row = reinterpret_cast<uint16_t*>(t + rw * kPairStride);
-            row[lane] = (uint16_t)(__float_as_uint(wl) >> 16);
-            row[64 + lane] = (uint16_t)(bf16_mid_word(wl) >> 16);
-            row[4 * kPairStride + lane] = (uint16_t)(__float_as_uint(ql) >> 16);          // two rows below (halfword units)
-            row[4 * kPairStride + 64 + lane] = (uint16_t)(bf16_mid_word(ql) >> 16);
-        } else {
-            float* row = t + rw * kPairStride;
-            row[lane] = wl;
-            row[2 * kPairStride + lane] = ql;
-        }
+        float* row = t + rw * kPairStride;
+        row[lane] = wl;
+        row[2 * kPairStride + lane] = ql;
         // lane cnt of the stash register <- the wave-uniform id: v_writelane_b32, one instruction (a select costs a move of
         // the scalar into a VGPR plus a v_cndmask).  Two different SGPRs in one VOP3 exceed the constant bus, so the lane
         // select travels in M0 (saved and restored: M0 is the compiler's)
@@ -350,7 +288,7 @@ __device__ __forceinline__ int wave_max_i32(int v) {
 // features): a runtime value turned every per-channel update into v_cndmask selects and kept dead math alive.
 // DEPTH = false: no gradient arrives through the depth image (dL_ddepth == NULL -- every loss of the reference,
 // gaussian_renderer/__init__.py:362 "not used"): the depth recursion and its dL/dalpha term are compiled out.
-template <int C, int GC, bool DEPTH, bool BF16>
+template <int C, int GC, bool DEPTH>
 __global__ __launch_bounds__(kBlock) void blend_backward_kernel(
     const uint2* __restrict__ ranges, const float* __restrict__ stream, const uint32_t* __restrict__ quad_list, int W,
     int H, int gx, int tiles, const float* __restrict__ bg, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
@@ -377,7 +315,7 @@ __global__ __launch_bounds__(kBlock) void blend_backward_kernel(
     const int last_contrib = inside ? (int)n_contrib[pix] : 0;
     const int hi = __builtin_amdgcn_readfirstlane(wave_max_i32(last_contrib));
     if (hi == 0) return;                                 // wave-uniform; no barriers in this kernel
-    // this wave's quadrant stream (blend_fwd.hip::pack_sorted_kernel); n_contrib indexes into it
+    // this wave's quadrant stream (blend_fwd.hip::pack_blend_chunked_kernel); n_contrib indexes into it
     const int n_tile = (int)(range.y - range.x);
     const float* __restrict__ tb = stream + (size_t)range.x * RS;                                    // tile's records
     const uint32_t* __restrict__ qi = quad_list + ((size_t)range.x * 5 + (size_t)wave * n_tile);     // quadrant's indices
@@ -399,7 +337,7 @@ __global__ __launch_bounds__(kBlock) void blend_backward_kernel(
     const float gd = (DEPTH && inside) ? dL_ddepth[pix] : 0.f;
     const float ga = (inside && dL_dalpha_map) ? dL_dalpha_map[pix] : 0.f;
     // every slot of the gradient record is reduced over the quadrant's pixels on the matrix cores (PairFold)
-    PairFold<C, DEPTH, BF16> fold;
+    PairFold<C, DEPTH> fold;
     fold.skip_atomics = (pf_lines & 0x300) != 0;
     const float* __restrict__ ddepth_img = DEPTH ? dL_ddepth + (size_t)img * plane : nullptr;
     fold.init(&s_fold[wave], lane, tx, ty, wave, W, H, [&](int n, size_t p) {
@@ -411,8 +349,9 @@ __global__ __launch_bounds__(kBlock) void blend_backward_kernel(
     float Rd = 0.f, Ra = 0.f;
     const float tf_bg = T_final * bg_dot;                  // loop invariant of the background term
 
-    // Same SALU-frugal loop shape as blend_fwd.hip: no break / continue, two ping-pong records (no register
-    // rotation), unconditional prefetch (the stream is padded in front).
+    // SCALAR-ALU frugal loop (every nested divergent `if` costs exec-mask ops, and hipcc's structurizer turns break /
+    // continue into a scalar state machine): no break / continue, two ping-pong records (no register rotation),
+    // unconditional prefetch (the stream is padded in front).
     auto consume = [&](const StreamRec<C>& rec_j, int idx) {
         const f8 cur = rec_j.g;
         // blend_power(a2, b2, c2, dx, dy) with its first two products as PACKED operations on the record's even-aligned SGPR
@@ -471,13 +410,13 @@ __global__ __launch_bounds__(kBlock) void blend_backward_kernel(
             fold.push(w, q, __float_as_uint(cur[7]), grad_rec, lane);
         }
     };
-    // back-to-front over the quadrant's index stream (see blend_fwd.hip); reads below index 0 land in the previous
+    // back-to-front over the quadrant's index stream; reads below index 0 land in the previous
     // region / the front pad and are clamped
     const uint32_t* __restrict__ q = qi + (hi - 1);
     // the loop only touches the geometry and the first GC features of a record: 12 dwords for GC <= 3 without depth
     constexpr bool kBatched = GC <= 3 && !DEPTH;
     if constexpr (kBatched) {
-        // batches of two records with pinned scalar waits, as the forward walks (blend_fwd.hip): SMEM returns out of
+        // batches of two records with pinned scalar waits: SMEM returns out of
         // order, so the only wait there is is lgkmcnt(0) = "everything in flight" -- placed BEFORE the next batch is
         // issued, every record load gets two entries' worth of work to arrive.  (The one-ahead ping-pong below waits
         // right after issuing its next load, i.e. for that load too: SQ counters showed 36 % of this kernel's
@@ -528,96 +467,11 @@ __global__ __launch_bounds__(kBlock) void blend_backward_kernel(
 // recurrence (w = alpha * T, T *= 1 - alpha), so the weights are bit-identical to the forward pass.  Only channels
 // [F0, C) are produced (F0 = 3 in a fused pass whose channels 0..2 come from the -- detached -- SH colours), and
 // all of them through the matrix cores: no butterfly fold at all.
-template <int C, int F0, typename ACC>
-__global__ __launch_bounds__(kBlock) void blend_backward_feat_kernel(
-    const uint2* __restrict__ ranges, const float* __restrict__ stream, const uint32_t* __restrict__ quad_list, int W,
-    int H, int gx, int tiles, const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ qcount,
-    const float* __restrict__ dL_dcolor, ACC* __restrict__ grad_rec, int pf_lines, const uint32_t* __restrict__ tile_order) {
-    constexpr int RS = stream_vec4(C) * 4;
-    constexpr int GS = feat_grad_stride(C, F0);
-    constexpr int NS = C - F0;
-    static_assert(NS >= 1 && NS <= 9, "feature slots");
-    __shared__ WaveFoldLds s_fold[kBlock / kWave];
-
-    const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;
-    const int img = tile / tiles, timg = tile - img * tiles;
-    const int tx = timg % gx, ty = timg / gx;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int px = tx * kTile + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * kTile + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float fx = (float)px, fy = (float)py;
-    const size_t plane = (size_t)W * H;
-    const size_t pix = (size_t)img * plane + (size_t)py * W + px;
-    dL_dcolor += (size_t)img * C * plane;                               // image `img` of [G,C,H,W]
-
-    const uint2 range = ranges[tile];
-    const int last_contrib = inside ? (int)n_contrib[pix] : 0;
-    const int hi = __builtin_amdgcn_readfirstlane(wave_max_i32(last_contrib));
-    if (hi == 0) return;
-    const int n_tile = (int)(range.y - range.x);
-    const float* __restrict__ tb = stream + (size_t)range.x * RS;
-    const uint32_t* __restrict__ qi = quad_list + ((size_t)range.x * 5 + (size_t)wave * n_tile);
-    const int n_kept = (int)qcount[tile * 5 + 4];
-    const uint32_t lim = n_kept > 0 ? (uint32_t)n_kept - 1u : 0u;
-    auto rec_at = [&](uint32_t i) { return tb + (size_t)(min(i, lim) * (uint32_t)RS); };
-    RecordPrefetch pf;
-    pf.issue(tb, n_kept, RS, tid, pf_lines & 0xFF);
-
-    // the whole reduction is rank one: every slot goes through the matrix cores (RankOneFold above)
-    RankOneFold<NS, 0, GS, ACC, true> fold;       // channels F0..C-1 -> slots 0..NS-1 (feat-only layout, first half)
-    fold.skip_atomics = (pf_lines & 0x100) != 0;
-    fold.init(&s_fold[wave], lane, tx, ty, wave, W, H,
-              [&](int n, size_t p) { return dL_dcolor[(size_t)(F0 + n) * plane + p]; });
-    float T = 1.0f;
-
-    auto consume = [&](const StreamRec<C>& rec_j, int idx) {
-        const f8 cur = rec_j.g;
-        const float dx = cur[0] - fx, dy = cur[1] - fy;
-        const float power = blend_power(cur[2], cur[4], cur[3], dx, dy);
-        const bool near = fabsf(power + cur[5]) <= cur[5], reached = idx < last_contrib;   // pixels past their last contributor: no
-        const bool cand = near && reached;
-        const uint64_t cand_mask = __ballot(near) & __ballot(reached);
-        if (cand_mask == 0ull) return;
-        const float alpha = fminf(0.99f, cur[6] * __expf(power));
-        const bool act = cand && alpha >= kAlphaMin;
-        if ((__ballot(alpha >= kAlphaMin) & cand_mask) != 0ull) {
-            const float al = act ? alpha : 0.f;
-            const float w = al * T;
-            T = T * (1.0f - al);
-            fold.push(w, __float_as_uint(cur[7]), grad_rec, lane);
-        }
-    };
-    // front-to-back over the quadrant's index stream, batches of two records with pinned scalar waits (blend_fwd.hip)
-    StreamRec<C> a0, a1, b0, b1;
-    uint32_t i2 = qi[2], i3 = qi[3], i4 = qi[4], i5 = qi[5];
-    a0.load(rec_at(qi[0]));
-    a1.load(rec_at(qi[1]));
-    for (int j = 0; j < hi; j += 4) {
-        wait_scalar_loads();
-        b0.load(rec_at(i2));
-        b1.load(rec_at(i3));
-        const uint32_t n6 = qi[j + 6], n7 = qi[j + 7], n8 = qi[j + 8], n9 = qi[j + 9];
-        consume(a0, j);
-        if (j + 1 < hi) consume(a1, j + 1);
-        wait_scalar_loads();
-        a0.load(rec_at(i4));
-        a1.load(rec_at(i5));
-        if (j + 2 < hi) consume(b0, j + 2);
-        if (j + 3 < hi) consume(b1, j + 3);
-        i2 = n6; i3 = n7; i4 = n8; i5 = n9;
-    }
-    if (fold.cnt > 0) fold.flush(grad_rec, lane);
-    pf.retire(reinterpret_cast<uint32_t*>(grad_rec), W);
-}
-
-// ---- features-only backward, records through LDS instead of SGPRs (round 3; the default) --------------------------------
-// blend_backward_feat_kernel with ONE change: the wave-uniform record reaches the per-pixel arithmetic as VGPRs (a chunk of 64
-// records gathered by the lanes, parked in LDS, read back with broadcast ds_read_b128) instead of as SGPRs (scalar loads).  Same
-// quadrant walk, same lane occupancy, same fold -- but every vector instruction that read the record now issues at 2 cycles
-// instead of 4 (profiles/r03_valu_issue_price_list.json): 0.449 -> 0.364 ms at the headline workload.  The same change on the
-// FULL backward (geometry + features through LDS, or geometry through LDS and features on the scalar path) measured 0.645 ->
-// 0.648 / 0.69 / 0.77 ms and was not kept: DESIGN.md section 3 item 9.
+// The wave-uniform record reaches the per-pixel arithmetic as VGPRs: a chunk of 64 records gathered by the lanes, parked in
+// LDS, read back with broadcast ds_read_b128.  Every vector instruction that reads the record issues at 2 cycles instead of
+// the 4 of an SGPR operand (profiles/r03_valu_issue_price_list.json): 0.449 -> 0.364 ms at the headline workload against the
+// scalar-load walk.  The same change on the FULL backward (geometry + features through LDS, or geometry through LDS and
+// features on the scalar path) measured 0.645 -> 0.648 / 0.69 / 0.77 ms and was not kept: DESIGN.md section 3 item 9.
 template <int C, int F0, typename ACC>
 __global__ __launch_bounds__(kBlock) void blend_backward_feat_lds_kernel(
     const uint2* __restrict__ ranges, const float* __restrict__ stream, const uint32_t* __restrict__ quad_list, int W,
@@ -711,16 +565,6 @@ __global__ void wave_fold16_test_kernel(const float* __restrict__ in, float* __r
     for (int k = 0; k < 16; ++k) v[k] = in[threadIdx.x * 16 + k];
     out[threadIdx.x] = wave_fold16(v);
 }
-// features-only backward: records through LDS (VGPR operands; default) or, OGS_BLEND_FEAT_LDS=0, through scalar loads
-static bool feat_lds_enabled() {
-    static const bool v = [] { const char* e = getenv("OGS_BLEND_FEAT_LDS"); return !e || atoi(e) != 0; }();
-    return v;
-}
-
-static bool fold_bf16_enabled() {
-    static const bool v = [] { const char* e = getenv("OGS_BLEND_FOLD"); return e && strcmp(e, "bf16") == 0; }();
-    return v;
-}
 
 template <int C>
 int launch_c(const OgsRasterBwdArgs& a, const ImageState& is, void* grad_rec_, hipStream_t s) {
@@ -729,24 +573,16 @@ int launch_c(const OgsRasterBwdArgs& a, const ImageState& is, void* grad_rec_, h
     const int gx = (a.W + kTile - 1) / kTile, gy = (a.H + kTile - 1) / kTile;
     static constexpr const char* const kNames[4] = {"blend_backward_kernel<3>", "blend_backward_kernel<6>",
                                                     "blend_backward_kernel<9>", "blend_backward_kernel<12>"};
-    static constexpr const char* const kFeatNames[4] = {"blend_backward_feat_kernel<3>", "blend_backward_feat_kernel<6>",
-                                                        "blend_backward_feat_kernel<9>", "blend_backward_feat_kernel<12>"};
     const float* stream = (const float*)stream_base<C>(const_cast<void*>(a.sorted_rec));
     const uint32_t* quads = quad_base(const_cast<void*>(a.quad_list));
     const unsigned vtiles = (unsigned)(gx * gy) * (unsigned)num_groups_of(a.num_groups);
     const uint32_t* order = tile_order_of(is, vtiles, a.P);     // the forward's heaviest-first order (blend_fwd.hip)
     if (backward_is_features_only(a)) {
         // only dL/dcolors_precomp is owed (stages >= 1, train.py:431-436): no alpha recursion, no geometry partials
-    static constexpr const char* const kFeatLdsNames[4] = {"blend_backward_feat_lds_kernel<3>", "blend_backward_feat_lds_kernel<6>",
-                                                           "blend_backward_feat_lds_kernel<9>", "blend_backward_feat_lds_kernel<12>"};
-    const bool feat_lds = feat_lds_enabled();
+        static constexpr const char* const kFeatLdsNames[4] = {"blend_backward_feat_lds_kernel<3>", "blend_backward_feat_lds_kernel<6>",
+                                                               "blend_backward_feat_lds_kernel<9>", "blend_backward_feat_lds_kernel<12>"};
 #define OGS_BWD_FEAT(F0V)                                                                                             \
-    if (feat_lds)                                                                                                     \
     OGS_LAUNCH_NAMED(chan_name<C>(kFeatLdsNames), (blend_backward_feat_lds_kernel<C, F0V, ACC>), dim3(vtiles), dim3(kBlock), 0, \
-                     s, (const uint2*)is.ranges, stream, quads, a.W, a.H, gx, gx * gy, (const uint32_t*)is.n_contrib,    \
-                     (const uint32_t*)is.qcount, a.dL_dcolor, grad_rec, blend_prefetch_lines(), order);                \
-    else                                                                                                              \
-    OGS_LAUNCH_NAMED(chan_name<C>(kFeatNames), (blend_backward_feat_kernel<C, F0V, ACC>), dim3(vtiles), dim3(kBlock), 0, \
                      s, (const uint2*)is.ranges, stream, quads, a.W, a.H, gx, gx * gy, (const uint32_t*)is.n_contrib,    \
                      (const uint32_t*)is.qcount, a.dL_dcolor, grad_rec, blend_prefetch_lines(), order)
         if constexpr (C > 3) {
@@ -758,17 +594,8 @@ int launch_c(const OgsRasterBwdArgs& a, const ImageState& is, void* grad_rec_, h
         OGS_LAUNCH_CHECK(a.debug, s);
         return OGS_OK;
     }
-    // the fold's product: exact fp32 on v_mfma_f32_16x16x4_f32 (default) or, OGS_BLEND_FOLD=bf16, a two-term bf16 split on
-    // v_mfma_f32_16x16x32_bf16 (round 4 a; kept for the alternative-kernel parity test and A-B timing)
-    const bool bf16 = fold_bf16_enabled();
 #define OGS_BWD_LAUNCH(GCV, DEPTHV)                                                                                  \
-    if (bf16)                                                                                                        \
-    OGS_LAUNCH_NAMED(chan_name<C>(kNames), (blend_backward_kernel<C, GCV, DEPTHV, true>), dim3(vtiles), dim3(kBlock), 0, s, \
-                     (const uint2*)is.ranges, stream, quads, a.W, a.H, gx, gx * gy, a.bg, (const float*)is.final_T,                  \
-                     (const uint32_t*)is.n_contrib, (const uint32_t*)is.qcount, a.dL_dcolor, a.dL_ddepth, a.dL_dalpha, grad_rec,  \
-                     blend_prefetch_lines(), order);                                                                 \
-    else                                                                                                             \
-    OGS_LAUNCH_NAMED(chan_name<C>(kNames), (blend_backward_kernel<C, GCV, DEPTHV, false>), dim3(vtiles), dim3(kBlock), 0, s, \
+    OGS_LAUNCH_NAMED(chan_name<C>(kNames), (blend_backward_kernel<C, GCV, DEPTHV>), dim3(vtiles), dim3(kBlock), 0, s,        \
                      (const uint2*)is.ranges, stream, quads, a.W, a.H, gx, gx * gy, a.bg, (const float*)is.final_T,                  \
                      (const uint32_t*)is.n_contrib, (const uint32_t*)is.qcount, a.dL_dcolor, a.dL_ddepth, a.dL_dalpha, grad_rec,  \
                      blend_prefetch_lines(), order)

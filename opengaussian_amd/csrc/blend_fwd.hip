@@ -1,28 +1,19 @@
-// Forward front-to-back alpha blend for gfx950 -- scalar-path design over
-// per-quadrant compacted index streams.
+// Forward front-to-back alpha blend for gfx950 over per-quadrant compacted index streams.
 //
-// History (profiles/): (v1) the classic "stage 256 Gaussians in LDS, every pixel thread
-// re-reads them" loop; (v2) the staged data is wave-uniform, so it moved to the SCALAR path: packed records
-// read with s_load into SGPRs, no LDS, no barriers; (v3) SQ counters showed the loop SALU-bound -> branch-free
-// body; (v4) measured on the bench scene only 48 % of the reference's (Gaussian, tile) list entries can reach
-// alpha >= 1/255 on ANY pixel of their tile and only 28 % of the (entry, 8x8 quadrant) pairs -- the reference's
-// tile rect is the square around ceil(3 sigma_max) -> per-quadrant streams; (v9, this file) the streams hold
-// 4-byte indices and every record is stored once per tile entry.
-//
-//   1. pack_sorted_kernel: one workgroup per tile walks the tile's sorted list, gathers the geometry half of
-//      each Gaussian's record (the only random reads of the pass), runs an EXACT conservative test per 8x8
-//      quadrant (maximum of the Gaussian's quadratic form over the quadrant's pixel box vs
-//      ln(1/(255*opacity)) - margin) and appends the entry's tile-local INDEX to the stream of every quadrant it
-//      can reach; a surviving entry gathers its feature half and writes one packed record at its own list
-//      position.  Depth order inside a quadrant stream is preserved with a block-wide prefix sum over four
-//      16-bit counters packed in one u64.  The reference-visible binning state (sorted keys, point list, tile
-//      ranges) is untouched and stays bit-exact; dropped entries are exactly those every lane of the quadrant
-//      would have skipped.
-//   2. blend_forward_kernel: one workgroup per tile, each wave64 owns one quadrant and walks ITS index stream;
-//      indices and records are fetched with wave-uniform scalar loads (s_load_dwordx2, then s_load_dwordx16 + x2
-//      -> SGPR operands of the per-pixel VALU math), records two entries ahead of their use.  ~3.6x fewer loop
-//      trips than walking the tile list, nearly all of them doing useful blending; the four waves of a tile
-//      share the records in the scalar cache.
+// Measured on the bench scene, only 48 % of the reference's (Gaussian, tile) list entries can reach alpha >= 1/255 on ANY
+// pixel of their tile and only 28 % of the (entry, 8x8 quadrant) pairs: the reference's tile rect is the square around
+// ceil(3 sigma_max).  So a pass PACKS each tile's sorted list before it blends it:
+//   * pack: an EXACT conservative test per 8x8 quadrant (maximum of the Gaussian's quadratic form over the quadrant's pixel
+//     box vs ln(1/(255*opacity)) - margin); a surviving entry gathers its record and writes ONE packed copy at its
+//     compact position, and its compact index is appended to the index stream of every quadrant it can reach.  Depth
+//     order inside a stream is preserved with a block-wide prefix sum over per-quadrant counters packed in one u64.  The
+//     reference-visible binning state (sorted keys, point list, tile ranges) is untouched and stays bit-exact; dropped
+//     entries are exactly those every lane of the quadrant would have skipped.
+//   * blend: each wave64 owns one quadrant and walks its index stream in chunks of 64 entries, per 4x4 pixel block
+//     (blend_rows_tile), with every operand of the per-pixel arithmetic in VGPRs.
+// pack_blend_chunked_kernel does both for a tile in one workgroup, chunk by chunk, and stops when every pixel is done (the
+// default forward).  blend_forward_rows_kernel blends streams that are already packed: a pass with an empty list, and the
+// re-blend of a kept pass.  DESIGN.md section 3 has the history of this design and of the kernels it replaced.
 // No MFMA: the loop is a per-pixel recurrence, not a contraction.
 #include "ogs_common.h"
 
@@ -45,259 +36,11 @@ __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
 //   [8..8+C) features  [8+C] view depth, rest zero padding to a multiple of 4 floats.
 // The depth sits right behind the features so that the (feature, feature) / (feature, depth) operand pairs of
 // the blend loops' packed FMAs are even-aligned SGPR pairs straight out of s_load (no s_mov shuffles).
-// shared memory of the pack phase: carved out of one raw buffer so that the fused pack + blend kernel can reuse it
-template <int C>
-struct PackLds {
-    uint64_t wave_tot[kBlock / kWave];
-    float4 s_rec[kBlock * stream_vec4(C)];
-};
 
-// one tile: running[0..3] = entries kept per quadrant, running[4] = records kept by the tile (block-uniform on return)
-template <int C>
-__device__ __forceinline__ void pack_tile(const uint2 range, const uint32_t* __restrict__ point_list, int gx, int timg,
-                                          const float4* __restrict__ rec, float4* __restrict__ stream,
-                                          uint32_t* __restrict__ quad_list, PackLds<C>& lds, uint32_t (&running)[5]) {
-    constexpr int NV = rec_vec4(C);
-    constexpr int SV = stream_vec4(C);
-    uint64_t* wave_tot = lds.wave_tot;
-    float4* s_rec = lds.s_rec;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = (int)(range.y - range.x);
-    const float X0 = (float)((timg % gx) * kTile), Y0 = (float)((timg / gx) * kTile);
-#pragma unroll
-    for (int q = 0; q < 5; ++q) running[q] = 0u;           // kept entries so far: per quadrant, and by the tile (block-uniform)
-
-    for (int base = 0; base < n; base += kBlock) {
-        const int i = base + tid;
-        uint32_t mask = 0;
-        float4 a = make_float4(0, 0, 0, 0), b = a;
-        float h = 0.f;
-        uint32_t gid_of_thread = 0;
-        // sorted value = Gaussian id | "reaches this tile" << 31: duplicate_kernel ran ONE box test per (Gaussian, tile)
-        // pair while the Gaussian's geometry sat in LDS; nothing is gathered here for the 52 % of the pairs that reach
-        // no pixel of the tile
-        const uint32_t sv = i < n ? point_list[range.x + i] : 0u;
-        if (sv >> kReachBit) {
-            const uint32_t gid = sv & kGidMask;
-            gid_of_thread = gid;
-            const float4* src = rec + (size_t)gid * NV;
-            a = src[0]; b = src[1];              // geometry only: the features are fetched if the entry survives
-            // candidate window thr <= power <= 0, thr = ln(1/(255*opacity)) - margin; stored as h = -thr/2 so the
-            // blend loops test it with ONE compare |power + h| <= h (opacity <= 0: NaN/-inf, never a candidate)
-            h = 0.5f * (__logf(255.0f * b.w) + kThrMargin);
-            const float thr = -2.0f * h;
-            const float nbA = -b.y / b.x, nbC = -b.y / b.z;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float qx = X0 + (float)((q & 1) * 8), qy = Y0 + (float)((q >> 1) * 8);
-                // d = centre - pixel, pixel in [qx, qx+7] x [qy, qy+7]
-                const float m = max_power_in_box(b.x, b.y, b.z, nbA, nbC, a.x - qx - 7.f, a.x - qx, a.y - qy - 7.f, a.y - qy);
-                if (m >= thr) mask |= 1u << q;
-            }
-        }
-        // block-wide exclusive prefix of the four per-quadrant keep flags and of "kept at all" (12-bit fields of one u64)
-        const uint64_t mine = (uint64_t)(mask & 1u) | ((uint64_t)((mask >> 1) & 1u) << 12) |
-                              ((uint64_t)((mask >> 2) & 1u) << 24) | ((uint64_t)((mask >> 3) & 1u) << 36) |
-                              ((uint64_t)(mask != 0u ? 1u : 0u) << 48);
-        uint64_t inc = mine;
-#pragma unroll
-        for (int d = 1; d < kWave; d <<= 1) {
-            const uint64_t t = shfl_up_u64(inc, d);
-            if (lane >= d) inc += t;
-        }
-        if (lane == kWave - 1) wave_tot[wave] = inc;
-        __syncthreads();
-        uint64_t before = 0, total = 0;                    // chunk-local: every 12-bit field <= 256
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) {
-            const uint64_t t = wave_tot[w];
-            if (w < wave) before += t;
-            total += t;
-        }
-        const uint64_t pos = before + inc - mine;          // exclusive position inside this chunk, per quadrant
-        if (mask) {
-            // ONE copy of the record, COMPACTED: kept entry number c of the tile goes to record range.x + c (depth
-            // order preserved).  The chunk's kept records are staged in LDS and written below by the whole workgroup
-            // as one contiguous range (a thread storing its own 16*SV-byte record makes every store instruction touch
-            // 64 different cache lines) ...
-            const uint32_t c_loc = (uint32_t)(pos >> 48) & 0xFFFu;
-            const uint32_t c_idx = running[4] + c_loc;
-            float4* dst = s_rec + c_loc * SV;
-            dst[0] = make_float4(a.x, a.y, -0.5f * b.x, -0.5f * b.z);
-            dst[1] = make_float4(-b.y, h, b.w, __uint_as_float(gid_of_thread));
-            // features (gathered only now: 52 % of the bench scene's entries reach no quadrant), then the view
-            // depth in slot C, zero padding behind it
-            const float4* src = rec + (size_t)gid_of_thread * NV;
-            float f[(SV - 2) * 4];
-#pragma unroll
-            for (int k = 0; k < (SV - 2) * 4; ++k) f[k] = 0.f;
-#pragma unroll
-            for (int v = 0; v < NV - 2; ++v) {
-                const float4 t = src[2 + v];
-                f[4 * v] = t.x; f[4 * v + 1] = t.y; f[4 * v + 2] = t.z; f[4 * v + 3] = t.w;
-            }
-            f[C] = a.z;
-#pragma unroll
-            for (int v = 0; v < SV - 2; ++v) dst[2 + v] = make_float4(f[4 * v], f[4 * v + 1], f[4 * v + 2], f[4 * v + 3]);
-            // ... its compact index appended to the index stream of every quadrant it can reach, and its position in
-            // the tile's full list kept for the n_contrib export
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (mask & (1u << q)) {
-                    const uint32_t p = running[q] + ((uint32_t)(pos >> (12 * q)) & 0xFFFu);
-                    quad_list[(size_t)range.x * 5 + (size_t)q * n + p] = c_idx;
-                }
-            }
-            quad_list[(size_t)range.x * 5 + (size_t)4 * n + c_idx] = (uint32_t)i;
-        }
-        __syncthreads();
-        {
-            const int kept4 = (int)((uint32_t)(total >> 48) & 0xFFFu) * SV;
-            float4* __restrict__ out = stream + ((size_t)range.x + (size_t)running[4]) * SV;
-            for (int e = tid; e < kept4; e += kBlock) out[e] = s_rec[e];
-        }
-#pragma unroll
-        for (int q = 0; q < 5; ++q) running[q] += (uint32_t)(total >> (12 * q)) & 0xFFFu;
-        __syncthreads();
-    }
-}
-
-template <int C>
-__global__ __launch_bounds__(kBlock) void pack_sorted_kernel(const uint2* __restrict__ ranges,
-                                                             const uint32_t* __restrict__ point_list, int gx,
-                                                             int tiles, const float4* __restrict__ rec,
-                                                             float4* __restrict__ stream,
-                                                             uint32_t* __restrict__ quad_list,
-                                                             uint32_t* __restrict__ qcount,
-                                                             const uint32_t* __restrict__ tile_order) {
-    __shared__ PackLds<C> lds;
-    const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;   // virtual tile: image (group) * tiles + tile in the image
-    uint32_t running[5];
-    pack_tile<C>(ranges[tile], point_list, gx, tile % tiles, rec, stream, quad_list, lds, running);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) qcount[tile * 5 + q] = running[q];
-    }
-}
-
-template <int C>
-__global__ __launch_bounds__(kBlock) void blend_forward_kernel(
-    const uint2* __restrict__ ranges, const uint32_t* __restrict__ qcount, const float* __restrict__ stream,
-    const uint32_t* __restrict__ quad_list, int W, int H, int gx, int tiles, const float* __restrict__ bg, float* __restrict__ out_color,
-    float* __restrict__ out_depth, float* __restrict__ out_alpha, uint32_t* __restrict__ n_contrib,
-    float* __restrict__ final_T, int pf_lines, const uint32_t* __restrict__ tile_order) {
-    constexpr int RS = stream_vec4(C) * 4;      // floats per stream record
-    const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;   // virtual tile (grouped pass): image * tiles + tile in the image
-    const int img = tile / tiles, timg = tile - img * tiles;
-    const int tx = timg % gx, ty = timg / gx;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int px = tx * kTile + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * kTile + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float fx = (float)px, fy = (float)py;
-
-    const uint2 range = ranges[tile];
-    const int n_tile = (int)(range.y - range.x);
-    const int n = (int)qcount[tile * 5 + wave];                        // this quadrant's kept entries
-    const int n_kept = (int)qcount[tile * 5 + 4];                      // records the tile keeps (compacted)
-    const float* __restrict__ tb = stream + (size_t)range.x * RS;                                    // tile's records
-    const uint32_t* __restrict__ qi = quad_list + ((size_t)range.x * 5 + (size_t)wave * n_tile);     // quadrant's indices
-    const uint32_t lim = n_kept > 0 ? (uint32_t)n_kept - 1u : 0u;
-    // index -> record address; whatever the two-ahead prefetch reads past the end of the region is clamped
-    auto rec_at = [&](uint32_t i) { return tb + (size_t)(min(i, lim) * (uint32_t)RS); };
-    RecordPrefetch pf;
-    pf.issue(tb, n_kept, RS, tid, pf_lines);
-
-    // The loop is written to be SCALAR-ALU frugal (rocprof: the first version issued more SALU than VALU
-    // instructions -- one scalar unit per CU -- because every nested divergent `if` costs exec-mask ops):
-    //   * a finished / outside pixel is "parked" far away (fxe = kFar): its power becomes hugely negative and
-    //     the single candidate compare fails, so no `done` flag enters the control flow;
-    //   * candidate test thr <= power <= 0 is ONE compare: |power + h| <= h with h = -thr/2 from the stream;
-    //   * inside the (single) divergent region everything is selects, not branches;
-    //   * no break / continue (hipcc's structurizer turns them into a scalar state machine): `all_done` is a
-    //     wave-uniform flag in the loop condition; entries are consumed in pairs from two ping-pong records,
-    //     so "current = next" costs no register moves.
-    float fxe = inside ? fx : kFar;
-    float T = 1.0f;
-    // accumulators of (feature 0..C-1, depth) as register pairs: one v_pk_fma_f32 per pair and entry
-    constexpr int NPF = (C + 2) / 2;
-    v2f accp[NPF];
-#pragma unroll
-    for (int k = 0; k < NPF; ++k) accp[k] = (v2f){0.f, 0.f};
-    float wacc = 0.f;
-    uint32_t last = 0;
-    bool all_done = false;
-
-    auto consume = [&](const StreamRec<C>& rec_j, int j) {
-        const f8 cur = rec_j.g;
-        const float dx = cur[0] - fxe, dy = cur[1] - fy;
-        const float power = blend_power(cur[2], cur[4], cur[3], dx, dy);
-        const bool cand = fabsf(power + cur[5]) <= cur[5];
-        if (__ballot(cand) != 0ull) {
-            bool stop = false;
-            if (cand) {
-                float alpha = fminf(0.99f, cur[6] * __expf(power));
-                alpha = alpha >= kAlphaMin ? alpha : 0.f;
-                const float test_T = T * (1.0f - alpha);
-                stop = test_T < 0.0001f;                       // this entry is NOT applied (A.3)
-                const float w = stop ? 0.f : alpha * T;
-                const v2f w2 = {w, w};
-#pragma unroll
-                for (int k = 0; k < NPF; ++k)       // explicit FMA (the tiny pass reproduces these bits)
-                    accp[k] = __builtin_elementwise_fma((v2f){rec_j.feat(2 * k), rec_j.feat(2 * k + 1)}, w2, accp[k]);
-                wacc += w;
-                T = stop ? T : test_T;
-                last = w > 0.f ? (uint32_t)j + 1u : last;
-                fxe = stop ? kFar : fxe;
-            }
-            if (__ballot(stop) != 0ull) all_done = __ballot(fxe < kFarTest) == 0ull;   // whole wave finished?
-        }
-    };
-    // Software pipeline over the wave-uniform index stream, in BATCHES of two records.  SMEM returns out of order,
-    // so the only wait there is is lgkmcnt(0) = "everything in flight": a wait placed after a load covers that
-    // load too.  Hence: wait (batch issued two entries ago) -> issue the NEXT batch -> blend two entries.  Every
-    // record load gets two entries' worth of blending to arrive (SQ counters of the one-ahead version: 53 % of the
-    // forward's wave-cycles parked on s_waitcnt).  Four record register sets = 72 SGPRs.
-    if (n > 0) {
-        StreamRec<C> a0, a1, b0, b1;
-        uint32_t i2 = qi[2], i3 = qi[3], i4 = qi[4], i5 = qi[5];
-        a0.load(rec_at(qi[0]));
-        a1.load(rec_at(qi[1]));
-        for (int j = 0; j < n && !all_done; j += 4) {
-            wait_scalar_loads();
-            b0.load(rec_at(i2));
-            b1.load(rec_at(i3));
-            const uint32_t n6 = qi[j + 6], n7 = qi[j + 7], n8 = qi[j + 8], n9 = qi[j + 9];
-            consume(a0, j);
-            if (j + 1 < n) consume(a1, j + 1);
-            wait_scalar_loads();
-            a0.load(rec_at(i4));
-            a1.load(rec_at(i5));
-            if (j + 2 < n) consume(b0, j + 2);
-            if (j + 3 < n) consume(b1, j + 3);
-            i2 = n6; i3 = n7; i4 = n8; i5 = n9;
-        }
-    }
-
-    if (inside) {
-        const size_t plane = (size_t)W * H;
-        const size_t pix = (size_t)img * plane + (size_t)py * W + px;       // pixel of image `img`
-        float* oc = out_color + (size_t)img * (C - 1) * plane;               // + pix: image stride is C planes
-#pragma unroll
-        for (int c = 0; c < C; ++c) oc[c * plane + pix] = ((c & 1) ? accp[c / 2].y : accp[c / 2].x) + T * bg[c];
-        out_depth[pix] = (C & 1) ? accp[C / 2].y : accp[C / 2].x;
-        out_alpha[pix] = wacc;
-        n_contrib[pix] = last;          // index into the QUADRANT stream (+1); see export_n_contrib_kernel
-        final_T[pix] = T;               // the backward starts its T recursion from this, not from 1 - alpha
-    }
-    pf.retire(n_contrib, W);
-}
-
-// ---- forward blend, one list per 4x4 pixel block (round 3) -------------------------------------------------------------
-// The quadrant walk above keeps ~51 % of its lanes busy (an entry that reaches an 8x8 quadrant touches half of its pixels
-// on average) and pays 4 issue cycles for nearly every vector instruction, because the entry's record sits in SGPRs
-// (profiles/r03_valu_issue_price_list.json: any SGPR operand halves the issue rate).  Here a wave still owns a quadrant
-// and walks the same quadrant index stream, but in CHUNKS of 64 entries:
+// ---- forward blend, one list per 4x4 pixel block ----------------------------------------------------------------------
+// A wave owns a quadrant and walks its index stream in CHUNKS of 64 entries.  (Walking it one entry at a time with the
+// record in SGPRs keeps ~51 % of the lanes busy and pays 4 issue cycles for nearly every vector instruction:
+// profiles/r03_valu_issue_price_list.json, any SGPR operand halves the issue rate.)
 //   1. lane e gathers record e of the chunk with vector loads (L2 hits: the prefetch at kernel entry pulled the tile's
 //      records in), tests it against the four 4x4 blocks of the quadrant (the exact box-vs-ellipse test of pack, on a
 //      4x4 box) and parks the record in the wave's LDS region;
@@ -305,10 +48,10 @@ __global__ __launch_bounds__(kBlock) void blend_forward_kernel(
 //   3. the four rows of the wave -- row r = the 16 pixels of block r -- walk THEIR lists side by side: per step a row reads
 //      its next record from LDS into VGPRs (four different records per ds_read_b128, one LDS cycle per row) and every
 //      operand of the per-pixel arithmetic is a VGPR.
-// The arithmetic per (pixel, entry) is the quadrant kernel's, in the same order (blend_power, the same candidate window,
-// the same FMAs): a skipped (entry, block) pair is one every pixel of the block would have skipped, so images,
-// n_contrib (still the 1-based position in the QUADRANT stream: the backward kernels are unchanged) and final_T are bit
-// for bit those of blend_forward_kernel.
+// A skipped (entry, block) pair is one every pixel of the block would have skipped.  n_contrib is the 1-based position of
+// the pixel's last contributor in the QUADRANT stream (the backward walks the same streams).  A finished or outside pixel is
+// parked far away (fxe = kFar): its power becomes hugely negative and the candidate compare fails, so no `done` flag enters
+// the control flow; `all_done` is a wave-uniform flag in the loop condition.
 template <int C>
 struct RowRec {          // one record in VGPRs
     static constexpr int NV4 = stream_vec4(C);
@@ -514,54 +257,21 @@ __global__ __launch_bounds__(kBlock) void blend_forward_rows_kernel(
                            bg, out_color, out_depth, out_alpha, n_contrib, final_T, pf_lines, lds, feats);
 }
 
-// ---- pack + forward blend of a tile in ONE workgroup (round 3) -------------------------------------------------------
-// pack_sorted_kernel is bound by the latency of its gathers (61 % of the HBM peak, little arithmetic), the blend by vector
-// issue: run back to back they leave the other resource idle in turn.  Here a workgroup packs ITS tile -- same code, same
-// global outputs (the backward reads the compacted records, the quadrant streams and the counts) -- and blends it right
-// away from the records it just wrote (its own CU's L2 / L1: __syncthreads orders them at workgroup scope), so that on every
-// CU some workgroups gather while others blend.  One launch less, and the counts travel in registers.
-template <int C>
-__global__ __launch_bounds__(kBlock) void pack_blend_forward_kernel(
-    const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const float4* __restrict__ rec,
-    float4* __restrict__ stream, uint32_t* __restrict__ quad_list, uint32_t* __restrict__ qcount, int W, int H, int gx, int tiles,
-    const float* __restrict__ bg, float* __restrict__ out_color, float* __restrict__ out_depth, float* __restrict__ out_alpha,
-    uint32_t* __restrict__ n_contrib, float* __restrict__ final_T, const uint32_t* __restrict__ tile_order) {
-    constexpr size_t kBytes = sizeof(PackLds<C>) > sizeof(RowsLds<C>) ? sizeof(PackLds<C>) : sizeof(RowsLds<C>);
-    __shared__ __attribute__((aligned(16))) unsigned char raw[kBytes];
-    const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;
-    const int img = tile / tiles, timg = tile - img * tiles;
-    const uint2 range = ranges[tile];
-    uint32_t running[5];
-    pack_tile<C>(range, point_list, gx, timg, rec, stream, quad_list, *reinterpret_cast<PackLds<C>*>(raw), running);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) qcount[tile * 5 + q] = running[q];
-    }
-    __syncthreads();        // the tile's records and index streams are written (workgroup-scope release / acquire); LDS changes hands
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int n = (int)(wave == 0 ? running[0] : wave == 1 ? running[1] : wave == 2 ? running[2] : running[3]);
-    blend_rows_tile<C>(range, n, (int)running[4], reinterpret_cast<const float*>(stream), quad_list, W, H, gx, img, timg, bg, out_color,
-                       out_depth, out_alpha, n_contrib, final_T, 0, *reinterpret_cast<RowsLds<C>*>(raw));
-}
-
-// ---- pack + forward blend of a tile, CHUNK BY CHUNK with a workgroup-wide exit (round 4; the default) ----------------------
+// ---- pack + forward blend of a tile, CHUNK BY CHUNK with a workgroup-wide exit (the default forward) -------------------
 // The reference's forward fetches a tile's list 256 entries at a time and the whole block stops once every pixel is done
-// (SURVEY.md section 2.1 `renderCUDA`, Appendix A.3).  pack_blend_forward_kernel above packed the tile's ENTIRE list -- box
-// tests, 80-byte record gathers, index streams, record write-back -- before the first pixel was blended, although on a
-// ScanNet-class view (2 M Gaussians behind a 648 x 484 image, culled tile lists of ~3 000 entries) the last contributor of any
-// pixel sits at 15 % of its tile's list (scripts/list_depth_stats.py -> profiles/r04_list_depth.json; 77 % at the headline
-// workload).  Here the tile's list is taken in chunks of 256 entries:
-//     pack the chunk (pack_tile's body: quadrant box tests, block scan, kept records staged in LDS, index streams and records
-//     written out for the backward) -> barrier -> every wave blends the entries the chunk ADDED to its quadrant's stream,
-//     reading the records from the LDS staging itself -> the four waves vote; the workgroup leaves the list when every
-//     pixel of the tile is done.
-// What that changes besides the exit: the blend no longer re-reads the records it has just written (round 3: global stores,
-// then vector loads of the same lines + a wave-private LDS copy; VERDICT r3 weak 7: 2.1 x the algorithmic bytes) -- the
-// per-4x4-block walk takes them from the chunk's staging buffer, which all four waves share read-only between two barriers.
-// Per (pixel, entry) the arithmetic is blend_rows_tile's, in the same order: images, n_contrib (1-based position in the
-// quadrant stream) and final_T are bit for bit the unchunked kernels'.  qcount holds the counts AT THE EXIT: the backward
-// (which starts from n_contrib) and the n_contrib export never look past them; entries behind the exit are neither packed
-// nor written.
+// (SURVEY.md section 2.1 `renderCUDA`, Appendix A.3).  On a ScanNet-class view (2 M Gaussians behind a 648 x 484 image, culled
+// tile lists of ~3 000 entries) the last contributor of any pixel sits at 15 % of its tile's list
+// (scripts/list_depth_stats.py -> profiles/r04_list_depth.json; 77 % at the headline workload), so packing the whole list
+// before the first pixel is blended does mostly wasted work.  Here the tile's list is taken in chunks of 256 entries:
+//     pack the chunk (quadrant box tests, block scan, kept records staged in LDS, index streams and records written out for
+//     the backward) -> barrier -> every wave blends the entries the chunk ADDED to its quadrant's stream, reading the
+//     records from the LDS staging itself -> the four waves vote; the workgroup leaves the list when every pixel of the
+//     tile is done.
+// The blend takes the records from the chunk's staging buffer, which all four waves share read-only between two barriers,
+// instead of re-reading the records it has just written.  Per (pixel, entry) the arithmetic is blend_rows_tile's, in the
+// same order: images, n_contrib (1-based position in the quadrant stream) and final_T are bit for bit what
+// blend_forward_rows_kernel gives on the packed streams.  qcount holds the counts AT THE EXIT: the backward (which starts
+// from n_contrib) and the n_contrib export never look past them; entries behind the exit are neither packed nor written.
 template <int C>
 struct ChunkLds {
     static constexpr int SV = stream_vec4(C);
@@ -672,18 +382,22 @@ void pack_blend_chunked_kernel(
     const float bx0 = (float)qx0, by0 = (float)qy0;
 
     for (int base = 0; base < n; base += kBlock) {
-        // ================= pack the chunk (pack_tile's body) =================
+        // ================= pack the chunk =================
         const int i = base + tid;
         uint32_t mask = 0;
         float4 a = make_float4(0, 0, 0, 0), b = a;
         float h = 0.f;
         uint32_t gid_of_thread = 0;
+        // sorted value = Gaussian id | "reaches this tile" << 31: duplicate_kernel ran ONE box test per (Gaussian, tile) pair,
+        // so nothing is gathered here for the pairs that reach no pixel of the tile
         const uint32_t sv = i < n ? point_list[range.x + i] : 0u;
         if (sv >> kReachBit) {
             const uint32_t gid = sv & kGidMask;
             gid_of_thread = gid;
             const float4* src = rec + (size_t)gid * NV;
-            a = src[0]; b = src[1];
+            a = src[0]; b = src[1];              // geometry only: the features are fetched if the entry survives
+            // candidate window thr <= power <= 0, thr = ln(1/(255*opacity)) - margin; stored as h = -thr/2 so the blend loops
+            // test it with ONE compare |power + h| <= h (opacity <= 0: NaN/-inf, never a candidate)
             h = 0.5f * (__logf(255.0f * b.w) + kThrMargin);
             const float thr = -2.0f * h;
             const float nbA = -b.y / b.x, nbC = -b.y / b.z;
@@ -694,6 +408,7 @@ void pack_blend_chunked_kernel(
                 if (m >= thr) mask |= 1u << q;
             }
         }
+        // block-wide exclusive prefix of the four per-quadrant keep flags and of "kept at all" (12-bit fields of one u64)
         const uint64_t mine = (uint64_t)(mask & 1u) | ((uint64_t)((mask >> 1) & 1u) << 12) |
                               ((uint64_t)((mask >> 2) & 1u) << 24) | ((uint64_t)((mask >> 3) & 1u) << 36) |
                               ((uint64_t)(mask != 0u ? 1u : 0u) << 48);
@@ -714,6 +429,9 @@ void pack_blend_chunked_kernel(
         }
         const uint64_t pos = before + inc - mine;
         if (mask) {
+            // ONE copy of the record, COMPACTED (kept entry c of the tile -> record range.x + c, depth order preserved), staged
+            // in LDS; its compact index goes to the index stream of every quadrant it can reach, and its position in the
+            // tile's full list is kept for the n_contrib export
             const uint32_t c_loc = (uint32_t)(pos >> 48) & 0xFFFu;
             const uint32_t c_idx = running[4] + c_loc;
             float4* dst = lds.s_rec + c_loc * SV;
@@ -861,8 +579,8 @@ __global__ __launch_bounds__(kBlock) void export_n_contrib_kernel(const uint2* _
 // Tiny pass (P <= kTinyMaxP, see preprocess_fwd.hip::tiny_geometry_kernel): no duplicate / sort / ranges / pack.  One
 // workgroup per tile walks the P depth-sorted Gaussians, keeps those whose tile rect (A.1 step 8) covers the tile --
 // exactly the reference's tile list, in its order -- stages their blend records in LDS and blends them with the
-// same arithmetic as blend_forward_kernel (same record fields, same FMA shapes), so the images equal the streaming
-// path's bit for bit.  2 launches per pass instead of ~25; nothing is kept for a backward pass (the facade
+// per-pixel arithmetic of the streaming forward (blend_power, the same candidate window, the same FMAs), so the images
+// equal the streaming path's bit for bit.  2 launches per pass instead of ~25; nothing is kept for a backward pass (the facade
 // re-renders through the streaming path if backward() is ever called on a tiny pass).
 template <int C>
 __global__ __launch_bounds__(kBlock) void tiny_blend_kernel(int P, const uint32_t* __restrict__ order,
@@ -932,7 +650,7 @@ __global__ __launch_bounds__(kBlock) void tiny_blend_kernel(int P, const uint32_
     }
     __syncthreads();
 
-    // ---- blend (A.3), one pixel per thread, same arithmetic as blend_forward_kernel::consume ------------------
+    // ---- blend (A.3), one pixel per thread, same arithmetic as blend_rows_tile's consume ----------------------
     const int px = tx * kTile + (wave & 1) * 8 + (lane & 7);
     const int py = ty * kTile + (wave >> 1) * 8 + (lane >> 3);
     const bool inside = px < W && py < H;
@@ -1081,26 +799,14 @@ __global__ __launch_bounds__(kOrderThreads) void tile_order_kernel(const uint2* 
     }
 }
 
-// the per-4x4-block forward (blend_forward_rows_kernel) is the default; OGS_BLEND_ROWS=0: the quadrant walk (A-B runs)
-static bool blend_rows_enabled() {
-    static const bool v = [] { const char* e = getenv("OGS_BLEND_ROWS"); return !(e && atoi(e) == 0); }();
-    return v;
-}
-
-// pack and forward blend of a tile in one workgroup: chunk by chunk with a workgroup-wide exit (pack_blend_chunked_kernel, the
-// default); OGS_PACK_FUSED=2: the whole list packed first (pack_blend_forward_kernel, round 3); OGS_PACK_FUSED=0: two launches
-static int pack_fused_mode() {
-    static const int v = [] { const char* e = getenv("OGS_PACK_FUSED"); return e ? atoi(e) : 1; }();
-    return v;
-}
-
+// D > 0: pack and blend in one launch; an empty list: no counts to pack, the stand-alone blend writes the background
 template <int C>
 int launch_c(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& is, int64_t D, hipStream_t s) {
     const int gx = (a.W + kTile - 1) / kTile, gy = (a.H + kTile - 1) / kTile;
     const int tiles = gx * gy;
     const unsigned vtiles = (unsigned)tiles * (unsigned)num_groups_of(a.num_groups);
-    const uint32_t* order = D > 0 ? launch_tile_order(is, vtiles, a.P, s, a.debug) : nullptr;
-    if (D > 0 && blend_rows_enabled() && pack_fused_mode() == 1) {
+    if (D > 0) {
+        const uint32_t* order = launch_tile_order(is, vtiles, a.P, s, a.debug);
         static constexpr const char* const kChunked[4] = {"pack_blend_chunked_kernel<3>", "pack_blend_chunked_kernel<6>",
                                                           "pack_blend_chunked_kernel<9>", "pack_blend_chunked_kernel<12>"};
         OGS_LAUNCH_NAMED(chan_name<C>(kChunked), pack_blend_chunked_kernel<C>, dim3(vtiles), dim3(kBlock), 0, s,
@@ -1110,42 +816,13 @@ int launch_c(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& i
         OGS_LAUNCH_CHECK(a.debug, s);
         return OGS_OK;
     }
-    if (D > 0 && blend_rows_enabled() && pack_fused_mode() != 0) {
-        static constexpr const char* const kFused[4] = {"pack_blend_forward_kernel<3>", "pack_blend_forward_kernel<6>",
-                                                        "pack_blend_forward_kernel<9>", "pack_blend_forward_kernel<12>"};
-        OGS_LAUNCH_NAMED(chan_name<C>(kFused), pack_blend_forward_kernel<C>, dim3(vtiles), dim3(kBlock), 0, s,
-                         (const uint2*)is.ranges, (const uint32_t*)a.point_list, (const float4*)gs.rec, stream_base<C>(a.sorted_rec),
-                         quad_base(a.quad_list), is.qcount, a.W, a.H, gx, tiles, a.bg, a.out_color, a.out_depth, a.out_alpha,
-                         is.n_contrib, is.final_T, order);
-        OGS_LAUNCH_CHECK(a.debug, s);
-        return OGS_OK;
-    }
-    if (D > 0) {
-        static constexpr const char* const kPack[4] = {"pack_sorted_kernel<3>", "pack_sorted_kernel<6>",
-                                                       "pack_sorted_kernel<9>", "pack_sorted_kernel<12>"};
-        OGS_LAUNCH_NAMED(chan_name<C>(kPack), pack_sorted_kernel<C>, dim3(vtiles), dim3(kBlock), 0, s,
-                         (const uint2*)is.ranges, (const uint32_t*)a.point_list, gx, tiles, (const float4*)gs.rec,
-                         stream_base<C>(a.sorted_rec), quad_base(a.quad_list), is.qcount, order);
-        OGS_LAUNCH_CHECK(a.debug, s);
-    } else {
-        OGS_HIP_CHECK(hipMemsetAsync(is.qcount, 0, (size_t)vtiles * 5 * sizeof(uint32_t), s));
-    }
-    static constexpr const char* const kNames[4] = {"blend_forward_kernel<3>", "blend_forward_kernel<6>",
-                                                    "blend_forward_kernel<9>", "blend_forward_kernel<12>"};
-    if (blend_rows_enabled()) {
-        static constexpr const char* const kRows[4] = {"blend_forward_rows_kernel<3>", "blend_forward_rows_kernel<6>",
-                                                       "blend_forward_rows_kernel<9>", "blend_forward_rows_kernel<12>"};
-        OGS_LAUNCH_NAMED(chan_name<C>(kRows), blend_forward_rows_kernel<C>, dim3(vtiles), dim3(kBlock), 0, s,
-                         (const uint2*)is.ranges, (const uint32_t*)is.qcount, (const float*)stream_base<C>(a.sorted_rec),
-                         (const uint32_t*)quad_base(a.quad_list), a.W, a.H, gx, tiles, a.bg, a.out_color, a.out_depth,
-                         a.out_alpha, is.n_contrib, is.final_T, blend_prefetch_lines(), order, (const float*)nullptr);
-        OGS_LAUNCH_CHECK(a.debug, s);
-        return OGS_OK;
-    }
-    OGS_LAUNCH_NAMED(chan_name<C>(kNames), blend_forward_kernel<C>, dim3(vtiles), dim3(kBlock), 0, s,
+    OGS_HIP_CHECK(hipMemsetAsync(is.qcount, 0, (size_t)vtiles * 5 * sizeof(uint32_t), s));
+    static constexpr const char* const kRows[4] = {"blend_forward_rows_kernel<3>", "blend_forward_rows_kernel<6>",
+                                                   "blend_forward_rows_kernel<9>", "blend_forward_rows_kernel<12>"};
+    OGS_LAUNCH_NAMED(chan_name<C>(kRows), blend_forward_rows_kernel<C>, dim3(vtiles), dim3(kBlock), 0, s,
                      (const uint2*)is.ranges, (const uint32_t*)is.qcount, (const float*)stream_base<C>(a.sorted_rec),
                      (const uint32_t*)quad_base(a.quad_list), a.W, a.H, gx, tiles, a.bg, a.out_color, a.out_depth,
-                     a.out_alpha, is.n_contrib, is.final_T, blend_prefetch_lines(), order);
+                     a.out_alpha, is.n_contrib, is.final_T, blend_prefetch_lines(), (const uint32_t*)nullptr, (const float*)nullptr);
     OGS_LAUNCH_CHECK(a.debug, s);
     return OGS_OK;
 }

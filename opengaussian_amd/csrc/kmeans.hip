@@ -11,9 +11,9 @@
 // of the HBM roofline).  Workgroups grid-stride over the points and flush one partial table each; a small
 // second kernel sums the tables in fixed order and applies the reference's count/centre bookkeeping.
 // Algorithmic traffic per iteration: N*4*d bytes read (+ N*8 for the final id write).
-// Shapes outside the MFMA tiling (k > 256 or d > 15) use the LDS-accumulator fallback kernel.
-#include <stdlib.h>
-
+// For the reference's widths (d = 6, 9) the distances run as a GEMM on the bf16 matrix path (k <= 64) and the
+// accumulate folds the one-hot product in bf16 terms (64 < k <= 256).  Shapes outside the MFMA tiling (k > 256 or
+// d > 15) use the LDS-accumulator fallback kernel.  The table at launch_pass names the kernel of every shape.
 #include "ogs_common.h"
 #include "../../include/ogs_kmeans.h"
 
@@ -72,47 +72,17 @@ __device__ __forceinline__ int nearest_centre(const float* __restrict__ rows, in
     return best_id;
 }
 
-// Two points per lane (d compile-time): the nine subtract / multiply-add pairs of a centre are issued as PACKED fp32
-// ops (v_pk_add_f32 / v_pk_fma_f32: two fp32 results per lane and issue slot) over the register pair {x_a[j], x_b[j]}
-// with the centre coordinate -- an SGPR from a scalar load -- broadcast to both halves.  Per centre and point
-// ~11 VALU issue slots instead of ~21; every point still sees exactly the arithmetic of nearest_centre (same
-// operation order, one fma per term), so the ids are identical.
-typedef float v2f_km __attribute__((ext_vector_type(2)));
-template <int DT>
-__device__ __forceinline__ void nearest_centre2(const float* __restrict__ rows, int row_a, int row_b,
-                                                const float* __restrict__ cs, int k_active, int& id_a, int& id_b) {
-    v2f_km x[DT];
-#pragma unroll
-    for (int j = 0; j < DT; ++j) x[j] = v2f_km{rows[row_a * DT + j], rows[row_b * DT + j]};
-    float best_a = 3.4e38f, best_b = 3.4e38f;
-    id_a = 0; id_b = 0;
-#pragma unroll 4
-    for (int c = 0; c < k_active; ++c) {
-        const float* cc = cs + c * DT;
-        v2f_km s = {0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < DT; ++j) {
-            const v2f_km t = x[j] - v2f_km{cc[j], cc[j]};
-            s = __builtin_elementwise_fma(t, t, s);
-        }
-        if (s.x < best_a) { best_a = s.x; id_a = c; }
-        if (s.y < best_b) { best_b = s.y; id_b = c; }
-    }
-}
-
 // ---- MFMA path: CB blocks of 16 clusters (k <= 16*CB), d <= 15 ---------------------------------------------------
 // ACCUM: Lloyd iteration (partials only); otherwise final re-assignment (ids only)
-template <int CB, bool ACCUM, int DT, int PPL>
+template <int CB, bool ACCUM, int DT>
 __global__ __launch_bounds__(kBlock) void kmeans_mfma_pass_kernel(const float* __restrict__ feat, int64_t N, int d,
                                                                   const float* __restrict__ centers, int k,
                                                                   int k_active, int64_t* __restrict__ ids_out,
                                                                   int64_t id_offset, float* __restrict__ partials) {
-    static_assert(PPL == 1 || (PPL == 2 && DT > 0), "two points per lane need a compile-time width");
-    constexpr int ROWS = kBlock * PPL;                  // rows staged per trip
     extern __shared__ float smem[];
     float* cs = smem;                                   // [k*d] centres
-    float* rows = cs + ((k * d + 3) & ~3);              // [ROWS*d] staged rows, 16-byte aligned (float4 stores)
-    int* ids_s = reinterpret_cast<int*>(rows + ROWS * d);     // [ROWS] ids of the staged rows (-1: no row)
+    float* rows = cs + ((k * d + 3) & ~3);              // [kBlock*d] staged rows, 16-byte aligned (float4 stores)
+    int* ids_s = reinterpret_cast<int*>(rows + kBlock * d);     // [kBlock] ids of the staged rows (-1: no row)
     float* wtab = rows;                                 // [4][CB*16][16] per-wave tables: epilogue only, reuses `rows`
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < k * d; i += kBlock) cs[i] = centers[i];
@@ -122,19 +92,18 @@ __global__ __launch_bounds__(kBlock) void kmeans_mfma_pass_kernel(const float* _
     __syncthreads();
 
     const int kq = lane >> 4, j = lane & 15;            // MFMA operand coordinates of this lane
-    const int64_t nblk = (N + ROWS - 1) / ROWS;
+    const int64_t nblk = (N + kBlock - 1) / kBlock;
     for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-        const int64_t row0 = blk * ROWS;
-        const int nrows = (int)min((int64_t)ROWS, N - row0);
+        const int64_t row0 = blk * kBlock;
+        const int nrows = (int)min((int64_t)kBlock, N - row0);
         const float* src = feat + row0 * d;
-        if constexpr (DT > 0 && (ROWS * DT) % 4 == 0) {
+        if constexpr (DT > 0 && (kBlock * DT) % 4 == 0) {
             // Full trips: every thread issues ALL its 16-byte loads before the first LDS store.  (The plain
             // `rows[i] = src[i]` loop ran one dependent load -> store round trip per iteration: 34 sequential HBM
-            // latencies per workgroup and pass -- the pass was bound by that, not by the distance loop: halving the
-            // loop's VALU work with packed math changed nothing until the staging was fixed.)
-            constexpr int NV4 = ROWS * DT / 4;                       // float4s per trip (a trip starts 16-byte aligned)
+            // latencies per workgroup and pass -- the pass was bound by that, not by the distance loop.)
+            constexpr int NV4 = kBlock * DT / 4;                       // float4s per trip (a trip starts 16-byte aligned)
             constexpr int ITER = (NV4 + kBlock - 1) / kBlock;
-            if (nrows == ROWS && (reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
+            if (nrows == kBlock && (reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
                 float4 buf[ITER];
 #pragma unroll
                 for (int it = 0; it < ITER; ++it) {
@@ -153,33 +122,18 @@ __global__ __launch_bounds__(kBlock) void kmeans_mfma_pass_kernel(const float* _
             for (int i = tid; i < nrows * d; i += kBlock) rows[i] = src[i];
         }
         __syncthreads();
-        if constexpr (PPL == 2) {
-            // rows tid and tid + 256: both halves of the register pairs always hold a valid row (a missing second
-            // row re-scores the first one), the surplus id is discarded
-            const int ra = min(tid, nrows - 1), rb = min(tid + kBlock, nrows - 1);
-            int ia, ib;
-            nearest_centre2<DT>(rows, ra, rb, centers, k_active, ia, ib);
-            if (!ACCUM) {
-                if (tid < nrows) ids_out[row0 + tid] = (int64_t)ia + id_offset;
-                if (tid + kBlock < nrows) ids_out[row0 + tid + kBlock] = (int64_t)ib + id_offset;
-            } else {
-                ids_s[tid] = tid < nrows ? ia : -1;
-                ids_s[tid + kBlock] = tid + kBlock < nrows ? ib : -1;
-            }
-        } else {
-            int best_id = -1;
-            if (tid < nrows) {
-                best_id = nearest_centre<DT>(rows, tid, d, DT > 0 ? centers : cs, k_active);
-                if (!ACCUM) ids_out[row0 + tid] = (int64_t)best_id + id_offset;
-            }
-            if (ACCUM) ids_s[tid] = best_id;
+        int best_id = -1;
+        if (tid < nrows) {
+            best_id = nearest_centre<DT>(rows, tid, d, DT > 0 ? centers : cs, k_active);
+            if (!ACCUM) ids_out[row0 + tid] = (int64_t)best_id + id_offset;
         }
         if (ACCUM) {
+            ids_s[tid] = best_id;
             __syncthreads();
-            // this wave folds its ROWS / 4 points, 4 per MFMA
+            // this wave folds its kBlock / 4 points, 4 per MFMA
 #pragma unroll 4
-            for (int g = 0; g < ROWS / 16; ++g) {
-                const int p = wave * (ROWS / 4) + g * 4 + kq;
+            for (int g = 0; g < kBlock / 16; ++g) {
+                const int p = wave * (kBlock / 4) + g * 4 + kq;
                 const int id = ids_s[p];
                 float b = 0.f;
                 if (id >= 0) b = j < d ? rows[p * d + j] : (j == d ? 1.0f : 0.f);
@@ -211,112 +165,6 @@ __global__ __launch_bounds__(kBlock) void kmeans_mfma_pass_kernel(const float* _
     }
 }
 
-// ---- accumulate pass, software pipelined --------------------------------------------------------------------------
-// SQ counters of the plain pass (profiles/r02_kmeans_sq_counters_per_launch.json): 75.7 us of VALU issue (the distance
-// loop, at 100 % of the issue slots) + 26 us of matrix-pipe time (the exact-fp32 one-hot MFMAs, at the f32 MFMA peak),
-// back to back because workgroup barriers separate the two phases.  Here the rows are double-buffered in LDS and the
-// MFMAs of trip t-1 are issued INSIDE the distance loop of trip t -- one group of CB MFMAs after every four centres --
-// so the matrix pipe works under the VALU.  Same points in the same order into the same accumulators: the partial
-// tables are bit-identical to the plain kernel's.  (PPL = 1, compile-time width only.)
-template <int CB, int DT>
-__global__ __launch_bounds__(kBlock) void kmeans_accum_pipelined_kernel(const float* __restrict__ feat, int64_t N,
-                                                                        const float* __restrict__ centers, int k,
-                                                                        int k_active, float* __restrict__ partials) {
-    constexpr int d = DT;
-    constexpr int GROUPS = kWave / 4;                    // MFMA groups (4 points each) per wave and trip
-    extern __shared__ float smem[];
-    float* rows0 = smem;                                 // [2][256*d] staged rows, double buffered
-    int* ids0 = reinterpret_cast<int*>(rows0 + 2 * kBlock * d);   // [2][256] ids of the staged rows (-1: no row)
-    float* wtab = rows0;                                 // epilogue only: per-wave tables reuse the rows region
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    floatx4 acc[CB];
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb) acc[cb] = floatx4{0.f, 0.f, 0.f, 0.f};
-    const int kq = lane >> 4, j = lane & 15;
-    const int64_t nblk = (N + kBlock - 1) / kBlock;
-    int buf = 0;
-    bool have_prev = false;
-    auto group = [&](const float* __restrict__ prow, const int* __restrict__ pids, int g) {
-        const int p = wave * kWave + g * 4 + kq;
-        const int id = pids[p];
-        float b = 0.f;
-        if (id >= 0) b = j < d ? prow[p * d + j] : (j == d ? 1.0f : 0.f);
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb) {
-            const float a = (id == cb * 16 + j) ? 1.0f : 0.f;
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc[cb], 0, 0, 0);
-        }
-    };
-    for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-        float* rows = rows0 + buf * kBlock * d;
-        int* ids = ids0 + buf * kBlock;
-        const float* prow = rows0 + (buf ^ 1) * kBlock * d;
-        const int* pids = ids0 + (buf ^ 1) * kBlock;
-        const int64_t row0 = blk * kBlock;
-        const int nrows = (int)min((int64_t)kBlock, N - row0);
-        const float* src = feat + row0 * d;
-        for (int i = tid; i < nrows * d; i += kBlock) rows[i] = src[i];
-        __syncthreads();                 // rows staged; the previous trip's ids are visible
-        const int row = min(tid, nrows - 1);
-        float x[DT];
-#pragma unroll
-        for (int jj = 0; jj < DT; ++jj) x[jj] = rows[row * DT + jj];
-        float best = 3.4e38f;
-        int best_id = 0, g = 0;
-        const int kc = k_active & ~3;
-        for (int c0 = 0; c0 < kc; c0 += 4) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float* cc = centers + (c0 + u) * DT;       // wave-uniform: scalar loads, SGPR operands
-                float s = 0.f;
-#pragma unroll
-                for (int jj = 0; jj < DT; ++jj) {
-                    const float t = x[jj] - cc[jj];
-                    s = fmaf(t, t, s);
-                }
-                if (s < best) { best = s; best_id = c0 + u; }
-            }
-            if (have_prev && g < GROUPS) { group(prow, pids, g); ++g; }
-        }
-        for (int c = kc; c < k_active; ++c) {
-            const float* cc = centers + c * DT;
-            float s = 0.f;
-#pragma unroll
-            for (int jj = 0; jj < DT; ++jj) {
-                const float t = x[jj] - cc[jj];
-                s = fmaf(t, t, s);
-            }
-            if (s < best) { best = s; best_id = c; }
-        }
-        if (have_prev)
-            for (; g < GROUPS; ++g) group(prow, pids, g);
-        ids[tid] = tid < nrows ? best_id : -1;
-        __syncthreads();                 // everyone is done with the previous buffers; this trip's ids are written
-        have_prev = true;
-        buf ^= 1;
-    }
-    if (have_prev) {                     // drain: the last trip's points
-        const float* prow = rows0 + (buf ^ 1) * kBlock * d;
-        const int* pids = ids0 + (buf ^ 1) * kBlock;
-        for (int g = 0; g < GROUPS; ++g) group(prow, pids, g);
-    }
-    __syncthreads();                     // wtab aliases the rows
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            wtab[(wave * CB * 16 + cb * 16 + kq * 4 + r) * 16 + j] = acc[cb][r];
-    __syncthreads();
-    float* out = partials + (size_t)blockIdx.x * k * (d + 1);
-    for (int e = tid; e < k * (d + 1); e += kBlock) {
-        const int c = e / (d + 1), col = e - c * (d + 1);
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) s += wtab[(w * CB * 16 + c) * 16 + col];   // fixed order
-        out[e] = s;
-    }
-}
-
 // ---- accumulate pass with the one-hot product on the bf16 matrix path --------------------------------------------
 // The one-hot accumulate  table[id[p]] += [x_p, 1]  is  onehot^T @ rows.  In exact fp32 (v_mfma_f32_16x16x4_f32) it
 // costs N*k*16*2 flops at the f32 MFMA peak = 26 us at N = 2M, k = 64, and that time ADDS to the VALU time of the
@@ -324,6 +172,8 @@ __global__ __launch_bounds__(kBlock) void kmeans_accum_pipelined_kernel(const fl
 // three bf16 terms hi + mid + lo that carry its 24 significant bits (each residual is exactly representable in
 // fp32), so the same product runs as three v_mfma_f32_16x16x32_bf16 (32 points each, fp32 accumulate) on the
 // 16x faster bf16 path.  Differences to the exact-fp32 table: the rounding of the fp32 accumulation only.
+// The rows are double-buffered in LDS and the MFMAs of trip t-1 are issued INSIDE the distance loop of trip t, so the
+// matrix pipe works under the VALU instead of after a workgroup barrier.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 template <int CB, int DT>
 __global__ __launch_bounds__(kBlock) void kmeans_accum_bf16_kernel(const float* __restrict__ feat, int64_t N,
@@ -891,25 +741,6 @@ __global__ __launch_bounds__(kBlock) void kmeans_gather_kernel(const float* __re
     out[i] = centers[ids[row] * vec_dim + col];
 }
 
-// tuning knobs (A/B timing only): OGS_KM_PPL=2 -> two points per lane on packed fp32 ops (measured: no faster than
-// one -- 115-123 vs 112-118 us per accumulate pass at N = 2M, k = 64, d = 9: the pass is not VALU-issue bound, see
-// DESIGN.md section 4); OGS_KM_BLOCKS=n -> workgroups per pass
-inline int km_ppl() {
-    static const int v = [] { const char* e = getenv("OGS_KM_PPL"); return (e && atoi(e) == 2) ? 2 : 1; }();
-    return v;
-}
-inline int km_pipelined() {     // OGS_KM_PIPE=0: the plain (phase-separated) accumulate pass
-    static const int v = [] { const char* e = getenv("OGS_KM_PIPE"); return (e && atoi(e) == 0) ? 0 : 1; }();
-    return v;
-}
-inline int km_bf16() {          // OGS_KM_BF16=0: the exact-fp32 one-hot MFMAs
-    static const int v = [] { const char* e = getenv("OGS_KM_BF16"); return (e && atoi(e) == 0) ? 0 : 1; }();
-    return v;
-}
-inline int km_max_blocks() {
-    static const int v = [] { const char* e = getenv("OGS_KM_BLOCKS"); const int n = e ? atoi(e) : 0; return n > 0 ? n : kMaxBlocks; }();
-    return v;
-}
 int check_dims(int64_t N, int d, int k) {
     if (N < 0 || d < 1 || d > kMaxD || k < 1 || (int64_t)k * (d + 1) > OGS_KMEANS_MAX_ACC) {
         set_error("kmeans: unsupported sizes N=%lld d=%d k=%d (d <= %d, k*(d+1) <= %d)", (long long)N, d, k, kMaxD,
@@ -919,10 +750,9 @@ int check_dims(int64_t N, int d, int k) {
     return OGS_OK;
 }
 
-int pass_blocks(int64_t N) {      // upper bound over both trip sizes (tmp sizing); workgroups grid-stride anyway
+int pass_blocks(int64_t N) {      // workgroups per pass (also sizes tmp); they grid-stride over the trips
     const int64_t nblk = (N + kBlock - 1) / kBlock;
-    const int mb = km_max_blocks();
-    return (int)(nblk < mb ? (nblk > 0 ? nblk : 1) : mb);
+    return (int)(nblk < kMaxBlocks ? (nblk > 0 ? nblk : 1) : kMaxBlocks);
 }
 
 int cluster_blocks(int d, int k) {       // 0: MFMA tiling not applicable
@@ -930,11 +760,9 @@ int cluster_blocks(int d, int k) {       // 0: MFMA tiling not applicable
     return k <= 16 ? 1 : (k <= 64 ? 4 : 16);
 }
 
-inline int rows_per_trip(int d) { return ((d == 6 || d == 9) && km_ppl() == 2) ? 2 * kBlock : kBlock; }   // compile-time widths: 2 points per lane
 size_t mfma_lds(int d, int k, int CB, bool accum) {
-    const size_t rows = (size_t)rows_per_trip(d);
     // staged rows + ids; the epilogue's per-wave tables reuse the rows region
-    const size_t body = rows * d + rows;
+    const size_t body = (size_t)kBlock * d + kBlock;
     const size_t wtab = accum ? (size_t)4 * CB * 16 * 16 : 0;
     return sizeof(float) * ((((size_t)k * d + 3) & ~(size_t)3) + (body > wtab ? body : wtab));
 }
@@ -951,68 +779,37 @@ int allow_lds(K kernel, size_t bytes) {
     return OGS_OK;
 }
 
-template <int CB, bool ACCUM, int DT, int PPL>
-int launch_mfma_p(int nb, hipStream_t s, const float* feat, int64_t N, int d, const float* centers, int k, int k_active,
-                  int64_t* ids_out, int64_t id_offset, float* partials) {
-    const size_t lds = mfma_lds(d, k, CB, ACCUM);
-    int rc = allow_lds(kmeans_mfma_pass_kernel<CB, ACCUM, DT, PPL>, lds);
-    if (rc != OGS_OK) return rc;
-    OGS_LAUNCH_NAMED(ACCUM ? "kmeans_mfma_pass_kernel<accum>" : "kmeans_mfma_pass_kernel<assign>",
-                     (kmeans_mfma_pass_kernel<CB, ACCUM, DT, PPL>), dim3(nb), dim3(kBlock), lds, s, feat, N, d, centers, k,
-                     k_active, ids_out, id_offset, partials);
-    OGS_LAUNCH_CHECK(0, s);
-    return OGS_OK;
-}
-
-inline int km_gemm() {          // OGS_KM_GEMM=0: the direct-difference distance loop on the VALU (round 2)
-    static const int v = [] { const char* e = getenv("OGS_KM_GEMM"); return (e && atoi(e) == 0) ? 0 : 1; }();
-    return v;
-}
-
 template <int CB, bool ACCUM, int DT>
 int launch_mfma_d(int nb, hipStream_t s, const float* feat, int64_t N, int d, const float* centers, int k, int k_active,
                   int64_t* ids_out, int64_t id_offset, float* partials) {
     if constexpr ((DT == 6 || DT == 9) && CB <= 4) {
-        if (km_gemm()) {
-            const size_t setup = (size_t)k * DT + k + DT;                      // shifted centres, biases, mean (before the first trip)
-            size_t body = (size_t)kBlock * DT + kBlock;
-            const size_t wtab = ACCUM ? (size_t)4 * CB * 16 * 16 : 0;
-            body = body > wtab ? body : wtab;
-            const size_t lds = sizeof(float) * (body > setup ? body : setup);
-            int rc = allow_lds(kmeans_gemm_pass_kernel<CB, ACCUM, DT>, lds);
-            if (rc != OGS_OK) return rc;
-            OGS_LAUNCH_NAMED(ACCUM ? "kmeans_gemm_pass_kernel<accum>" : "kmeans_gemm_pass_kernel<assign>",
-                             (kmeans_gemm_pass_kernel<CB, ACCUM, DT>), dim3(nb), dim3(kBlock), lds, s, feat, N, centers, k,
-                             k_active, ids_out, id_offset, partials);
-            OGS_LAUNCH_CHECK(0, s);
-            return OGS_OK;
-        }
+        const size_t setup = (size_t)k * DT + k + DT;                      // shifted centres, biases, mean (before the first trip)
+        size_t body = (size_t)kBlock * DT + kBlock;
+        const size_t wtab = ACCUM ? (size_t)4 * CB * 16 * 16 : 0;
+        body = body > wtab ? body : wtab;
+        const size_t lds = sizeof(float) * (body > setup ? body : setup);
+        int rc = allow_lds(kmeans_gemm_pass_kernel<CB, ACCUM, DT>, lds);
+        if (rc != OGS_OK) return rc;
+        OGS_LAUNCH_NAMED(ACCUM ? "kmeans_gemm_pass_kernel<accum>" : "kmeans_gemm_pass_kernel<assign>",
+                         (kmeans_gemm_pass_kernel<CB, ACCUM, DT>), dim3(nb), dim3(kBlock), lds, s, feat, N, centers, k,
+                         k_active, ids_out, id_offset, partials);
+    } else if constexpr (DT > 0 && ACCUM) {
+        const size_t rows = (size_t)2 * kBlock * DT + 2 * kBlock, wtab = (size_t)4 * CB * 16 * 16;
+        const size_t lds = sizeof(float) * (rows > wtab ? rows : wtab);
+        int rc = allow_lds(kmeans_accum_bf16_kernel<CB, DT>, lds);
+        if (rc != OGS_OK) return rc;
+        OGS_LAUNCH_NAMED("kmeans_mfma_pass_kernel<accum>", (kmeans_accum_bf16_kernel<CB, DT>), dim3(nb), dim3(kBlock), lds,
+                         s, feat, N, centers, k, k_active, partials);
+    } else {
+        const size_t lds = mfma_lds(d, k, CB, ACCUM);
+        int rc = allow_lds(kmeans_mfma_pass_kernel<CB, ACCUM, DT>, lds);
+        if (rc != OGS_OK) return rc;
+        OGS_LAUNCH_NAMED(ACCUM ? "kmeans_mfma_pass_kernel<accum>" : "kmeans_mfma_pass_kernel<assign>",
+                         (kmeans_mfma_pass_kernel<CB, ACCUM, DT>), dim3(nb), dim3(kBlock), lds, s, feat, N, d, centers, k,
+                         k_active, ids_out, id_offset, partials);
     }
-    if constexpr (DT > 0 && ACCUM) {
-        if (km_ppl() == 1 && km_pipelined()) {
-            const size_t rows = (size_t)2 * kBlock * DT + 2 * kBlock, wtab = (size_t)4 * CB * 16 * 16;
-            const size_t lds = sizeof(float) * (rows > wtab ? rows : wtab);
-            if (km_bf16()) {
-                int rc = allow_lds(kmeans_accum_bf16_kernel<CB, DT>, lds);
-                if (rc != OGS_OK) return rc;
-                OGS_LAUNCH_NAMED("kmeans_mfma_pass_kernel<accum>", (kmeans_accum_bf16_kernel<CB, DT>), dim3(nb), dim3(kBlock), lds,
-                                 s, feat, N, centers, k, k_active, partials);
-                OGS_LAUNCH_CHECK(0, s);
-                return OGS_OK;
-            }
-            int rc = allow_lds(kmeans_accum_pipelined_kernel<CB, DT>, lds);
-            if (rc != OGS_OK) return rc;
-            OGS_LAUNCH_NAMED("kmeans_mfma_pass_kernel<accum>", (kmeans_accum_pipelined_kernel<CB, DT>), dim3(nb), dim3(kBlock), lds,
-                             s, feat, N, centers, k, k_active, partials);
-            OGS_LAUNCH_CHECK(0, s);
-            return OGS_OK;
-        }
-    }
-    if constexpr (DT > 0) {
-        if (km_ppl() == 2)
-            return launch_mfma_p<CB, ACCUM, DT, 2>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials);
-    }
-    return launch_mfma_p<CB, ACCUM, DT, 1>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials);
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
 }
 
 template <int CB, bool ACCUM>
@@ -1025,6 +822,13 @@ int launch_mfma(int nb, hipStream_t s, const float* feat, int64_t N, int d, cons
     }
 }
 
+// One kernel per shape and pass (CB = cluster_blocks(d, k), DT = the compile-time width or 0):
+//
+//   shape                       accumulate pass                      assign pass
+//   d in {6, 9}, k <= 64        kmeans_gemm_pass_kernel              kmeans_gemm_pass_kernel
+//   d in {6, 9}, 64 < k <= 256  kmeans_accum_bf16_kernel             kmeans_mfma_pass_kernel
+//   other d <= 15, k <= 256     kmeans_mfma_pass_kernel<..., DT = 0> kmeans_mfma_pass_kernel<..., DT = 0>
+//   k > 256 or d = 16           kmeans_lds_pass_kernel               kmeans_lds_pass_kernel
 template <bool ACCUM>
 int launch_pass(int nb, hipStream_t s, const float* feat, int64_t N, int d, const float* centers, int k, int k_active,
                 int64_t* ids_out, int64_t id_offset, float* partials) {

@@ -146,7 +146,7 @@ struct StreamRec {
 //            centre inside the blend kernel).  preprocess_bwd.hip re-centres them in fp64 (d = centre - pixel: S0, Sx, Sy,
 //            Sxx, Sxy, Syy) and maps those to dL/dmean2D, dL/dconic, dL/dopacity
 // (blend_bwd.hip: every slot is reduced on the matrix cores).
-// Features-only backward (blend_backward_feat_kernel): channels F0..C-1 sit at slots 0..C-F0-1 (first half only).
+// Features-only backward (blend_backward_feat_lds_kernel): channels F0..C-1 sit at slots 0..C-F0-1 (first half only).
 constexpr int kSlotDepth = 9, kSlotMoments = 10;
 __host__ __device__ constexpr int grad_stride(int C) { return (C + 7 <= 16) ? 16 : 32; }
 // features-only backward: the record of a Gaussian is its NS = C - F0 feature sums alone -- one 64-byte segment when they fit
@@ -392,7 +392,7 @@ int blend_prefetch_lines();     // capi.hip: OGS_BLEND_PREFETCH (default kPrefet
 // Candidate window of the blend loops: thr <= power <= 0 with thr = ln(1 / (255 * opacity)) - kThrMargin, i.e. alpha can
 // reach 1/255 (the margin absorbs the rounding differences between this test and the blend kernels' own evaluation of
 // the power).  duplicate_kernel (preprocess_fwd.hip) tests the whole 16x16 tile once per (Gaussian, tile) pair and
-// flags the pair in the top bit of the sorted value; pack_sorted_kernel (blend_fwd.hip) tests the four 8x8 quadrants
+// flags the pair in the top bit of the sorted value; pack_blend_chunked_kernel (blend_fwd.hip) tests the four 8x8 quadrants
 // of the flagged pairs.
 constexpr float kThrMargin = 0.01f;
 constexpr int kReachBit = 31;                           // Gaussian ids are < 2^31

@@ -477,7 +477,7 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
             const uint32_t tx = (rc & 0xFFFu) + col, ty = (rc >> 12 & 0xFFFu) + row;
             const uint32_t key = s_key0[lo] + ty * (uint32_t)gx + tx;
             // can the Gaussian reach ANY pixel of this tile?  One box test per pair, here, while its geometry sits in
-            // LDS: pack_sorted_kernel then gathers records (and tests the four quadrants) only for the pairs that can
+            // LDS: pack_blend_chunked_kernel then gathers records (and tests the four quadrants) only for the pairs that can
             const float4 c = s_ctr[lo];
             const float4 k = s_con[lo];
             const float X0 = (float)(tx * kTile), Y0 = (float)(ty * kTile);

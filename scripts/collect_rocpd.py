@@ -33,7 +33,6 @@ def short(name):
 READ_PATTERN = {
     "preprocess_kernel": ("coalesced vector loads of the per-Gaussian inputs (SH rows 192 B per lane as 16-byte loads)", True),
     "preprocess_backward_kernel": ("coalesced 16-byte vector loads of inputs + the 128-byte fp64 gradient record", True),
-    "pack_sorted_kernel": ("4-byte point-list stream + 32 / 48-byte record gathers by sorted id (16-byte loads)", True),
     "duplicate_kernel": ("4-byte / 16-byte coalesced loads of the depth-ordered per-Gaussian state", True),
     "radix_hist_kernel": ("4-byte-per-lane coalesced key stream", False),
     "radix_scatter_kernel": ("4-byte-per-lane coalesced key / value streams", False),
@@ -44,15 +43,11 @@ READ_PATTERN = {
     "scan_apply_kernel": ("4-byte-per-lane loads through a gather index", False),
     "tile_ranges_kernel": ("4-byte-per-lane coalesced key stream", False),
     "tile_order_kernel": ("small table", False),
-    "blend_forward_kernel": ("SCALAR loads of the record stream (s_load_dwordx16) + one-dword-per-line vector prefetch touches", False),
     "blend_forward_rows_kernel": ("per-lane 16-byte gathers of 80-byte records (L2 resident after the line-touch prefetch) + the prefetch touches", False),
     "blend_backward_kernel": ("SCALAR loads of the record stream + line touches + per-pixel 4-byte loads; writes are fp64 atomics", False),
-    "blend_backward_feat_kernel": ("SCALAR loads of the record stream + line touches; writes are fp64 atomics", False),
     "blend_backward_feat_lds_kernel": ("per-lane 16-byte gathers of the records' geometry halves + line touches; writes are fp64 atomics", False),
     "pack_blend_chunked_kernel": ("pack's 4-byte point-list stream + 32 / 48-byte record gathers by sorted id (per-lane, random); the records are "
                                   "blended from LDS, the compacted copy and the index streams are written once for the backward", True),
-    "pack_blend_forward_kernel": ("pack's 4-byte point-list stream + 32 / 48-byte record gathers by sorted id, then per-lane 16-byte gathers "
-                                  "of the records the workgroup just wrote (L2 / L1 resident)", True),
 }
 
 

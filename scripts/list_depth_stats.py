@@ -10,8 +10,7 @@ of a default (culled-binning) pass:
     packed(t) = records the chunked forward really packed before its workgroup-wide exit (qcount[t][4]) -- equals the number of
                 records the tile's list keeps when the tile ran to the end of its list
 
-and the work-weighted fractions  sum used / sum len  and  sum packed(t) / sum kept-if-fully-packed(t)  (the second from two passes:
-OGS_PACK_FUSED=2 packs every list to the end).
+and the work-weighted fraction  sum used / sum len.
 
 usage: python scripts/list_depth_stats.py [workload ...]      (default: S1M-1080p C3-500k-988 C4-2M-648 C2-100k-800)
 """
@@ -83,10 +82,6 @@ def main():
     dev = torch.device("cuda:0")
     names = sys.argv[1:] or ["S1M-1080p", "C3-500k-988", "C4-2M-648", "C2-100k-800"]
     res = [stats(n, dev) for n in names]
-    mode = os.environ.get("OGS_PACK_FUSED", "1")
-    for r in res:
-        r["pack_mode"] = {"1": "chunked with workgroup-wide exit (default)", "2": "whole list packed (round 3)",
-                          "0": "two launches, whole list packed"}.get(mode, mode)
     print(json.dumps(res, indent=1))
 
 

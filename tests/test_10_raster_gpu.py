@@ -2,8 +2,6 @@
 identical seeded inputs.  Tolerances (BASELINE.json north_star): images / depth / alpha within 1e-4 fp32;
 radii, tile ranges, sorted (tile<<32 | depth_bits) keys and point lists BIT-EXACT; n_contrib exact except
 for pixels where the device exp and the host exp disagree on a threshold (bounded fraction, documented)."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -877,26 +875,3 @@ def test_random_configurations_forward_parity(gpu_device):
             helpers.assert_close_modulo_threshold_flips(depth.cpu().numpy(), ref["depth"], IMG_TOL * 10, flip_tol=4e-2)
         except AssertionError as e:
             raise AssertionError(f"{tag}: {e}") from None
-
-
-@pytest.mark.parametrize("env", [{"OGS_BLEND_ROWS": "0"}, {"OGS_BLEND_FOLD": "bf16"},
-                                 {"OGS_BLEND_FEAT_LDS": "0"}, {"OGS_PACK_FUSED": "0"}, {"OGS_PACK_FUSED": "2"}])
-def test_alternative_blend_kernels_keep_parity(gpu_device, env):
-    """The forward blend exists in two structures: the quadrant walk (records in SGPRs) and the per-4x4-block walk (records in
-    VGPRs through LDS, the default).  The full backward reduces its gradient records on the matrix cores with exact-fp32 MFMAs by
-    default and with a two-term bf16 split of both operands under OGS_BLEND_FOLD=bf16 (same speed: the kernel is bound by its
-    atomics; 2^-15 per product shows when a Gaussian's sum cancels, scripts/fuzz_parity.py); the forward packs and blends a tile chunk by chunk with a workgroup-wide exit by default
-    (OGS_PACK_FUSED=2: the whole list packed first, round 3; =0: two launches); the
-    features-only backward walks quadrants with its records through LDS by default, through scalar loads otherwise; pack and
-    forward blend of a tile run in one workgroup by default, as two launches otherwise.  The
-    non-default ones are selected by environment variables read once per process, so they are checked in a child process:
-    forward / backward parity against the oracle, the adversarial scenes, the fused and grouped passes."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_10_raster_gpu.py"), "-x", "-q", "-m", "gpu", "-k",
-           "test_forward_parity or test_backward_parity or test_adversarial_scenes or test_fused_pass or test_grouped_pass or test_tiny_pass"
-           " or test_features_only_backward"]
-    r = subprocess.run(cmd, cwd=root, env=dict(os.environ, **env), capture_output=True, text=True, timeout=1500)
-    assert r.returncode == 0, r.stdout[-3000:]
-    assert " passed" in r.stdout and " failed" not in r.stdout

@@ -153,6 +153,34 @@ def test_lloyd_matches_oracle_with_inactive_rows(gpu_device):
     assert float(cent[6:].abs().max()) == 0.0 and int(ids.min()) >= 30 and int(ids.max()) < 36
 
 
+# one case per pass the product launches (kmeans.hip, launch_pass); k_active < k on the bf16 accumulate path
+@pytest.mark.parametrize("k,d,k_active", [
+    (128, 9, None), (200, 6, None),         # kmeans_accum_bf16_kernel + the CB = 16 assign
+    (64, 7, None), (16, 3, None),           # kmeans_mfma_pass_kernel, DT = 0, CB = 4 / 1
+    (300, 9, None), (8, 16, None),          # kmeans_lds_pass_kernel
+    (160, 9, 100),
+])
+def test_lloyd_and_assign_match_oracle_on_every_size_path(gpu_device, k, d, k_active):
+    from opengaussian_amd import kmeans
+    g = torch.Generator().manual_seed(k * 31 + d)
+    N, iters, off = 24000, 4, 0 if k_active is None else 17
+    ka = k if k_active is None else k_active
+    nchunks = N // 10000 + 1
+    feat = torch.rand(N, d, generator=g)
+    cent0 = feat[torch.randperm(N, generator=g)[:k]].clone()
+    cref, iref = ko.lloyd(feat.numpy(), cent0.numpy(), iters=iters, nchunks=nchunks, k_active=k_active, id_offset=off)
+    fdev = feat.to(gpu_device)
+    cent = cent0.to(gpu_device).clone()
+    ids = kmeans.lloyd(fdev, cent, iters=iters, nchunks=nchunks, k_active=k_active, id_offset=off)
+    c = cent.cpu().numpy()
+    assert_centers_close(c, cref, f"(k={k}, d={d}, k_active={ka})")
+    helpers.kmeans_final_ids_attribution(feat.numpy(), cref[:ka], iref - off, c[:ka], ids.cpu().numpy() - off, "lloyd")
+    # assignment alone, with the same centres on both sides
+    aids = kmeans.assign(fdev, cent[:ka].contiguous(), id_offset=off).cpu().numpy()
+    want = ko._argmin_sqdist(feat.numpy(), c[:ka])
+    helpers.kmeans_final_ids_attribution(feat.numpy(), c[:ka], want, c[:ka], aids - off, "assign")
+
+
 def test_edge_sizes(gpu_device):
     from opengaussian_amd import kmeans
     dev = gpu_device
