@@ -195,7 +195,8 @@ size_t ogs_raster_quad_list_bytes(int64_t num_rendered);
 /* Phase 1: fills radii + geom_buffer, leaves the depth order and tile offsets in geom_tmp, writes
  * num_rendered to *num_rendered_host (host memory) and returns after the stream has finished it
  * (the same blocking read-back the reference performs once per forward).
- * num_rendered_host == NULL: no read-back, no synchronisation (see the deferred variant below). */
+ * num_rendered_host == NULL: no read-back, no synchronisation (see the deferred variant below).  out_color / out_depth /
+ * out_alpha are not touched by this phase and may be NULL (a statistics pass has none). */
 int ogs_raster_forward_geometry(const OgsRasterFwdArgs* args, void* stream, int64_t* num_rendered_host);
 
 /* Phase 2: needs args->point_list / binning_tmp / sorted_rec / quad_list sized for num_rendered.  Asynchronous. */
@@ -254,6 +255,40 @@ int ogs_raster_forward_reblend(const OgsRasterFwdArgs* args, void* stream);
 int ogs_raster_compact_kept(int32_t W, int32_t H, int32_t C, const void* image_buffer, const void* sorted_rec,
                             const void* quad_list, void* new_image_buffer, void* new_sorted_rec, void* new_quad_list,
                             void* stream);
+
+/* Grouped label statistics (new capability; no reference counterpart).  The 2D-3D association of the reference
+ * (train.py construct_pseudo_ins_feat, stages 2.2 and 3) renders every cluster / leaf subset of a view and reads a few numbers
+ * per (subset g, pseudo mask l) off the images: the pixels with alpha_g > thr inside mask l, the sum of subset g's blended colour
+ * over them, and the maximum alpha of g.  The masks of one SAM level are disjoint, so one int32 label image carries them all and
+ * those numbers are a histogram over it.  This pass is a grouped pass (OgsRasterFwdArgs.group_ids / num_groups) that takes the
+ * histogram in the blend's epilogue instead of writing images: same preprocess, duplicate, sort, pack and blend, the same
+ * per-pixel alpha and colour bit for bit, and nothing of size G*W*H allocated or written (no colour / depth / alpha images, no
+ * n_contrib / final_T, no records or quadrant streams for a backward).
+ *
+ * Sequence: ogs_raster_forward_geometry(args, stream, &num_rendered) with args.out_color / out_depth / out_alpha == NULL allowed,
+ * then this call with args.point_list / binning_tmp sized for num_rendered and args.image_buffer of
+ * ogs_raster_stats_image_bytes(W, H, G); args.sorted_rec / quad_list are not used.  Outputs (cleared by the call):
+ *   max_alpha [G] fp32        maximum over the image of group g's alpha (0 for a group without Gaussians);
+ *   count     [G, L+1] int64  pixels with alpha > alpha_threshold, by label; bucket L = "no mask" (a label outside [0, L));
+ *   feat_sum  [G, L+1, C] fp32 sum over those pixels of the blended colour INCLUDING the background term T * bg[c] -- the value
+ *                             a grouped pass writes to out_color -- accumulated as int64 fixed point with a 2^-32 quantum
+ *                             (order-independent: bit-reproducible run to run), rounded to fp32 once.  Exact to 2^-33 per
+ *                             pixel; valid while |colour| * pixels < 2^31 (e.g. |colour| < 512 on 4 M pixels).
+ * num_labels == 0 is legal (one bucket).  Asynchronous. */
+typedef struct OgsGroupStatsArgs {
+    const int32_t* labels;       /* [H*W] device: label of every pixel, -1 = no mask */
+    int32_t num_labels;          /* L >= 0 */
+    float alpha_threshold;       /* a pixel counts when alpha > alpha_threshold */
+    float* max_alpha;            /* [G] */
+    int64_t* count;              /* [G, L+1] */
+    float* feat_sum;             /* [G, L+1, C] */
+    void* stats_tmp;             /* ogs_raster_stats_tmp_bytes(G, L, C) */
+} OgsGroupStatsArgs;
+
+size_t ogs_raster_stats_image_bytes(int32_t W, int32_t H, int32_t num_groups);
+size_t ogs_raster_stats_tmp_bytes(int32_t num_groups, int32_t num_labels, int32_t C);
+int ogs_raster_forward_group_stats(const OgsRasterFwdArgs* args, const OgsGroupStatsArgs* stats, int64_t num_rendered,
+                                   void* stream);
 
 /* Backward.  Asynchronous on `stream`.  In the features-only case (see OgsRasterBwdArgs) only P, W, H, C, num_rendered,
  * num_groups, radii, dL_dcolor, image_buffer, sorted_rec, quad_list, bwd_tmp, dL_dcolors are read, `colors_precomp` and `shs`

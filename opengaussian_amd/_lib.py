@@ -62,6 +62,11 @@ class OgsDensifyArgs(C.Structure):
                 ("prune_world_size", C.c_int32)]
 
 
+class OgsGroupStatsArgs(C.Structure):
+    _fields_ = [("labels", _vp), ("num_labels", C.c_int32), ("alpha_threshold", C.c_float), ("max_alpha", _vp),
+                ("count", _vp), ("feat_sum", _vp), ("stats_tmp", _vp)]
+
+
 # name -> (restype, argtypes); also the list the symbol-export test checks against the headers
 SIGNATURES = {
     "ogs_version": (C.c_int, []),
@@ -78,6 +83,9 @@ SIGNATURES = {
     "ogs_raster_forward_render": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.c_int64, _vp]),
     "ogs_raster_read_num_rendered_async": (C.c_int, [C.POINTER(OgsRasterFwdArgs), _vp, _vp]),
     "ogs_raster_forward_render_deferred": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.c_int64, _vp]),
+    "ogs_raster_stats_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "ogs_raster_stats_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "ogs_raster_forward_group_stats": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsGroupStatsArgs), C.c_int64, _vp]),
     "ogs_raster_backward": (C.c_int, [C.POINTER(OgsRasterBwdArgs), _vp]),
     "ogs_raster_tiny_max_points": (C.c_size_t, []),
     "ogs_raster_forward_tiny": (C.c_int, [C.POINTER(OgsRasterFwdArgs), _vp]),

@@ -282,17 +282,115 @@ struct ChunkLds {
     uint8_t s_qnew[4][kBlock];                             // per quadrant: staging slot of every entry the chunk adds to its stream
 };
 
+// ---- grouped label statistics (ogs_raster_forward_group_stats) ----------------------------------------------------------
+// Per (group g, label bucket l): the pixels of image g with alpha > thr whose label is l (bucket L: no mask), the sum of their
+// blended colour, and per group the maximum alpha -- what the 2D-3D association reads off the images of a grouped pass, taken
+// in the blend's epilogue instead.  Sums are int64 fixed point (quantum 2^-32): integer adds commute, so the result does not
+// depend on the order in which workgroups arrive -- bit-reproducible run to run (fp32 atomics are not).  One tile reduces in
+// LDS first: wave 0 walks the tile's 256 pixels (four per lane) label by label (the first pending label of the first pending
+// lane, broadcast), sums the matching pixels per lane, then across the wave, and issues ONE global atomic per (label, channel)
+// the tile touched.
+struct GroupStatsOut {
+    const int32_t* labels;       // [H*W]
+    int32_t L;                   // labels in [0, L); anything else -> bucket L
+    float thr;
+    uint32_t* max_alpha;         // [G] fp32 bit patterns (alpha >= 0: integer order == float order)
+    unsigned long long* count;   // [G, L+1]
+    unsigned long long* fsum;    // [G, L+1, C] int64, quantum 2^-32
+};
+
+constexpr float kFixedScale = 4294967296.0f;          // 2^32
+
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
+    const uint32_t lo = __shfl_xor((uint32_t)v, m, kWave), hi = __shfl_xor((uint32_t)(v >> 32), m, kWave);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// s_buf: >= (C + 2) * kBlock floats of LDS no other wave reads any more.  pix = py * W + px, or -1 outside the image.
+template <int C>
+__device__ __forceinline__ void group_stats_epilogue(const GroupStatsOut& st, float* __restrict__ s_buf, int img, int W, int pix,
+                                                     float alpha, const float (&colour)[C]) {
+    float* s_val = s_buf;                                               // [C][kBlock]
+    float* s_alpha = s_buf + C * kBlock;                                // [kBlock]
+    int* s_key = reinterpret_cast<int*>(s_buf + (C + 1) * kBlock);      // [kBlock]: bucket, -1 = not counted
+    const int tid = threadIdx.x, lane = tid & 63;
+    int key = -1;
+    if (pix >= 0 && alpha > st.thr) {
+        const int l = st.labels[pix];
+        key = (l >= 0 && l < st.L) ? l : st.L;
+    }
+    s_key[tid] = key;
+    s_alpha[tid] = pix >= 0 ? alpha : 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) s_val[c * kBlock + tid] = colour[c];
+    lds_barrier();
+    if (tid >= kWave) return;
+    int k[kBlock / kWave];
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < kBlock / kWave; ++j) {
+        k[j] = s_key[lane + kWave * j];
+        m = fmaxf(m, s_alpha[lane + kWave * j]);
+    }
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+    if (lane == 0 && m > 0.f) atomicMax(st.max_alpha + img, __float_as_uint(m));
+    const size_t row0 = (size_t)img * (size_t)(st.L + 1);
+    for (;;) {
+        int cand = -1;
+#pragma unroll
+        for (int j = kBlock / kWave - 1; j >= 0; --j) cand = k[j] >= 0 ? k[j] : cand;
+        const uint64_t pending = __ballot(cand >= 0);
+        if (pending == 0ull) break;
+        const int K = __shfl(cand, __ffsll((unsigned long long)pending) - 1, kWave);
+        unsigned long long cnt = 0, sum[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) sum[c] = 0ull;
+#pragma unroll
+        for (int j = 0; j < kBlock / kWave; ++j) {
+            if (k[j] == K) {
+                ++cnt;
+#pragma unroll
+                for (int c = 0; c < C; ++c) sum[c] += (unsigned long long)__float2ll_rn(s_val[c * kBlock + lane + kWave * j] * kFixedScale);
+                k[j] = -1;
+            }
+        }
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1) {
+            cnt += (unsigned long long)__shfl_xor((uint32_t)cnt, off, kWave);
+#pragma unroll
+            for (int c = 0; c < C; ++c) sum[c] += shfl_xor_u64(sum[c], off);
+        }
+        if (lane == 0) {
+            const size_t r = row0 + (size_t)K;
+            atomicAdd(st.count + r, cnt);
+#pragma unroll
+            for (int c = 0; c < C; ++c) atomicAdd(st.fsum + r * C + c, sum[c]);
+        }
+    }
+}
+
+// fixed point -> fp32, once per (group, bucket, channel)
+__global__ __launch_bounds__(256) void group_stats_finish_kernel(const long long* __restrict__ fsum, float* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (float)((double)fsum[i] * (1.0 / 4294967296.0));
+}
+
 // Six waves per SIMD: the kernel is sensitive to occupancy (probe: 24 KB more LDS per workgroup, three workgroups per CU instead of
 // six: 0.402 -> 0.514 ms) and its 26 KB of LDS allow six workgroups per CU, but at C = 9 the register allocator settles at 92 VGPRs
 // = five waves.  Asking for six costs six spilled dwords (80 VGPRs) and gives 0.402 -> 0.390 ms (A-B-A-B on one box); C = 12
 // cannot fit and stays where it was.
-template <int C>
+// STATS (ogs_raster_forward_group_stats): the same walk -- same packing, same per-pixel arithmetic, same exit -- with the
+// image epilogue replaced by group_stats_epilogue (per-(group, label) statistics, nothing of size G*W*H) and the write-outs
+// kept for the backward (records, quadrant streams, qcount) compiled out.  `st` is unused when STATS is false.
+template <int C, bool STATS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8)))
 void pack_blend_chunked_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const float4* __restrict__ rec,
     float4* __restrict__ stream, uint32_t* __restrict__ quad_list, uint32_t* __restrict__ qcount, int W, int H, int gx, int tiles,
     const float* __restrict__ bg, float* __restrict__ out_color, float* __restrict__ out_depth, float* __restrict__ out_alpha,
-    uint32_t* __restrict__ n_contrib, float* __restrict__ final_T, const uint32_t* __restrict__ tile_order) {
+    uint32_t* __restrict__ n_contrib, float* __restrict__ final_T, const uint32_t* __restrict__ tile_order,
+    GroupStatsOut st = GroupStatsOut{}) {
     constexpr int NV = rec_vec4(C);
     constexpr int SV = stream_vec4(C);
     constexpr int kListLen = kRowListLen;
@@ -453,14 +551,14 @@ void pack_blend_chunked_kernel(
             for (int q = 0; q < 4; ++q) {
                 if (mask & (1u << q)) {
                     const uint32_t pq = (uint32_t)(pos >> (12 * q)) & 0xFFFu;
-                    quad_list[(size_t)range.x * 5 + (size_t)q * n + running[q] + pq] = c_idx;      // for the backward
+                    if constexpr (!STATS) quad_list[(size_t)range.x * 5 + (size_t)q * n + running[q] + pq] = c_idx;   // for the backward
                     lds.s_qnew[q][pq] = (uint8_t)c_loc;                                            // for this chunk's blend
                 }
             }
-            quad_list[(size_t)range.x * 5 + (size_t)4 * n + c_idx] = (uint32_t)i;
+            if constexpr (!STATS) quad_list[(size_t)range.x * 5 + (size_t)4 * n + c_idx] = (uint32_t)i;
         }
         lds_barrier();                    // (2) the chunk's records and stream entries are staged
-        {
+        if constexpr (!STATS) {
             // record write-out for the backward: one contiguous range, the whole workgroup (stores only: nothing waits for them)
             const int kept4 = (int)((uint32_t)(total >> 48) & 0xFFFu) * SV;
             float4* __restrict__ out = stream + ((size_t)range.x + (size_t)running[4]) * SV;
@@ -530,20 +628,28 @@ void pack_blend_chunked_kernel(
         lds_barrier();                    // (3) the staging buffer is free again; the four votes are in
         if ((lds.done[0] & lds.done[1] & lds.done[2] & lds.done[3]) != 0u) break;       // block-uniform
     }
-    if (tid == 0) {
+    if constexpr (STATS) {
+        // every wave is past barrier (3) of the last chunk (or never entered the loop): the staging buffer is free
+        float colour[C];
 #pragma unroll
-        for (int q = 0; q < 5; ++q) qcount[tile * 5 + q] = running[q];
-    }
-    if (inside) {
-        const size_t plane = (size_t)W * H;
-        const size_t pix = (size_t)img * plane + (size_t)py * W + px;
-        float* oc = out_color + (size_t)img * (C - 1) * plane;
+        for (int c = 0; c < C; ++c) colour[c] = ((c & 1) ? accp[c / 2].y : accp[c / 2].x) + T * bg[c];
+        group_stats_epilogue<C>(st, reinterpret_cast<float*>(lds.s_rec), img, W, inside ? py * W + px : -1, wacc, colour);
+    } else {
+        if (tid == 0) {
 #pragma unroll
-        for (int c = 0; c < C; ++c) oc[c * plane + pix] = ((c & 1) ? accp[c / 2].y : accp[c / 2].x) + T * bg[c];
-        out_depth[pix] = (C & 1) ? accp[C / 2].y : accp[C / 2].x;
-        out_alpha[pix] = wacc;
-        n_contrib[pix] = last;
-        final_T[pix] = T;
+            for (int q = 0; q < 5; ++q) qcount[tile * 5 + q] = running[q];
+        }
+        if (inside) {
+            const size_t plane = (size_t)W * H;
+            const size_t pix = (size_t)img * plane + (size_t)py * W + px;
+            float* oc = out_color + (size_t)img * (C - 1) * plane;
+#pragma unroll
+            for (int c = 0; c < C; ++c) oc[c * plane + pix] = ((c & 1) ? accp[c / 2].y : accp[c / 2].x) + T * bg[c];
+            out_depth[pix] = (C & 1) ? accp[C / 2].y : accp[C / 2].x;
+            out_alpha[pix] = wacc;
+            n_contrib[pix] = last;
+            final_T[pix] = T;
+        }
     }
 }
 
@@ -827,6 +933,41 @@ int launch_c(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& i
     return OGS_OK;
 }
 
+// statistics variant of launch_c: the chunked walk on every virtual tile (an empty list included: n = 0, the pixels keep the
+// background), then the fixed-point sums to fp32.  The outputs and the fixed-point scratch are cleared here.
+template <int C>
+int stats_c(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& sa, const GeomState& gs, const ImageState& is, hipStream_t s) {
+    const int gx = (a.W + kTile - 1) / kTile, gy = (a.H + kTile - 1) / kTile;
+    const int tiles = gx * gy;
+    const int G = num_groups_of(a.num_groups);
+    const unsigned vtiles = (unsigned)tiles * (unsigned)G;
+    const size_t rows = (size_t)G * (size_t)(sa.num_labels + 1);
+    long long* fixed = static_cast<long long*>(sa.stats_tmp);
+    OGS_HIP_CHECK(hipMemsetAsync(sa.max_alpha, 0, (size_t)G * sizeof(float), s));
+    OGS_HIP_CHECK(hipMemsetAsync(sa.count, 0, rows * sizeof(int64_t), s));
+    OGS_HIP_CHECK(hipMemsetAsync(fixed, 0, rows * C * sizeof(long long), s));
+    const uint32_t* order = launch_tile_order(is, vtiles, a.P, s, a.debug);
+    GroupStatsOut st;
+    st.labels = sa.labels;
+    st.L = sa.num_labels;
+    st.thr = sa.alpha_threshold;
+    st.max_alpha = reinterpret_cast<uint32_t*>(sa.max_alpha);
+    st.count = reinterpret_cast<unsigned long long*>(sa.count);
+    st.fsum = reinterpret_cast<unsigned long long*>(fixed);
+    static constexpr const char* const kStats[4] = {"pack_blend_chunked_kernel<3, stats>", "pack_blend_chunked_kernel<6, stats>",
+                                                    "pack_blend_chunked_kernel<9, stats>", "pack_blend_chunked_kernel<12, stats>"};
+    OGS_LAUNCH_NAMED(chan_name<C>(kStats), (pack_blend_chunked_kernel<C, true>), dim3(vtiles), dim3(kBlock), 0, s,
+                     (const uint2*)is.ranges, (const uint32_t*)a.point_list, (const float4*)gs.rec, (float4*)nullptr,
+                     (uint32_t*)nullptr, (uint32_t*)nullptr, a.W, a.H, gx, tiles, a.bg, (float*)nullptr, (float*)nullptr,
+                     (float*)nullptr, (uint32_t*)nullptr, (float*)nullptr, order, st);
+    OGS_LAUNCH_CHECK(a.debug, s);
+    const size_t n = rows * C;
+    OGS_LAUNCH(group_stats_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const long long*)fixed,
+               sa.feat_sum, n);
+    OGS_LAUNCH_CHECK(a.debug, s);
+    return OGS_OK;
+}
+
 // ---- re-blend of a kept pass (frozen geometry, round 4) ----------------------------------------------------------------
 // From stage 1 on the reference trains `_ins_feat` alone (train.py:431-436): for a given camera every later pass bins, sorts and
 // packs exactly what the first one did, only the feature channels of the records differ.  A caller that kept image_buffer,
@@ -942,6 +1083,17 @@ int launch_blend_forward(const OgsRasterFwdArgs& a, const GeomState& gs, const I
         case 6: return launch_c<6>(a, gs, is, D, s);
         case 9: return launch_c<9>(a, gs, is, D, s);
         case 12: return launch_c<12>(a, gs, is, D, s);
+        default: set_error("unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
+    }
+}
+
+int launch_group_stats(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& st, const GeomState& gs, const ImageState& is,
+                       hipStream_t s) {
+    switch (a.C) {
+        case 3: return stats_c<3>(a, st, gs, is, s);
+        case 6: return stats_c<6>(a, st, gs, is, s);
+        case 9: return stats_c<9>(a, st, gs, is, s);
+        case 12: return stats_c<12>(a, st, gs, is, s);
         default: set_error("unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
     }
 }

@@ -110,7 +110,7 @@ static int bit_length(uint32_t v) {
     return n;
 }
 
-static int validate_fwd(const OgsRasterFwdArgs* a) {
+static int validate_fwd(const OgsRasterFwdArgs* a, bool images = true) {
     if (!a) { set_error("args == NULL"); return OGS_ERR_INVALID_ARG; }
     if (a->P < 0 || a->W <= 0 || a->H <= 0) { set_error("bad sizes P=%d W=%d H=%d", a->P, a->W, a->H); return OGS_ERR_INVALID_ARG; }
     if (a->C != 3 && a->C != 6 && a->C != 9 && a->C != 12) { set_error("C=%d unsupported (3, 6, 9, 12)", a->C); return OGS_ERR_UNSUPPORTED; }
@@ -131,7 +131,7 @@ static int validate_fwd(const OgsRasterFwdArgs* a) {
             return OGS_ERR_INVALID_ARG;
         }
     }
-    if (!a->bg || !a->viewmatrix || !a->projmatrix || !a->campos || !a->out_color || !a->out_depth || !a->out_alpha) {
+    if (!a->bg || !a->viewmatrix || !a->projmatrix || !a->campos || (images && (!a->out_color || !a->out_depth || !a->out_alpha))) {
         set_error("NULL required pointer"); return OGS_ERR_INVALID_ARG;
     }
     if (a->P > 0 && (!a->means3D || !a->opacities || !a->radii || !a->geom_buffer || !a->geom_tmp)) {
@@ -216,7 +216,7 @@ size_t ogs_raster_quad_list_bytes(int64_t D) {
 size_t ogs_raster_backward_tmp_bytes(int32_t P) { return align_up((size_t)(P > 0 ? P : 1) * 16 * sizeof(double)); }
 
 int ogs_raster_forward_geometry(const OgsRasterFwdArgs* a, void* stream_, int64_t* num_rendered_host) {
-    int rc = validate_fwd(a);
+    int rc = validate_fwd(a, /*images=*/false);        // the images are written by the render phase only
     if (rc != OGS_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream_);
     if (num_rendered_host) *num_rendered_host = 0;
@@ -281,12 +281,15 @@ int ogs_raster_read_num_rendered_async(const OgsRasterFwdArgs* a, void* stream_,
 
 // D = exact num_rendered (deferred == false) or the CAPACITY of point_list / binning_tmp / sorted_rec while the
 // binning kernels read the true count from device memory (deferred == true).
-static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipStream_t s) {
-    int rc = validate_fwd(a);
+// stats != NULL: the statistics pass of ogs_raster_forward_group_stats (no images; its own, smaller image state).
+static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipStream_t s,
+                       const OgsGroupStatsArgs* stats = nullptr) {
+    int rc = validate_fwd(a, stats == nullptr);
     if (rc != OGS_OK) return rc;
     if (!a->image_buffer) { set_error("image_buffer == NULL"); return OGS_ERR_INVALID_ARG; }
     const int G = num_groups_of(a->num_groups);
-    const ImageState is = ImageState::carve(a->image_buffer, a->W, a->H, G);
+    const ImageState is = stats ? ImageState::carve_stats(a->image_buffer, a->W, a->H, G)
+                                : ImageState::carve(a->image_buffer, a->W, a->H, G);
     const int gx = (a->W + kTile - 1) / kTile, gy = (a->H + kTile - 1) / kTile;
     const int64_t tiles = (int64_t)gx * gy * G;             // virtual tiles: image (group) * tiles_per_image + tile
     if (tiles >= (1ll << 31)) { set_error("%d groups x %d tiles exceed 2^31 virtual tiles", G, gx * gy); return OGS_ERR_UNSUPPORTED; }
@@ -343,12 +346,34 @@ static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipS
     } else {
         OGS_HIP_CHECK(hipMemsetAsync(is.ranges, 0, (size_t)tiles * sizeof(uint2), s));
     }
+    if (stats) return launch_group_stats(*a, *stats, gs, is, s);
     if (!a->sorted_rec || !a->quad_list) { set_error("sorted_rec / quad_list == NULL"); return OGS_ERR_INVALID_ARG; }
     return launch_blend_forward(*a, gs, is, D, s);
 }
 
 int ogs_raster_forward_render(const OgsRasterFwdArgs* a, int64_t D, void* stream_) {
     return render_impl(a, D, false, static_cast<hipStream_t>(stream_));
+}
+
+size_t ogs_raster_stats_image_bytes(int32_t W, int32_t H, int32_t G) {
+    return ImageState::stats_bytes(W > 0 ? W : 1, H > 0 ? H : 1, num_groups_of(G));
+}
+size_t ogs_raster_stats_tmp_bytes(int32_t G, int32_t L, int32_t C) {
+    return align_up((size_t)num_groups_of(G) * (size_t)((L > 0 ? L : 0) + 1) * (size_t)(C > 0 ? C : 1) * sizeof(int64_t));
+}
+
+// Grouped label statistics (include/ogs_raster.h): the render phase of a grouped pass with the statistics epilogue.
+// The tile sort's keys are the virtual tile ids g * tiles + t (render_impl rejects 2^31 and more): 640 groups of a 1080p frame
+// are 640 * 8160 = 5.2 M virtual tiles, 23 key bits, three 8-bit passes.
+int ogs_raster_forward_group_stats(const OgsRasterFwdArgs* a, const OgsGroupStatsArgs* st, int64_t D, void* stream_) {
+    if (!a || !st) { set_error("forward_group_stats: NULL argument"); return OGS_ERR_INVALID_ARG; }
+    if (st->num_labels < 0) { set_error("forward_group_stats: num_labels=%d < 0", st->num_labels); return OGS_ERR_INVALID_ARG; }
+    if (!st->labels || !st->max_alpha || !st->count || !st->feat_sum || !st->stats_tmp) {
+        set_error("forward_group_stats: NULL labels / output / stats_tmp pointer"); return OGS_ERR_INVALID_ARG;
+    }
+    if (D < 0) { set_error("forward_group_stats: num_rendered=%lld < 0", (long long)D); return OGS_ERR_INVALID_ARG; }
+    if (a->P == 0) D = 0;
+    return render_impl(a, D, false, static_cast<hipStream_t>(stream_), st);
 }
 
 int ogs_raster_forward_render_deferred(const OgsRasterFwdArgs* a, int64_t capacity, void* stream_) {

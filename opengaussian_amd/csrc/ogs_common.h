@@ -204,6 +204,22 @@ struct ImageState {     // kept until backward
         c.take<float>((size_t)G * W * H);
         c.take<uint32_t>(tiles);
         return c.off;
+    }    // the image state of a statistics pass (ogs_raster_forward_group_stats): tile ranges and workgroup order only -- nothing
+    // per pixel, nothing kept for a backward
+    static ImageState carve_stats(void* p, int W, int H, int G) {
+        Carver c(p);
+        ImageState s{};
+        const size_t tiles = (size_t)G * ((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile);
+        s.ranges = c.take<uint2>(tiles);
+        s.tile_order = c.take<uint32_t>(tiles);
+        return s;
+    }
+    static size_t stats_bytes(int W, int H, int G) {
+        Carver c(nullptr);
+        const size_t tiles = (size_t)G * ((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile);
+        c.take<uint2>(tiles);
+        c.take<uint32_t>(tiles);
+        return c.off;
     }
 };
 // heaviest-first workgroup order of the per-tile kernels; returns the array the kernels index with blockIdx.x, or
@@ -327,6 +343,8 @@ int launch_duplicate(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomT
 int launch_tile_ranges(const uint32_t* tile_keys_sorted, int64_t D, uint2* ranges, int64_t tiles, hipStream_t s,
                        int debug, const uint32_t* n_dev = nullptr, bool already_zeroed = false);
 inline int num_groups_of(int g) { return g > 1 ? g : 1; }
+int launch_group_stats(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& st, const GeomState& gs, const ImageState& is,
+                       hipStream_t s);
 int launch_blend_forward(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& is, int64_t D,
                          hipStream_t s);
 // The per-Gaussian gradient record is accumulated in fp64 (128 B = one L2 line): with thousands of float atomics per

@@ -756,6 +756,142 @@ def rasterize_groups(means3D, means2D, opacities, group_ids, num_groups, raster_
                                      group_ids, int(num_groups))
 
 
+def _stats_inputs(means3D, opacities, raster_settings, colors_precomp, scales, rotations, cov3D_precomp):
+    """fp32 contiguous inputs of a forward-only pass (statistics, preprocess-only); raises when autograd would be asked
+    for a gradient no such pass can give."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                       for t in (means3D, opacities, colors_precomp, scales, rotations, cov3D_precomp)):
+        raise RuntimeError("statistics / preprocess-only passes have no backward: detach the inputs or use torch.no_grad()")
+    _require_gpu(means3D, "means3D")
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    if (scales is None) != (rotations is None) or (scales is None) == (cov3D_precomp is None):
+        raise RuntimeError("provide exactly one of (scales, rotations) / cov3D_precomp")
+    dev = means3D.device
+    cols = _f32c(colors_precomp)
+    if cols is None or cols.dim() != 2 or cols.shape[0] != means3D.shape[0]:
+        if means3D.shape[0] != 0:
+            raise RuntimeError("colors_precomp must be [P, C]")
+    Cn = int(colors_precomp.shape[-1])
+    if Cn not in SUPPORTED_CHANNELS:
+        raise RuntimeError(f"the blended channel count must be 3, 6, 9 or 12, got {Cn}")
+    rs = raster_settings
+    bg = _f32c(rs.bg.to(dev))
+    if bg is None or bg.numel() != Cn:
+        if bg is not None and bg.numel() == 3 and Cn > 3:
+            bg = _tiled_bg(bg, Cn)         # as every other pass of the facade: the 3-wide background over all channels
+        else:
+            raise RuntimeError(f"bg must have {Cn} entries")
+    return (Cn, _f32c(means3D), _f32c(opacities), cols, _f32c(scales), _f32c(rotations), _f32c(cov3D_precomp), bg,
+            _f32c(rs.viewmatrix.to(dev)), _f32c(rs.projmatrix.to(dev)), _f32c(rs.campos.to(dev)))
+
+
+def visible_radii(means3D, opacities, raster_settings, colors_precomp, scales=None, rotations=None, cov3D_precomp=None):
+    """Preprocess only: the int32 radii [P] an ungrouped pass over the same inputs returns (the geometry phase alone, no
+    binning, no blend).  A radius depends on its own Gaussian only, so ``radii > 0`` is bit for bit the visibility filter of
+    the reference's RGB pass of the same camera -- what the association drivers select subsets by before a statistics pass."""
+    Cn, m3, opac, cols, scl, rot, cov, bg, view, proj, campos = _stats_inputs(
+        means3D, opacities, raster_settings, colors_precomp, scales, rotations, cov3D_precomp)
+    P = int(means3D.shape[0])
+    dev = means3D.device
+    radii = torch.zeros(P, dtype=torch.int32, device=dev)
+    if P == 0:
+        return radii
+    lib = _lib.lib()
+    a = _fwd_args(raster_settings, P, Cn, m3, None, cols, opac, scl, rot, cov, bg, view, proj, campos, None, None, None,
+                  radii, None, 1)
+    gb, gtb, _ = _geom_sizes(P, int(a.W), int(a.H), Cn, 1)
+    geom = torch.empty(gb, dtype=torch.uint8, device=dev)
+    geom_tmp = torch.empty(gtb, dtype=torch.uint8, device=dev)
+    a.geom_buffer, a.geom_tmp = ptr(geom), ptr(geom_tmp)
+    check(lib.ogs_raster_forward_geometry(C.byref(a), _stream(), None), "ogs_raster_forward_geometry")
+    return radii
+
+
+def rasterize_group_stats(means3D, opacities, group_ids, num_groups, labels, num_labels, raster_settings, colors_precomp,
+                          scales=None, rotations=None, cov3D_precomp=None, alpha_threshold=0.5):
+    """Per-(subset, label) statistics of a grouped pass, without its images (include/ogs_raster.h,
+    ogs_raster_forward_group_stats).  For every g in [0, num_groups) -- the subset ``group_ids == g``, rendered as
+    rasterize_groups renders it -- and every label l of the int32 label image ``labels`` [H, W] (values in [0, num_labels);
+    -1 or anything else: bucket num_labels, "no mask"):
+
+      max_alpha [G] fp32          the maximum of the subset's alpha image;
+      count     [G, L+1] int64    the pixels with alpha > alpha_threshold carrying label l;
+      feat_sum  [G, L+1, C] fp32  the sum over those pixels of the blended colour, background term included -- the
+                                  values rasterize_groups writes to `color` (int64 fixed-point accumulation: the same
+                                  bits every run);
+      radii     [P] int32         as rasterize_groups returns them (0 outside the groups).
+
+    Same alpha and colour per pixel as rasterize_groups, bit for bit, so every threshold decision agrees with its images;
+    nothing of size G*H*W is allocated.  Forward only (raises when an input requires grad under grad mode).  Uses the
+    blocking num_rendered read-back, as every grouped pass."""
+    Cn, m3, opac, cols, scl, rot, cov, bg, view, proj, campos = _stats_inputs(
+        means3D, opacities, raster_settings, colors_precomp, scales, rotations, cov3D_precomp)
+    rs = raster_settings
+    G, L = int(num_groups), int(num_labels)
+    if G < 0 or L < 0:
+        raise RuntimeError(f"num_groups ({G}) and num_labels ({L}) must be >= 0")
+    H, W = int(rs.image_height), int(rs.image_width)
+    dev = means3D.device
+    P = int(means3D.shape[0])
+    if labels.numel() != H * W:
+        raise RuntimeError(f"labels must have H*W = {H * W} entries, got {tuple(labels.shape)}")
+    lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+    max_alpha = torch.zeros(G, dtype=torch.float32, device=dev)
+    count = torch.zeros(G, L + 1, dtype=torch.int64, device=dev)
+    feat_sum = torch.zeros(G, L + 1, Cn, dtype=torch.float32, device=dev)
+    radii = torch.zeros(P, dtype=torch.int32, device=dev)
+    if G == 0:
+        return max_alpha, count, feat_sum, radii
+    gid = group_ids.to(device=dev, dtype=torch.int32).contiguous()
+    if gid.numel() != P:
+        raise RuntimeError("group_ids must be [P]")
+    sub = None
+    if G == 1:
+        # the C ABI reads num_groups <= 1 as the ungrouped pass: a single subset is the plain pass on its members
+        sub = gid == 0
+        idx = lambda t: None if t is None else t[sub].contiguous()
+        m3, opac, cols, scl, rot, cov = idx(m3), idx(opac), idx(cols), idx(scl), idx(rot), idx(cov)
+        P_pass, gid_pass = int(m3.shape[0]), None
+        sub_radii = torch.zeros(P_pass, dtype=torch.int32, device=dev)
+    else:
+        P_pass, gid_pass, sub_radii = P, gid, radii
+    lib = _lib.lib()
+    a = _fwd_args(rs, P_pass, Cn, m3, None, cols, opac, scl, rot, cov, bg, view, proj, campos, None, None, None, sub_radii,
+                  gid_pass, G)
+    if P_pass == 0:
+        # nothing is read per Gaussian without Gaussians; the argument check wants a colour source and one covariance form
+        a.colors_precomp = a.scales = a.rotations = ptr(bg)
+        a.cov3D_precomp = None
+    u8 = lambda n: torch.empty(int(n), dtype=torch.uint8, device=dev)
+    stream = _stream()
+    keep = []
+    D = 0
+    if P_pass > 0:
+        gb, gtb, _ = _geom_sizes(P_pass, W, H, Cn, 1)
+        keep += [u8(gb), u8(gtb)]
+        a.geom_buffer, a.geom_tmp = ptr(keep[0]), ptr(keep[1])
+        n = C.c_int64(0)
+        PASS_STATS["blocking"] += 1
+        check(lib.ogs_raster_forward_geometry(C.byref(a), stream, C.byref(n)), "ogs_raster_forward_geometry")
+        D = int(n.value)
+    image = u8(lib.ogs_raster_stats_image_bytes(W, H, G))
+    tmp = u8(lib.ogs_raster_stats_tmp_bytes(G, L, Cn))
+    a.image_buffer = ptr(image)
+    if D > 0:
+        btb, _, _ = _render_sizes(D, W, H, Cn)
+        pl, bt = torch.empty(D, dtype=torch.int32, device=dev), u8(btb)
+        keep += [pl, bt]
+        a.point_list, a.binning_tmp = ptr(pl), ptr(bt)
+    st = _lib.OgsGroupStatsArgs()
+    st.labels, st.num_labels, st.alpha_threshold = ptr(lab), L, float(alpha_threshold)
+    st.max_alpha, st.count, st.feat_sum, st.stats_tmp = ptr(max_alpha), ptr(count), ptr(feat_sum), ptr(tmp)
+    check(lib.ogs_raster_forward_group_stats(C.byref(a), C.byref(st), D, stream), "ogs_raster_forward_group_stats")
+    if sub is not None:
+        radii[sub] = sub_radii
+    return max_alpha, count, feat_sum, radii
+
+
 class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings):
         super().__init__()
