@@ -306,7 +306,7 @@ __global__ __launch_bounds__(kBlock) void radix_scatter_kernel(const uint32_t* _
 //     they wait -- so every wait ends; each spin is bounded all the same: past `spin_limit` polls the workgroup ORs
 //     kAsyncRadixSpin into the library's sticky status word (pinned host memory, ogs_common.h::async_status_word -- a
 //     system-scope atomic that only ever executes on this path), gives up the look-back and writes a wrong permutation
-//     INSIDE its output range (no hang, no stray write); the host raises on the next status check: the read-back every
+//     INSIDE its output range (no hang, no stray write: the final scatter is bounded by n, see there); the host raises on the next status check: the read-back every
 //     forward waits on, the entry of the next forward / backward, ogs_check_async_status (round 4);
 //   * stability: ticket order == memory order of the tiles, ranks inside a tile as in radix_scatter_kernel.
 constexpr uint32_t kStatAgg = 1u << 30, kStatInc = 2u << 30, kStatMask = (1u << 30) - 1u;
@@ -475,8 +475,14 @@ __global__ __launch_bounds__(kBlock) void radix_onesweep_kernel(const uint32_t* 
     for (uint32_t j = tid; j < n_valid; j += kBlock) {
         const uint32_t k = stage_k[j];
         const uint32_t pos = glob_base[(k >> shift) & mask] + j;
-        keys_out[pos] = k;
-        vals_out[pos] = stage_v[j];
+        // pos < n always holds while the keys are a permutation of what radix_hist_all_kernel counted.  After a look-back that
+        // gave up they no longer are: the pass leaves output slots unwritten, the NEXT pass reads whatever those hold, and
+        // digit_base (from the histogram of the original keys) + `before` (from the keys actually met) can then pass the
+        // end of the arrays.  The sort is already reported as failed (kAsyncRadixSpin); it must not write out of bounds too.
+        if ((int64_t)pos < n) {
+            keys_out[pos] = k;
+            vals_out[pos] = stage_v[j];
+        }
     }
 }
 

@@ -19,6 +19,116 @@ def tiny_scene(P, W, H, f, seed=0, log_scale_mean=-3.0, with_ties=False):
     return sc, cam
 
 
+def tanfovs(W, H, fx, fy=None):
+    """(tanfovx, tanfovy) of a W x H image with focal lengths fx, fy in pixels (fy=None: the same focal length)."""
+    return W / (2 * fx), H / (2 * (fx if fy is None else fy))
+
+
+def rotation_matrix(axis, angle):
+    """Rodrigues rotation about `axis` by `angle` radians, float64 [3,3]."""
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.eye(3) + np.sin(angle) * K + (1.0 - np.cos(angle)) * (K @ K)
+
+
+def _quat_of_rotation(R):
+    """unit quaternion (r, x, y, z) of a proper rotation matrix, float64 (largest-component branch: no division by ~0)."""
+    R = np.asarray(R, np.float64)
+    assert abs(np.linalg.det(R) - 1.0) < 1e-6 and np.abs(R @ R.T - np.eye(3)).max() < 1e-6, "not a rotation"
+    q = np.array([1.0 + R[0, 0] + R[1, 1] + R[2, 2], 1.0 + R[0, 0] - R[1, 1] - R[2, 2],
+                  1.0 - R[0, 0] + R[1, 1] - R[2, 2], 1.0 - R[0, 0] - R[1, 1] + R[2, 2]])
+    i = int(q.argmax())
+    if i == 0:
+        q = np.array([q[0], R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    elif i == 1:
+        q = np.array([R[2, 1] - R[1, 2], q[1], R[0, 1] + R[1, 0], R[0, 2] + R[2, 0]])
+    elif i == 2:
+        q = np.array([R[0, 2] - R[2, 0], R[0, 1] + R[1, 0], q[2], R[1, 2] + R[2, 1]])
+    else:
+        q = np.array([R[1, 0] - R[0, 1], R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], q[3]])
+    return q / np.linalg.norm(q)
+
+
+def _quat_mul(a, b):
+    """Hamilton product a * b of (r, x, y, z) quaternions: R(a * b) = R(a) R(b); b may be [P,4]."""
+    ar, ax, ay, az = a
+    br, bx, by, bz = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    return np.stack([ar * br - ax * bx - ay * by - az * bz, ar * bx + ax * br + ay * bz - az * by,
+                     ar * by - ax * bz + ay * br + az * bx, ar * bz + ax * by - ay * bx + az * br], axis=-1)
+
+
+def _poses():
+    """name -> (R, t) of W2C = [R | t].  Quarter turns and the two half turns are signed permutation matrices: exact in fp32, so
+    a transposed or mis-indexed rotation block is a gross error, not rounding.  "general" leaves no entry of the view and
+    projection matrices at zero or one.  "down_neg_z": the camera looks down the world's -z axis (half turn about x).
+    Translations are of scene size (the scenes span z = 2 .. 10 in the camera frame)."""
+    q = lambda rows: np.array(rows, np.float64)
+    return {
+        "quarter_x": (q([[1, 0, 0], [0, 0, -1], [0, 1, 0]]), (0.7, -0.4, 1.3)),
+        "quarter_y": (q([[0, 0, 1], [0, 1, 0], [-1, 0, 0]]), (-1.5, 0.8, 2.0)),
+        "quarter_z": (q([[0, -1, 0], [1, 0, 0], [0, 0, 1]]), (2.2, 1.1, -0.9)),
+        "roll_180": (q([[-1, 0, 0], [0, -1, 0], [0, 0, 1]]), (-0.6, 1.7, 3.1)),
+        "down_neg_z": (q([[1, 0, 0], [0, -1, 0], [0, 0, -1]]), (1.2, -2.3, 0.8)),
+        "general": (rotation_matrix((0.3, -0.8, 0.5), 2.1), (0.7, -0.4, 1.3)),
+        "general_b": (rotation_matrix((-0.6, 0.2, 0.75), -1.3), (-3.0, 2.5, 4.0)),
+    }
+
+
+POSES = _poses()
+
+
+def general_camera(W, H, fx, fy, R, t):
+    """Camera with W2C = [R | t] (X_cam = R X_world + t) and separate focal lengths."""
+    return make_camera(W, H, fx, fy, R=torch.as_tensor(np.asarray(R), dtype=torch.float32),
+                       t=torch.as_tensor(np.asarray(t), dtype=torch.float32))
+
+
+def scene_to_world(sc, R, t):
+    """The scene `sc`, given in the frame of a camera [R | t], in world coordinates: X_w = R^T (X_c - t) and every Gaussian's
+    orientation composed with R^T (Sigma_w = R^T Sigma_c R), so the posed camera sees what the identity camera saw of `sc`.
+    Arithmetic in float64, rounded to fp32 once.  SH coefficients are kept (the view direction they are evaluated at moves
+    with the frame, so SH colours differ from the camera-frame scene's; precomputed colours do not)."""
+    from opengaussian_amd.synthetic import Scene
+    R = np.asarray(R, np.float64)
+    t = np.asarray(t, np.float64)
+    Xw = (sc.means3D.double().numpy() - t[None, :]) @ R                       # rows: (R^T (x - t))^T = (x - t)^T R
+    qw = _quat_mul(_quat_of_rotation(R.T), sc.rotations.double().numpy())
+    qw = qw / np.linalg.norm(qw, axis=1, keepdims=True)
+    f32 = lambda a: torch.tensor(a, dtype=torch.float32).contiguous()
+    return Scene(f32(Xw), sc.scales.clone(), f32(qw), sc.opacities.clone(), sc.shs.clone(), sc.ins_feat.clone())
+
+
+def push_beyond_clamp(sc, W, H, fx, fy, share, scale=0.4, seed=0):
+    """Move `share` of the centres of a CAMERA-FRAME scene to (1.35 .. 1.75) x tanfov -- past the +-1.3 x tanfov clamp of
+    tx/tz, ty/tz (Appendix A.1 step 4) -- in x only, in y only and in both, both signs, and give them scale `scale` so that
+    their footprints still reach the image.  Rows in front of the near plane only.  Returns the moved row indices."""
+    g = torch.Generator().manual_seed(90_000 + seed)
+    tanx, tany = tanfovs(W, H, fx, fy)
+    front = torch.nonzero(sc.means3D[:, 2] > 0.5).reshape(-1)
+    rows = front[torch.randperm(front.numel(), generator=g)[: int(round(share * sc.means3D.shape[0]))]]
+    n = rows.numel()
+    z = sc.means3D[rows, 2]
+    far = (torch.rand(2, n, generator=g) * 0.4 + 1.35) * (torch.randint(0, 2, (2, n), generator=g) * 2.0 - 1.0)
+    near = torch.rand(2, n, generator=g) * 1.8 - 0.9
+    kind = torch.arange(n) % 3                                                 # 0: x beyond, 1: y beyond, 2: both
+    u = torch.where(kind != 1, far[0], near[0])
+    v = torch.where(kind != 0, far[1], near[1])
+    sc.means3D[rows, 0] = u * z * tanx
+    sc.means3D[rows, 1] = v * z * tany
+    sc.scales[rows] = scale * (0.5 + torch.rand(n, 3, generator=g))
+    return rows.numpy()
+
+
+def posed_scene(P, W, H, fx, fy, R, t, seed=0, log_scale_mean=-3.0, beyond_clamp=0.0, clamp_scale=0.4):
+    """make_scene drawn in the camera frame as tiny_scene does, moved to the world frame of the camera [R | t] (fx != fy
+    allowed).  beyond_clamp: share of the centres pushed past the tx/tz, ty/tz clamp (push_beyond_clamp)."""
+    sc = make_scene(P, W, H, fx, fy, seed=seed, log_scale_mean=log_scale_mean)
+    if beyond_clamp:
+        push_beyond_clamp(sc, W, H, fx, fy, beyond_clamp, scale=clamp_scale, seed=seed)
+    return scene_to_world(sc, R, t), general_camera(W, H, fx, fy, R, t)
+
+
 def oracle_inputs(sc, cam, use_sh=True, use_cov=False, feat=None):
     from oracle import raster_oracle as ro
     inp = dict(means3D=sc.means3D.numpy(), opacities=sc.opacities.numpy(),
@@ -38,19 +148,20 @@ def oracle_inputs(sc, cam, use_sh=True, use_cov=False, feat=None):
     return inp
 
 
-def settings_for(cam, bg, sh_degree, device, debug=False):
+def settings_for(cam, bg, sh_degree, device, debug=False, scale_modifier=1.0):
     from opengaussian_amd.rasterizer import GaussianRasterizationSettings
     import math
     return GaussianRasterizationSettings(
         image_height=cam.image_height, image_width=cam.image_width,
         tanfovx=math.tan(cam.FoVx * 0.5), tanfovy=math.tan(cam.FoVy * 0.5),
-        bg=torch.as_tensor(bg, dtype=torch.float32, device=device), scale_modifier=1.0,
+        bg=torch.as_tensor(bg, dtype=torch.float32, device=device), scale_modifier=scale_modifier,
         viewmatrix=cam.world_view_transform.to(device), projmatrix=cam.full_proj_transform.to(device),
         sh_degree=sh_degree, campos=cam.camera_center.to(device), prefiltered=False, debug=debug)
 
 
-def hip_forward(inp, cam, bg, sh_degree, device, requires_grad=False, debug=False, tiny=False):
-    """Run GaussianRasterizer on `device` with the same arrays as the oracle.  Returns (outputs, leaves).
+def hip_forward(inp, cam, bg, sh_degree, device, requires_grad=False, debug=False, tiny=False, scale_modifier=1.0):
+    """Run GaussianRasterizer on `device` with the same arrays as the oracle.  Returns (outputs, leaves).  The field of view
+    comes from `cam` (tanfovx = W / (2 fx), tanfovy = H / (2 fy) separately).
     tiny=False forces the streaming path even for P <= TINY_MAX_P (callers export its binning state)."""
     from opengaussian_amd import rasterizer as R
     from opengaussian_amd.rasterizer import GaussianRasterizer
@@ -58,19 +169,19 @@ def hip_forward(inp, cam, bg, sh_degree, device, requires_grad=False, debug=Fals
     if not tiny:
         R.TINY_MAX_P = 0
     try:
-        return _hip_forward(inp, cam, bg, sh_degree, device, requires_grad, debug)
+        return _hip_forward(inp, cam, bg, sh_degree, device, requires_grad, debug, scale_modifier)
     finally:
         R.TINY_MAX_P = saved
 
 
-def _hip_forward(inp, cam, bg, sh_degree, device, requires_grad, debug):
+def _hip_forward(inp, cam, bg, sh_degree, device, requires_grad, debug, scale_modifier=1.0):
     from opengaussian_amd.rasterizer import GaussianRasterizer
     t = lambda k: (None if inp.get(k) is None else
                    torch.tensor(np.asarray(inp[k]), dtype=torch.float32, device=device, requires_grad=requires_grad))
     leaves = {k: t(k) for k in ("means3D", "opacities", "scales", "rotations", "cov3D_precomp", "shs", "colors_precomp")}
     P = leaves["means3D"].shape[0]
     leaves["means2D"] = torch.zeros(P, 3, dtype=torch.float32, device=device, requires_grad=requires_grad)
-    rast = GaussianRasterizer(settings_for(cam, bg, sh_degree, device, debug))
+    rast = GaussianRasterizer(settings_for(cam, bg, sh_degree, device, debug, scale_modifier))
     out = rast(means3D=leaves["means3D"], means2D=leaves["means2D"], opacities=leaves["opacities"],
                shs=leaves["shs"], colors_precomp=leaves["colors_precomp"], scales=leaves["scales"],
                rotations=leaves["rotations"], cov3D_precomp=leaves["cov3D_precomp"])
@@ -200,6 +311,19 @@ def assert_close_modulo_threshold_flips(got, want, tol=1e-4, flip_tol=4e-3, max_
     assert nbad <= max(max_pixels, 1e-5 * diff.size), f"{nbad} pixels off by more than {tol} (max {diff.max()})"
 
 
+NUDGES = (2e-5, -2e-5, 1e-4, -1e-4)      # relative opacity steps of the constructive flip attribution (see below)
+
+
+def nudged_opacities(inp, rows, rel):
+    """copy of the oracle inputs `inp` with the opacities of `rows` scaled by 1 + rel (fp32)"""
+    out = dict(inp)
+    op = np.array(inp["opacities"], dtype=np.float32, copy=True)
+    flat = op.reshape(-1)
+    flat[rows] = flat[rows] * np.float32(1.0 + rel)
+    out["opacities"] = op
+    return out
+
+
 def lazy(fn):
     """memoised thunk"""
     box = []
@@ -211,7 +335,8 @@ def lazy(fn):
     return get
 
 
-def assert_grads_close_modulo_threshold_flips(got, want, tol, want_fp32=None, flip_tol=1e-3, max_rows=2, what=""):
+def assert_grads_close_modulo_threshold_flips(got, want, tol, want_fp32=None, flip_tol=1e-3, max_rows=2, what="",
+                                              want_nudged=None):
     """Gradient comparison against the float64 oracle at `tol` (relative to the family's largest entry), with every
     Gaussian (row) that misses it ATTRIBUTED to an fp32 decision flip.
 
@@ -222,6 +347,15 @@ def assert_grads_close_modulo_threshold_flips(got, want, tol, want_fp32=None, fl
     (a callable returning the oracle's OWN graph evaluated in fp32 autograd, oracle.render_backward_f64(dtype=float32))
     identifies exactly those rows: a row may miss `tol` against float64 only if the fp32 oracle misses it too, and
     then it must agree with the fp32 oracle to `flip_tol`.  At most max(max_rows, 1e-3 * rows) such rows.
+
+    `want_nudged` (optional; callable (rows, rel) -> the float64 oracle's gradient of this family with the opacities of `rows`
+    scaled by 1 + rel): a second, constructive attribution for the flips that the fp32 oracle does NOT share.  Two fp32
+    evaluations of alpha = opacity * exp(power) differ by a few 1e-6 relative (contracted or separate multiply-adds in
+    `power`, the last ulp of exp), up to ~1e-4 once their conics come from differently ordered fp32 arithmetic, so the
+    device can take a decision the torch fp32 graph does not.  Scaling the Gaussian's opacity by 1 +- NUDGES moves its alphas
+    across the threshold they are within that margin of -- and changes its gradient by that relative amount, nothing else.
+    A row that misses `tol` unexplained by the fp32 oracle must then agree with one of the nudged float64 gradients TO `tol`:
+    it is held as tightly as every other row, against the oracle that takes the device's decision.
     Returns the largest relative error among the rows held to `tol`."""
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
     scale = np.abs(want).max() + 1e-30
@@ -233,10 +367,20 @@ def assert_grads_close_modulo_threshold_flips(got, want, tol, want_fp32=None, fl
         w32 = np.asarray(want_fp32(), np.float64).reshape(want.shape)
         flipped = rows(w32 - want) > 0.5 * tol                      # the fp32 oracle itself leaves the float64 one here
         unexplained = bad & ~flipped
+        nudged = np.zeros_like(bad)
+        if unexplained.any() and want_nudged is not None and int(unexplained.sum()) <= max(max_rows, int(2e-3 * len(err))):
+            for rel in NUDGES:
+                idx = np.nonzero(unexplained)[0]
+                if idx.size == 0:
+                    break
+                wn = np.asarray(want_nudged(idx, rel), np.float64).reshape(want.shape)
+                ok = idx[rows(got - wn)[idx] <= tol]
+                unexplained[ok] = False
+                nudged[ok] = True
         assert not unexplained.any(), (f"{what}: rows {np.nonzero(unexplained)[0][:5]} off by up to {err[unexplained].max():.2e} "
                                        f"although the fp32 oracle agrees with float64 there")
         e32 = rows(got - w32)
-        assert e32[bad].max() < flip_tol, f"{what}: flipped rows differ from the fp32 oracle by {e32[bad].max():.2e}"
+        assert not (bad & ~nudged).any() or e32[bad & ~nudged].max() < flip_tol, f"{what}: flipped rows differ from the fp32 oracle by {e32[bad].max():.2e}"
         assert int(bad.sum()) <= max(max_rows, int(2e-3 * len(err))), f"{what}: {int(bad.sum())} rows attributed to fp32 decision flips"
     return float(err[~bad].max()) if (~bad).any() else 0.0
 
@@ -266,6 +410,26 @@ def assert_grad_family_close(got, want, tol=2e-4, what="", row_rel_tol=GRAD_ROW_
         rel = (rows_e[big] / rows_w[big]).max()
         assert rel <= row_rel_tol, f"{what}: a row above {row_floor:.0e} of the family maximum is off by {rel:.2e} of its own size"
     return float(err)
+
+
+def assert_grad_family_close_modulo_threshold_flips(got, want, tol, want_fp32, what=""):
+    """assert_grad_family_close (both rulers), with the rows that the fp32 oracle itself moves away from the float64 one by
+    more than tol / 2 -- the attribution rule of assert_grads_close_modulo_threshold_flips, which holds those rows to the
+    fp32 oracle -- left out of the comparison.  At most max(2, 2e-3 * rows) rows; the fp32 oracle is evaluated only when
+    the plain check fails."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    try:
+        return assert_grad_family_close(got, want, tol, what=what)
+    except AssertionError:
+        if want_fp32 is None or got.shape != want.shape:
+            raise
+    w32 = np.asarray(want_fp32(), np.float64).reshape(want.shape)
+    scale = np.abs(want).max() + 1e-30
+    flipped = (np.abs(w32 - want) / scale).reshape(want.shape[0], -1).max(axis=1) > 0.5 * tol
+    assert int(flipped.sum()) <= max(2, int(2e-3 * len(flipped))), f"{what}: {int(flipped.sum())} rows moved by the fp32 oracle"
+    got = got.copy()
+    got[flipped] = want[flipped]
+    return assert_grad_family_close(got, want, tol, what=what)
 
 
 # ---- k-means: per-row attribution of every difference (VERDICT r1: no fraction-based tolerances) ---------------

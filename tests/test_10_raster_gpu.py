@@ -187,28 +187,42 @@ def test_scale_rot_path_equals_cov3d_precomp(gpu_device):
     torch.testing.assert_close(c1, c2, atol=0, rtol=0)
 
 
-def _grad_check(inp, cam, W, H, f, device, sh_degree=3, bg=(0.1, 0.2, 0.3), seed=0):
+def _grad_check(inp, cam, W, H, f, device, sh_degree=3, bg=(0.1, 0.2, 0.3), seed=0, fy=None, scale_modifier=1.0, tiny=False,
+                row_ruler=False, skip=(), rows=None):
+    """Every gradient family of the HIP pass against float64 autograd through the oracle.  `f` is the focal length in x, `fy`
+    the one in y (None: the same); row_ruler adds helpers.assert_grad_family_close (per-row ruler) on every family; `skip`
+    names families that are not compared; `rows` (name -> row indices) additionally holds those rows of every family to
+    GRAD_TOL of the SUBSET's own maximum.  Returns the worst relative error per family ("name[rows]" for the subsets)."""
     from oracle import raster_oracle as ro
-    ref = ro.render_forward(W=W, H=H, tanfovx=W / (2 * f), tanfovy=H / (2 * f), bg=np.array(bg, np.float32),
-                            sh_degree=sh_degree, **inp)
+    tanx, tany = helpers.tanfovs(W, H, f, fy)
+    ref = ro.render_forward(W=W, H=H, tanfovx=tanx, tanfovy=tany, bg=np.array(bg, np.float32),
+                            sh_degree=sh_degree, scale_modifier=scale_modifier, **inp)
     Cn = ref["color"].shape[0]
     rng = np.random.default_rng(seed)
     gC, gD, gA = rng.standard_normal((Cn, H, W)), rng.standard_normal((1, H, W)), rng.standard_normal((1, H, W))
-    gref = ro.render_backward_f64(inp, ref["binning"], W, H, W / (2 * f), H / (2 * f), np.array(bg, np.float64),
-                                  gC, gD, gA, sh_degree=sh_degree)
-    (color, radii, depth, alpha), leaves = helpers.hip_forward(inp, cam, bg, sh_degree, device, requires_grad=True)
+    back = lambda **kw: ro.render_backward_f64(inp, ref["binning"], W, H, tanx, tany, np.array(bg, np.float64), gC, gD, gA,
+                                               sh_degree=sh_degree, scale_modifier=scale_modifier, **kw)
+    gref = back()
+    (color, radii, depth, alpha), leaves = helpers.hip_forward(inp, cam, bg, sh_degree, device, requires_grad=True, tiny=tiny,
+                                                               scale_modifier=scale_modifier)
     t = lambda a: torch.tensor(a, dtype=torch.float32, device=device)
     loss = (color * t(gC)).sum() + (depth * t(gD)).sum() + (alpha * t(gA)).sum()
     loss.backward()
-    g32 = helpers.lazy(lambda: ro.render_backward_f64(inp, ref["binning"], W, H, W / (2 * f), H / (2 * f), np.array(bg, np.float64),
-                                                      gC, gD, gA, sh_degree=sh_degree, dtype=torch.float32))
+    g32 = helpers.lazy(lambda: back(dtype=torch.float32))
     out = {}
     for k, v in leaves.items():
-        if v is None or gref.get(k) is None:
+        if v is None or gref.get(k) is None or k in skip:
             continue
         got = v.grad.detach().cpu().double().numpy()
         want = gref[k].reshape(got.shape)
-        out[k] = helpers.assert_grads_close_modulo_threshold_flips(got, want, GRAD_TOL, want_fp32=lambda k=k: g32()[k], what=k)
+        w32 = lambda k=k, shape=got.shape: g32()[k].reshape(shape)
+        out[k] = helpers.assert_grads_close_modulo_threshold_flips(got, want, GRAD_TOL, want_fp32=w32, what=k)
+        if row_ruler:
+            helpers.assert_grad_family_close_modulo_threshold_flips(got, want, GRAD_TOL, w32, what=k)
+        for name, idx in (rows or {}).items():
+            assert np.abs(want[idx]).max() > 0, f"{k}[{name}]: the oracle gradient of these rows is all zero"
+            out[f"{k}[{name}]"] = helpers.assert_grads_close_modulo_threshold_flips(
+                got[idx], want[idx], GRAD_TOL, want_fp32=lambda w32=w32, idx=idx: w32()[idx], what=f"{k}[{name}]")
     return out
 
 

@@ -1,6 +1,7 @@
 """GPU: every BASELINE.json raster configuration against the CPU oracle AT ITS OWN SIZE, forward and backward.
 
     C2   100 k Gaussians, 800x800,   RGB (SH3) fwd+bwd                          (configs[1])
+    C2_posed   C2 seen by a rotated, translated camera with fx != fy (helpers.posed_scene, pose "general")
     C3   500 k Gaussians, 988x731,   RGB (SH3) + 6-D ins_feat, ONE fused pass  (configs[2], LeRF class)
     C4   2 M Gaussians,   648x484,   RGB (SH3) + 6-D ins_feat, ONE fused pass  (configs[3], ScanNet class)
     S1M  1 M Gaussians,   1920x1080, RGB (SH3) + 6-D ins_feat, ONE fused pass  (BASELINE.json `metric`)
@@ -18,7 +19,15 @@ The fused 9-channel pass is held to what the reference's separate passes produce
 104-151, train.py:431-436): oracle pass A = RGB with every gradient family, oracle pass B = the 6 feature channels
 with gradient to the features only.
 Tolerances: integers exact; images 1e-4 (depth 1e-3: un-normalised sum of z*w, z <= 10) up to the documented
-exp-threshold flips; gradients 2e-4 of the family's max vs float64 autograd."""
+exp-threshold flips; gradients 2e-4 of the family's max vs float64 autograd.
+
+C2_posed, measured: means3D 1.8e-4, scales 1.9e-4, rotations 8.8e-5, opacities 1.0e-4, shs 7.3e-5, means2D 2.0e-4 of the
+family maximum on the rows held to the bar.  One Gaussian (row 60846, dL/drotations off by 4.2e-4 of the family maximum, 14 % of
+its own size) takes the alpha >= 1/255 decision of ONE pixel differently from float64 AND from the torch fp32 graph: its alpha
+there is 1/255 * (1 + 2.3e-6) in the oracle's fp32 NumPy order, below 1/255 in float64.  With its opacity scaled by 1 + 2e-5 the
+float64 oracle takes the device's decision and agrees with the device to 1.1e-7 of the family maximum in every family; the
+posed case therefore passes `want_nudged` (helpers.assert_grads_close_modulo_threshold_flips), which holds such a row to the
+same 2e-4 against that oracle.  The unposed configurations are checked as before, without it."""
 import numpy as np
 import pytest
 import torch
@@ -39,18 +48,24 @@ CONFIGS = {
     "C4": (2_000_000, 648, 484, 500.0, True, 24),
     "S1M": (1_000_000, 1920, 1080, 1000.0, True, 64),
 }
+# the same checks under a general camera pose (helpers.POSES) with fx != fy: name -> (configuration, pose, focal length in y)
+POSED = {"C2_posed": ("C2", "general", 620.0)}
 
 
-@pytest.mark.parametrize("name", list(CONFIGS))
+@pytest.mark.parametrize("name", list(CONFIGS) + list(POSED))
 def test_baseline_config_forward_and_backward_vs_oracle(gpu_device, name):
     from oracle import raster_oracle as ro
     from opengaussian_amd.rasterizer import GaussianRasterizer, rasterize_fused
     torch.set_flush_denormal(True)
-    P, W, H, f, fused, n_sample = CONFIGS[name]
+    base, pose, fy = POSED.get(name, (name, None, None))
+    P, W, H, f, fused, n_sample = CONFIGS[base]
     dev = gpu_device
-    sc = make_scene(P, W, H, f, f, seed=0)
-    cam = make_camera(W, H, f, f)
-    tanx, tany = W / (2 * f), H / (2 * f)
+    if pose is None:
+        sc = make_scene(P, W, H, f, f, seed=0)
+        cam = make_camera(W, H, f, f)
+    else:
+        sc, cam = helpers.posed_scene(P, W, H, f, fy, *helpers.POSES[pose], seed=0, log_scale_mean=-4.5)
+    tanx, tany = helpers.tanfovs(W, H, f, fy)
     inp = helpers.oracle_inputs(sc, cam, use_sh=True)
 
     # ---- oracle: full preprocess + binning ---------------------------------------------------------------
@@ -125,13 +140,24 @@ def test_baseline_config_forward_and_backward_vs_oracle(gpu_device, name):
                                                      tiles=band_tiles, dtype=torch.float32)["colors_precomp"]
         return w32
     want32 = helpers.lazy(_want32)
+    nudge_cache = {}
+
+    def _want_nudged(k, rows, rel):
+        # posed case only: the float64 oracle with the opacities of `rows` scaled by 1 + rel, i.e. with their borderline
+        # alpha >= 1/255 decisions taken the other way (helpers.assert_grads_close_modulo_threshold_flips, want_nudged)
+        key = (tuple(rows.tolist()), rel)
+        if key not in nudge_cache:
+            nudge_cache[key] = ro.render_backward_f64(helpers.nudged_opacities(inp, rows, rel), b, W, H, tanx, tany, np.zeros(3),
+                                                      gC[:3], zero1, gA, sh_degree=3, tiles=band_tiles)
+        return nudge_cache[key][k]
     got = {k: leaves[k].grad for k in leaves if leaves[k].grad is not None} | {"means2D": m2.grad}
     assert set(want) <= set(got), (sorted(want), sorted(got))
     errs = {}
     for k, w in want.items():
         gk = got[k].cpu().double().numpy().reshape(w.shape)
-        errs[k] = helpers.assert_grads_close_modulo_threshold_flips(gk, w, GRAD_TOL, want_fp32=lambda k=k: want32()[k],
-                                                                    what=f"{name} {k}")
+        errs[k] = helpers.assert_grads_close_modulo_threshold_flips(
+            gk, w, GRAD_TOL, want_fp32=lambda k=k: want32()[k], what=f"{name} {k}",
+            want_nudged=None if pose is None or k == "ins_feat" else (lambda rows, rel, k=k: _want_nudged(k, rows, rel)))
     print(name + ": " + ", ".join(f"{k}={e:.2e}" for k, e in errs.items()))
 
 
