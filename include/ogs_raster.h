@@ -18,9 +18,10 @@
  * Forward is split in two calls because the size of the per-(Gaussian,tile) list
  * (`num_rendered`) is only known after the geometry phase:
  *
- *   ogs_raster_forward_geometry()  preprocess -> depth sort -> scan      (A.1, first half of A.2)
+ *   ogs_raster_forward_geometry()  preprocess -> scan                     (A.1, first half of A.2)
  *        -> host learns num_rendered, allocates point_list / binning scratch
- *   ogs_raster_forward_render()    duplicate -> tile sort -> ranges -> blend   (A.2, A.3)
+ *   ogs_raster_forward_render()    duplicate -> tile sort -> ranges -> per-tile depth sort -> blend   (A.2, A.3)
+ *   (grouped passes and P <= 1024 sort the Gaussians by depth in the geometry phase instead of each tile's list)
  *
  * Replaces the single upstream call `rasterize_gaussians(bg, means3D, colors, opacity, scales,
  * rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, H, W, sh,
@@ -192,7 +193,8 @@ size_t ogs_raster_backward_tmp_bytes(int32_t P);
 size_t ogs_raster_sorted_bytes(int64_t num_rendered, int32_t C);
 size_t ogs_raster_quad_list_bytes(int64_t num_rendered);
 
-/* Phase 1: fills radii + geom_buffer, leaves the depth order and tile offsets in geom_tmp, writes
+/* Phase 1: fills radii + geom_buffer, leaves the depth keys and tile offsets (and, for grouped passes and P <= 1024, the
+ * depth order) in geom_tmp, writes
  * num_rendered to *num_rendered_host (host memory) and returns after the stream has finished it
  * (the same blocking read-back the reference performs once per forward).
  * num_rendered_host == NULL: no read-back, no synchronisation (see the deferred variant below).  out_color / out_depth /
@@ -224,6 +226,11 @@ int ogs_raster_forward_render_deferred(const OgsRasterFwdArgs* args, int64_t cap
  * read-back. */
 size_t ogs_raster_tiny_max_points(void);
 int ogs_raster_forward_tiny(const OgsRasterFwdArgs* args, void* stream);
+
+/* List-length limits of the render phase's per-tile depth sort (test hook for their boundaries; no effect on results):
+ * level 0: the longest list one wave sorts alone; level 1: the longest list a workgroup sorts in LDS (longer lists take
+ * passes through global memory); 0 for any other level. */
+size_t ogs_raster_tile_sort_capacity(int32_t level);
 
 /* Re-blend of a KEPT pass (new capability; no reference counterpart -- the reference re-runs preprocess, both sorts and the
  * duplication on every call).  From stage 1 on the reference trains `_ins_feat` alone (train.py:431-436: every other Gaussian

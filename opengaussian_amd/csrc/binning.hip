@@ -3,10 +3,12 @@
 // integer work: coalesced 4-byte streams, LDS only for per-workgroup histograms, no float math.
 //
 // Sort strategy (DESIGN.md "binning"): the reference sorts D=(Gaussian,tile) duplicates on a 64-bit
-// key (tile<<32 | depth bits) -- 6 byte-digit passes over D.  Here the P Gaussians are sorted by depth
-// ONCE (4 passes over P), duplicates are emitted in that order, and a STABLE sort on the tile id alone
-// (ceil(log2 T / 8) = 2 passes over D at 1080p) yields bit-identical order: depth ascending inside a
-// tile, ties by Gaussian index.  ~3x less sort traffic on the dominant D term.
+// key (tile<<32 | depth bits) -- 6 byte-digit passes over D.  Here duplicates are emitted in Gaussian-index
+// order, a STABLE sort on the tile id alone (ceil(log2 T / 8) = 2 passes over D at 1080p) groups them
+// with every tile's list in id order, and one launch then sorts each tile's short list by depth in LDS
+// (tile_depth_sort_kernel): bit-identical order -- depth ascending inside a tile, ties by Gaussian index.
+// Grouped passes (up to 2^31 virtual tiles of a few entries) and the small path instead sort the P
+// Gaussians by depth once and emit the duplicates in that order.
 #include <stdlib.h>
 #include <string.h>
 
@@ -519,6 +521,331 @@ __global__ __launch_bounds__(kBlock) void tile_ranges_kernel(const uint32_t* __r
     }
 }
 
+// ---- per-tile depth order ----------------------------------------------------------------------------------------------
+// After the stable tile sort a tile's segment of the point list holds its Gaussians in id order (duplicate_kernel emits the
+// pairs in Gaussian-index order).  The segment is permuted in place into (depth key, Gaussian id) order: stable LSD passes on
+// the 32-bit key, so ties keep the id order.  The keys are gathered from the compact per-Gaussian key array preprocess wrote
+// (4 B per Gaussian), by the id in the value; the reach flag (bit 31) travels with the value.  Only the bits that differ inside
+// the tile are sorted on: [lowest, highest differing bit] in ceil(span / 8) passes of <= 8 bits.
+// A workgroup takes four tiles (tile_order[4b .. 4b+3]):
+//   * lists up to kWaveSortCap entries: one wave each, no workgroup barrier -- the common case (S1M: ~440 entries);
+//   * then, one after the other, its lists up to kTileSortCap entries: all four waves, in LDS;
+//   * longer lists: the same four-wave ranking on chunks of kTileSortCap entries, passes ping-pong between the segment and
+//     the same positions of `scratch` (a D-sized buffer the tile sort left free), a histogram pass over the list per digit.
+// Ranking inside a wave: every lane ORs its lane bit into the 64-bit match mask of its digit (LDS), reads the mask back -- the
+// lanes with the same digit -- and the lowest of them adds their count to the wave's running digit count.  One LDS round trip
+// per item whatever the digit width (a ballot per digit bit cost ~40 VALU per item).  Entry e of a wave's share is item e / 64,
+// lane e % 64; with several waves the share of wave w is [w * chunk, (w + 1) * chunk), chunk = 64 * ceil(m / 256), so
+// (wave, item, lane) order is memory order, which is what stability needs.
+constexpr int kTileSortWaves = kBlock / kWave;
+struct TileSortLds {
+    uint32_t hist[kTileSortWaves][256];     // per wave: running digit counts, then digit starts / wave offsets
+    uint32_t dig_start[256];                // four-wave ranking: workgroup-local start of every digit
+    uint32_t base[256];                     // long lists: output position of the next entry of each digit
+    uint32_t scan_sums[4];
+    uint32_t red[2];                        // AND / OR of a four-wave tile's keys
+    uint2 range[kTileSortWaves];            // the workgroup's four tiles
+    uint32_t kv[2 * kTileSortCap];          // keys, values; while a pass ranks, the 256 match masks of wave w (2 KB) alias the
+                                            // start of quarter w
+};
+// explicit LDS pointers: volatile / atomic accesses through generic ones stay generic (flat), and one such form ended in an
+// invalid instruction
+typedef __attribute__((address_space(3))) volatile uint32_t LdsWord;
+typedef __attribute__((address_space(3))) unsigned long long LdsMask;
+__device__ __forceinline__ LdsWord* lds_words(uint32_t* p) { return (LdsWord*)p; }
+__device__ __forceinline__ LdsMask* wave_masks(TileSortLds& sm, int wave) { return (LdsMask*)(sm.kv + wave * 2 * kWaveSortCap); }
+
+// zero a wave's 256 digit counts and 256 match masks (wave-local)
+__device__ __forceinline__ void wave_rank_clear(LdsWord* hist, LdsMask* masks) {
+    const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        hist[lane + j * kWave] = 0u;
+        __hip_atomic_store(&masks[lane + j * kWave], 0ull, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Stable ranking of a wave's items on digit (key >> shift) & mask: rank[i] = the wave's earlier entries with the same digit
+// (+ the count it had before), hist[d] += the wave's entries of digit d.  Item i, lane l is entry first + 64 i + l, valid below m.
+// The masks start zeroed and are left zeroed.
+__device__ __forceinline__ void wave_rank(LdsWord* hist, LdsMask* masks, const uint32_t (&key)[kTileSortItems],
+                                          uint32_t (&rank)[kTileSortItems], int ipl, int first, int m, int shift,
+                                          uint32_t mask) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const unsigned long long me = 1ull << lane;
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        if (i >= ipl) continue;                                  // wave-uniform
+        const bool valid = first + i * kWave + lane < m;
+        const uint32_t d = (key[i] >> shift) & mask;
+        if (valid) __hip_atomic_fetch_or(&masks[d], me, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        __builtin_amdgcn_wave_barrier();
+        const unsigned long long peers =
+            valid ? __hip_atomic_load(&masks[d], __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_WAVEFRONT) : 0ull;
+        const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));
+        uint32_t pre = 0;
+        if (valid) pre = hist[d];
+        __builtin_amdgcn_wave_barrier();
+        if (valid && r == 0) {
+            hist[d] = pre + (uint32_t)__popcll(peers);
+            __hip_atomic_store(&masks[d], 0ull, __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+        __builtin_amdgcn_wave_barrier();
+        rank[i] = pre + r;
+    }
+}
+
+// Item i of this lane: entry e = first + 64 i of list[0, m), and its key.  All loads first, then all key gathers, with no
+// lane-dependent branch in between: every item's load is in flight at once (a guarded load + gather per item made the compiler
+// wait for each one in turn).  Lanes past the end load the last entry again: a copy of a valid key changes no AND / OR, and the
+// ranking leaves those lanes out.
+__device__ __forceinline__ void load_items(const uint32_t* __restrict__ list, const uint32_t* __restrict__ depth_keys,
+                                           uint32_t (&key)[kTileSortItems], uint32_t (&val)[kTileSortItems], int ipl, int first,
+                                           int m) {
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        if (i >= ipl) continue;                                  // wave-uniform
+        val[i] = list[min(first + i * kWave, m - 1)];
+    }
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        if (i >= ipl) continue;
+        key[i] = depth_keys[val[i] & kGidMask];
+    }
+}
+
+// Four-wave ranking of one chunk of m entries (caller: a workgroup barrier since the key / value space was last read).
+// Afterwards rank[i] + hist[wave][d] is an entry's position among the chunk's entries of digit d, dig_start[d] the chunk-local
+// start of digit d.  Returns the chunk's count of digit `threadIdx.x`.
+__device__ __forceinline__ uint32_t tile_sort_rank(TileSortLds& sm, const uint32_t (&key)[kTileSortItems],
+                                                   uint32_t (&rank)[kTileSortItems], int ipl, int chunk, int m, int shift,
+                                                   uint32_t mask) {
+    const int tid = threadIdx.x, wave = tid >> 6;
+    LdsWord* hist = lds_words(sm.hist[wave]);
+    LdsMask* masks = wave_masks(sm, wave);
+    wave_rank_clear(hist, masks);
+    wave_rank(hist, masks, key, rank, ipl, wave * chunk, m, shift, mask);
+    __syncthreads();
+    uint32_t run_len = 0;
+#pragma unroll
+    for (int w = 0; w < kTileSortWaves; ++w) {
+        const uint32_t t = sm.hist[w][tid];
+        sm.hist[w][tid] = run_len;
+        run_len += t;
+    }
+    uint32_t total;
+    sm.dig_start[tid] = block_exclusive_scan(run_len, total, sm.scan_sums);
+    __syncthreads();
+    return run_len;
+}
+
+// One wave sorts a list of 2 .. kWaveSortCap entries in its quarter of the key / value space.
+__device__ __forceinline__ void wave_sort_list(TileSortLds& sm, uint32_t* __restrict__ seg, int n,
+                                               const uint32_t* __restrict__ depth_keys) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    LdsWord* wk = lds_words(sm.kv + wave * 2 * kWaveSortCap);
+    LdsWord* wv = wk + kWaveSortCap;
+    LdsWord* hist = lds_words(sm.hist[wave]);
+    LdsMask* masks = wave_masks(sm, wave);
+    uint32_t key[kTileSortItems], val[kTileSortItems], rank[kTileSortItems];
+    const int ipl = (n + kWave - 1) / kWave;
+    load_items(seg, depth_keys, key, val, ipl, lane, n);
+    uint32_t k_and = 0xFFFFFFFFu, k_or = 0u;
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        if (i >= ipl) continue;
+        k_and &= key[i];
+        k_or |= key[i];
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        k_and &= (uint32_t)__shfl_xor((int)k_and, d, kWave);
+        k_or |= (uint32_t)__shfl_xor((int)k_or, d, kWave);
+    }
+    const uint32_t diff = (uint32_t)__builtin_amdgcn_readfirstlane((int)(k_and ^ k_or));
+    if (diff == 0u) return;                                      // one key for the whole list: id order is the answer
+    const int lo = __builtin_ctz(diff), hi = 31 - __builtin_clz(diff);
+    const int npass = (hi - lo + 8) / 8;
+    const int per = (hi - lo + npass) / npass;                   // ceil(span / npass) <= 8
+    for (int p = 0; p < npass; ++p) {
+        const int shift = lo + p * per, bits = min(per, hi + 1 - shift);
+        const uint32_t mask = (1u << bits) - 1u;
+        wave_rank_clear(hist, masks);
+        wave_rank(hist, masks, key, rank, ipl, 0, n, shift, mask);
+        // digit starts: lane l scans digits 4l .. 4l + 3
+        uint32_t c[4], sum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[j] = hist[4 * lane + j]; sum += c[j]; }
+        uint32_t run = wave_inclusive_scan(sum) - sum;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { hist[4 * lane + j] = run; run += c[j]; }
+        __builtin_amdgcn_wave_barrier();
+        // positions first (every item's LDS read in flight at once), then the guarded writes
+#pragma unroll
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl) continue;
+            rank[i] += hist[(key[i] >> shift) & mask];
+        }
+#pragma unroll
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl) continue;
+            if (i * kWave + lane < n) {
+                wk[rank[i]] = key[i];
+                wv[rank[i]] = val[i];
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (p + 1 < npass) {
+#pragma unroll
+            for (int i = 0; i < kTileSortItems; ++i) {
+                if (i >= ipl) continue;
+                const int e = min(i * kWave + lane, n - 1);     // lanes past the end: a copy, left out of the ranking
+                key[i] = wk[e];
+                val[i] = wv[e];
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    for (int j = lane; j < n; j += kWave) seg[j] = wv[j];
+}
+
+// The whole workgroup sorts one list of more than kWaveSortCap entries.
+__device__ __forceinline__ void block_sort_list(TileSortLds& sm, uint32_t* __restrict__ seg, uint32_t* __restrict__ alt, int n,
+                                                const uint32_t* __restrict__ depth_keys) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool in_lds = n <= kTileSortCap;
+    uint32_t key[kTileSortItems], val[kTileSortItems], rank[kTileSortItems];
+    __syncthreads();                                             // the previous list's use of the LDS is over
+    if (tid < 2) sm.red[tid] = tid == 0 ? 0xFFFFFFFFu : 0u;
+    uint32_t k_and = 0xFFFFFFFFu, k_or = 0u;
+    const int ipl0 = (min(n, kTileSortCap) + kBlock - 1) / kBlock, chunk0 = ipl0 * kWave;
+    if (in_lds) {
+        load_items(seg, depth_keys, key, val, ipl0, wave * chunk0 + lane, n);
+#pragma unroll
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl0) continue;
+            k_and &= key[i];
+            k_or |= key[i];
+        }
+    } else {
+        for (int j = tid; j < n; j += kBlock) {
+            const uint32_t k = depth_keys[seg[j] & kGidMask];
+            k_and &= k;
+            k_or |= k;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        k_and &= (uint32_t)__shfl_xor((int)k_and, d, kWave);
+        k_or |= (uint32_t)__shfl_xor((int)k_or, d, kWave);
+    }
+    __syncthreads();
+    if (lane == 0) { atomicAnd(&sm.red[0], k_and); atomicOr(&sm.red[1], k_or); }
+    __syncthreads();
+    const uint32_t diff = sm.red[0] ^ sm.red[1];
+    if (diff == 0u) return;                                      // block-uniform: one key for the whole list
+    const int lo = __builtin_ctz(diff), hi = 31 - __builtin_clz(diff);
+    const int npass = (hi - lo + 8) / 8;
+    const int per = (hi - lo + npass) / npass;
+    uint32_t* const sk = sm.kv;
+    uint32_t* const sv = sm.kv + kTileSortCap;
+
+    if (in_lds) {
+        for (int p = 0; p < npass; ++p) {
+            const int shift = lo + p * per, bits = min(per, hi + 1 - shift);
+            const uint32_t mask = (1u << bits) - 1u;
+            tile_sort_rank(sm, key, rank, ipl0, chunk0, n, shift, mask);
+#pragma unroll
+            for (int i = 0; i < kTileSortItems; ++i) {
+                if (i >= ipl0) continue;
+                const uint32_t d = (key[i] >> shift) & mask;
+                rank[i] += sm.dig_start[d] + sm.hist[wave][d];
+            }
+#pragma unroll
+            for (int i = 0; i < kTileSortItems; ++i) {
+                if (i >= ipl0) continue;
+                if (wave * chunk0 + i * kWave + lane < n) {
+                    sk[rank[i]] = key[i];
+                    sv[rank[i]] = val[i];
+                }
+            }
+            __syncthreads();
+            if (p + 1 < npass) {
+#pragma unroll
+                for (int i = 0; i < kTileSortItems; ++i) {
+                    if (i >= ipl0) continue;
+                    const int e = min(wave * chunk0 + i * kWave + lane, n - 1);
+                    key[i] = sk[e];
+                    val[i] = sv[e];
+                }
+                __syncthreads();                                 // read before the next pass' masks overwrite the space
+            }
+        }
+        for (int j = tid; j < n; j += kBlock) seg[j] = sv[j];
+        return;
+    }
+
+    // long list: every pass streams the list through the chunk ranking, global memory in and out
+    for (int p = 0; p < npass; ++p) {
+        const int shift = lo + p * per, bits = min(per, hi + 1 - shift);
+        const uint32_t mask = (1u << bits) - 1u;
+        const uint32_t* __restrict__ src = (p & 1) ? alt : seg;
+        uint32_t* __restrict__ dst = (p & 1) ? seg : alt;
+        sm.base[tid] = 0u;
+        __syncthreads();
+        for (int j = tid; j < n; j += kBlock) atomicAdd(&sm.base[(depth_keys[src[j] & kGidMask] >> shift) & mask], 1u);
+        __syncthreads();
+        uint32_t total;
+        const uint32_t start = block_exclusive_scan(sm.base[tid], total, sm.scan_sums);
+        sm.base[tid] = start;
+        for (int c0 = 0; c0 < n; c0 += kTileSortCap) {
+            const int m = min(kTileSortCap, n - c0);
+            const int ipl = (m + kBlock - 1) / kBlock, chunk = ipl * kWave;
+            load_items(src + c0, depth_keys, key, val, ipl, wave * chunk + lane, m);
+            const uint32_t cnt = tile_sort_rank(sm, key, rank, ipl, chunk, m, shift, mask);
+#pragma unroll
+            for (int i = 0; i < kTileSortItems; ++i) {
+                if (i >= ipl) continue;
+                if (wave * chunk + i * kWave + lane < m) {
+                    const uint32_t d = (key[i] >> shift) & mask;
+                    dst[sm.base[d] + sm.hist[wave][d] + rank[i]] = val[i];
+                }
+            }
+            __syncthreads();                                     // every read of base[] and hist[] of this chunk is done
+            sm.base[tid] += cnt;
+        }
+        __syncthreads();                                         // dst complete (workgroup-scope fence) before it is read as src
+    }
+    if (npass & 1) {
+        for (int j = tid; j < n; j += kBlock) seg[j] = alt[j];
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void tile_depth_sort_kernel(const uint2* __restrict__ ranges, int tiles,
+                                                                 const uint32_t* __restrict__ tile_order,
+                                                                 uint32_t* __restrict__ point_list,
+                                                                 const uint32_t* __restrict__ depth_keys,
+                                                                 uint32_t* __restrict__ scratch) {
+    __shared__ TileSortLds sm;
+    const int wave = threadIdx.x >> 6;
+    if (threadIdx.x < kTileSortWaves) {
+        const int b = blockIdx.x * kTileSortWaves + threadIdx.x;
+        sm.range[threadIdx.x] = b < tiles ? ranges[tile_order ? tile_order[b] : (uint32_t)b] : make_uint2(0u, 0u);
+    }
+    __syncthreads();
+    // (readfirstlane: the list bounds are uniform -- the addresses then live in SGPRs, not in 2 VGPRs per item)
+    const uint32_t x = (uint32_t)__builtin_amdgcn_readfirstlane((int)sm.range[wave].x);
+    const int n = __builtin_amdgcn_readfirstlane((int)(sm.range[wave].y - sm.range[wave].x));
+    if (n >= 2 && n <= kWaveSortCap) wave_sort_list(sm, point_list + x, n, depth_keys);
+#pragma unroll 1
+    for (int w = 0; w < kTileSortWaves; ++w) {
+        const uint32_t xw = (uint32_t)__builtin_amdgcn_readfirstlane((int)sm.range[w].x);
+        const int nw = __builtin_amdgcn_readfirstlane((int)(sm.range[w].y - sm.range[w].x));
+        if (nw > kWaveSortCap) block_sort_list(sm, point_list + xw, scratch + xw, nw, depth_keys);        // block-uniform
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void export_keys_kernel(const uint2* __restrict__ ranges,
                                                              const uint32_t* __restrict__ point_list,
                                                              const float4* __restrict__ rec, int recv4,
@@ -720,6 +1047,17 @@ int launch_tile_ranges(const uint32_t* tile_keys_sorted, int64_t D, uint2* range
     if (D <= 0) return OGS_OK;
     const int grid = (int)((D + (int64_t)kBlock * kRangeItems - 1) / ((int64_t)kBlock * kRangeItems));
     OGS_LAUNCH(tile_ranges_kernel, dim3(grid), dim3(kBlock), 0, s, tile_keys_sorted, D, n_dev, ranges);
+    OGS_LAUNCH_CHECK(debug, s);
+    return OGS_OK;
+}
+
+int launch_tile_depth_sort(const uint2* ranges, int64_t tiles, const uint32_t* tile_order, uint32_t* point_list,
+                           const uint32_t* depth_keys, uint32_t* scratch, hipStream_t s, int debug) {
+    if (tiles <= 0) return OGS_OK;
+    if (tiles >= (1ll << 31)) { set_error("tile_depth_sort: %lld tiles", (long long)tiles); return OGS_ERR_UNSUPPORTED; }
+    const unsigned grid = (unsigned)((tiles + kTileSortWaves - 1) / kTileSortWaves);
+    OGS_LAUNCH(tile_depth_sort_kernel, dim3(grid), dim3(kBlock), 0, s, ranges, (int)tiles, tile_order, point_list, depth_keys,
+               scratch);
     OGS_LAUNCH_CHECK(debug, s);
     return OGS_OK;
 }

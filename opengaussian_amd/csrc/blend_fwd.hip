@@ -907,12 +907,12 @@ __global__ __launch_bounds__(kOrderThreads) void tile_order_kernel(const uint2* 
 
 // D > 0: pack and blend in one launch; an empty list: no counts to pack, the stand-alone blend writes the background
 template <int C>
-int launch_c(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& is, int64_t D, hipStream_t s) {
+int launch_c(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& is, int64_t D, hipStream_t s, bool order_ready) {
     const int gx = (a.W + kTile - 1) / kTile, gy = (a.H + kTile - 1) / kTile;
     const int tiles = gx * gy;
     const unsigned vtiles = (unsigned)tiles * (unsigned)num_groups_of(a.num_groups);
     if (D > 0) {
-        const uint32_t* order = launch_tile_order(is, vtiles, a.P, s, a.debug);
+        const uint32_t* order = order_ready ? tile_order_of(is, vtiles, a.P) : launch_tile_order(is, vtiles, a.P, s, a.debug);
         static constexpr const char* const kChunked[4] = {"pack_blend_chunked_kernel<3>", "pack_blend_chunked_kernel<6>",
                                                           "pack_blend_chunked_kernel<9>", "pack_blend_chunked_kernel<12>"};
         OGS_LAUNCH_NAMED(chan_name<C>(kChunked), pack_blend_chunked_kernel<C>, dim3(vtiles), dim3(kBlock), 0, s,
@@ -936,7 +936,8 @@ int launch_c(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& i
 // statistics variant of launch_c: the chunked walk on every virtual tile (an empty list included: n = 0, the pixels keep the
 // background), then the fixed-point sums to fp32.  The outputs and the fixed-point scratch are cleared here.
 template <int C>
-int stats_c(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& sa, const GeomState& gs, const ImageState& is, hipStream_t s) {
+int stats_c(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& sa, const GeomState& gs, const ImageState& is, hipStream_t s,
+            bool order_ready) {
     const int gx = (a.W + kTile - 1) / kTile, gy = (a.H + kTile - 1) / kTile;
     const int tiles = gx * gy;
     const int G = num_groups_of(a.num_groups);
@@ -946,7 +947,7 @@ int stats_c(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& sa, const GeomSt
     OGS_HIP_CHECK(hipMemsetAsync(sa.max_alpha, 0, (size_t)G * sizeof(float), s));
     OGS_HIP_CHECK(hipMemsetAsync(sa.count, 0, rows * sizeof(int64_t), s));
     OGS_HIP_CHECK(hipMemsetAsync(fixed, 0, rows * C * sizeof(long long), s));
-    const uint32_t* order = launch_tile_order(is, vtiles, a.P, s, a.debug);
+    const uint32_t* order = order_ready ? tile_order_of(is, vtiles, a.P) : launch_tile_order(is, vtiles, a.P, s, a.debug);
     GroupStatsOut st;
     st.labels = sa.labels;
     st.L = sa.num_labels;
@@ -1077,23 +1078,23 @@ int launch_tile_order_test(const uint32_t* ranges, int64_t vtiles, uint32_t* ord
 }
 
 int launch_blend_forward(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& is, int64_t D,
-                         hipStream_t s) {
+                         hipStream_t s, bool order_ready) {
     switch (a.C) {
-        case 3: return launch_c<3>(a, gs, is, D, s);
-        case 6: return launch_c<6>(a, gs, is, D, s);
-        case 9: return launch_c<9>(a, gs, is, D, s);
-        case 12: return launch_c<12>(a, gs, is, D, s);
+        case 3: return launch_c<3>(a, gs, is, D, s, order_ready);
+        case 6: return launch_c<6>(a, gs, is, D, s, order_ready);
+        case 9: return launch_c<9>(a, gs, is, D, s, order_ready);
+        case 12: return launch_c<12>(a, gs, is, D, s, order_ready);
         default: set_error("unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
     }
 }
 
 int launch_group_stats(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& st, const GeomState& gs, const ImageState& is,
-                       hipStream_t s) {
+                       hipStream_t s, bool order_ready) {
     switch (a.C) {
-        case 3: return stats_c<3>(a, st, gs, is, s);
-        case 6: return stats_c<6>(a, st, gs, is, s);
-        case 9: return stats_c<9>(a, st, gs, is, s);
-        case 12: return stats_c<12>(a, st, gs, is, s);
+        case 3: return stats_c<3>(a, st, gs, is, s, order_ready);
+        case 6: return stats_c<6>(a, st, gs, is, s, order_ready);
+        case 9: return stats_c<9>(a, st, gs, is, s, order_ready);
+        case 12: return stats_c<12>(a, st, gs, is, s, order_ready);
         default: set_error("unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
     }
 }

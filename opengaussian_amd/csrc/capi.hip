@@ -149,7 +149,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 400; }
+int ogs_version(void) { return 401; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 
@@ -229,10 +229,19 @@ int ogs_raster_forward_geometry(const OgsRasterFwdArgs* a, void* stream_, int64_
         // small pass: preprocess + depth order + scan in ONE single-workgroup launch instead of 15 (preprocess_fwd.hip)
         rc = launch_small_geometry(*a, gs, gt, s);
         if (rc != OGS_OK) return rc;
+    } else if (per_tile_depth_order(*a)) {
+        // no depth sort: duplicate walks the Gaussians in index order and every tile's list is sorted by depth in the render
+        // phase (tile_depth_sort_kernel, which gathers keys[0] as preprocess leaves it).  A culled Gaussian has tiles_touched 0,
+        // so the scan and duplicate pass over it.  offsets[i] = exclusive scan of tiles_touched; total = num_rendered
+        rc = launch_preprocess(*a, gs, gt, s);
+        if (rc != OGS_OK) return rc;
+        rc = exclusive_scan_u32(gt.tiles_touched, nullptr, gt.offsets, a->P, gt.num_rendered, gt.sort_tmp, s, a->debug);
+        if (rc != OGS_OK) return rc;
     } else {
         rc = launch_preprocess(*a, gs, gt, s);
         if (rc != OGS_OK) return rc;
-        // depth sort of the Gaussians that are drawn: 4 x 8-bit stable passes, ends in keys[0]/order[0].  A Gaussian that is
+        // grouped pass (up to 2^31 virtual tiles of a few entries each: the lists are not sorted one by one, the Gaussians are
+        // sorted once): depth sort of the Gaussians that are drawn, 4 x 8-bit stable passes, ends in keys[0]/order[0].  A Gaussian that is
         // not (behind the near plane, outside every group, degenerate, empty tile rect: preprocess gave it the key kDropKey)
         // leaves the list in the FIRST pass -- the mechanism the tile sort uses for its unreachable pairs -- and the other
         // three passes, the scan and duplicate run on the visible count (device word; the launches stay sized for P).  On the
@@ -294,6 +303,8 @@ static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipS
     const int64_t tiles = (int64_t)gx * gy * G;             // virtual tiles: image (group) * tiles_per_image + tile
     if (tiles >= (1ll << 31)) { set_error("%d groups x %d tiles exceed 2^31 virtual tiles", G, gx * gy); return OGS_ERR_UNSUPPORTED; }
     const GeomState gs = GeomState::carve(a->geom_buffer, a->P > 0 ? a->P : 1, a->C);
+    const bool per_tile = per_tile_depth_order(*a);        // as the geometry phase of this pass decided
+    bool order_ready = false;
     if (D > 0) {
         if (!a->point_list || !a->binning_tmp) { set_error("point_list / binning_tmp == NULL with num_rendered=%lld", (long long)D); return OGS_ERR_INVALID_ARG; }
         if (D >= (1ll << 31)) { set_error("num_rendered=%lld exceeds 2^31", (long long)D); return OGS_ERR_UNSUPPORTED; }
@@ -314,8 +325,8 @@ static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipS
         // flagged in bit 31 of the value, and pack skips them): what ogs_raster_export_binning hands to the parity tests.
         const bool cull = a->full_binning == 0;
         const bool zero_in_dup = tiles <= (int64_t)a->P;          // one thread per range to clear
-        rc = launch_duplicate(*a, gs, gt, bt.tile_keys[0], vbuf[0], (uint32_t)D, cull, s, zero_in_dup ? is.ranges : nullptr,
-                              zero_in_dup ? (int)tiles : 0);
+        rc = launch_duplicate(*a, gs, gt, bt.tile_keys[0], vbuf[0], (uint32_t)D, cull, !per_tile, s,
+                              zero_in_dup ? is.ranges : nullptr, zero_in_dup ? (int)tiles : 0);
         if (rc != OGS_OK) return rc;
         const bool sweep = radix_onesweep_enabled(D);
         int shifts[4], nbits[4];
@@ -343,12 +354,20 @@ static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipS
         }
         rc = launch_tile_ranges(bt.tile_keys[passes & 1], D, is.ranges, tiles, s, a->debug, cull ? bt.kept : n_dev, zero_in_dup);
         if (rc != OGS_OK) return rc;
+        if (per_tile) {
+            // each tile's list (id order after the stable tile sort) into depth order; heaviest tiles first, the same workgroup
+            // order pack then uses.  Long lists pass through bt.vals, which the tile sort's last pass left free
+            const uint32_t* order = launch_tile_order(is, tiles, a->P, s, a->debug);
+            order_ready = true;
+            rc = launch_tile_depth_sort(is.ranges, tiles, order, a->point_list, gt.keys[0], bt.vals, s, a->debug);
+            if (rc != OGS_OK) return rc;
+        }
     } else {
         OGS_HIP_CHECK(hipMemsetAsync(is.ranges, 0, (size_t)tiles * sizeof(uint2), s));
     }
-    if (stats) return launch_group_stats(*a, *stats, gs, is, s);
+    if (stats) return launch_group_stats(*a, *stats, gs, is, s, order_ready);
     if (!a->sorted_rec || !a->quad_list) { set_error("sorted_rec / quad_list == NULL"); return OGS_ERR_INVALID_ARG; }
-    return launch_blend_forward(*a, gs, is, D, s);
+    return launch_blend_forward(*a, gs, is, D, s, order_ready);
 }
 
 int ogs_raster_forward_render(const OgsRasterFwdArgs* a, int64_t D, void* stream_) {
@@ -411,6 +430,10 @@ int ogs_raster_compact_kept(int32_t W, int32_t H, int32_t C, const void* image_b
 }
 
 size_t ogs_raster_tiny_max_points(void) { return (size_t)kTinyMaxP; }
+
+size_t ogs_raster_tile_sort_capacity(int32_t level) {
+    return level == 0 ? (size_t)kWaveSortCap : level == 1 ? (size_t)kTileSortCap : 0;
+}
 
 int ogs_raster_forward_tiny(const OgsRasterFwdArgs* a, void* stream_) {
     int rc = validate_fwd(a);

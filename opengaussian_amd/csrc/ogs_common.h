@@ -272,12 +272,14 @@ int radix_pass(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_
 
 struct GeomTmp {        // transient, but must survive from forward_geometry to forward_render
     uint32_t* tiles_touched;   // [P]
-    uint32_t* keys[2];         // [P] depth bits ping-pong
-    uint32_t* order[2];        // [P] Gaussian ids ping-pong; order[0] holds the depth order at the end
-    uint32_t* offsets;         // [P] exclusive scan of tiles_touched in depth order
-    uint32_t* num_rendered;    // [64] word 0: num_rendered; word 1 (`visible()`): Gaussians in the depth order -- the culled ones
-                               // (key kDropKey: behind the near plane, outside every group, empty tile rect) leave the depth
-                               // sort in its first pass, so the later passes, the scan and duplicate only see what is drawn
+    uint32_t* keys[2];         // [P] depth bits ping-pong; keys[0] by Gaussian index as preprocess wrote it on the per-tile path
+                               // (per_tile_depth_order: nothing sorts it, tile_depth_sort_kernel gathers from it)
+    uint32_t* order[2];        // [P] Gaussian ids ping-pong; order[0] holds the depth order at the end (depth-sorted paths only)
+    uint32_t* offsets;         // [P] exclusive scan of tiles_touched in the order duplicate walks (index or depth order)
+    uint32_t* num_rendered;    // [64] word 0: num_rendered; word 1 (`visible()`, depth-sorted paths only): Gaussians in the depth
+                               // order -- the culled ones (key kDropKey: behind the near plane, outside every group, empty tile
+                               // rect) leave the depth sort in its first pass, so the later passes, the scan and duplicate only
+                               // see what is drawn
     void* sort_tmp;
     uint32_t* visible() const { return num_rendered + 1; }
     static GeomTmp carve(void* p, int P) {
@@ -337,16 +339,33 @@ int launch_reblend(const OgsRasterFwdArgs& a, const ImageState& is, hipStream_t 
 int launch_compact_kept(int W, int H, int C, const ImageState& is_old, const ImageState& is_new, const void* old_rec,
                         const void* old_quad, void* new_rec, void* new_quad, hipStream_t s);
 // zero_ranges / n_zero (optional, n_zero <= P): the kernel also clears that many tile ranges (then launch_tile_ranges is told so)
+// depth_order: walk the Gaussians in the depth order of the geometry phase (order[0], visible() of them); otherwise in index
+// order, all P (per_tile_depth_order)
 int launch_duplicate(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, uint32_t* tile_keys,
-                     uint32_t* vals, uint32_t capacity, bool drop_unreachable, hipStream_t s, uint2* zero_ranges = nullptr,
-                     int n_zero = 0);
+                     uint32_t* vals, uint32_t capacity, bool drop_unreachable, bool depth_order, hipStream_t s,
+                     uint2* zero_ranges = nullptr, int n_zero = 0);
 int launch_tile_ranges(const uint32_t* tile_keys_sorted, int64_t D, uint2* ranges, int64_t tiles, hipStream_t s,
                        int debug, const uint32_t* n_dev = nullptr, bool already_zeroed = false);
+// Ungrouped streaming passes with P > kSmallMaxP bin without a global depth sort: the geometry phase scans tiles_touched in
+// Gaussian-index order, duplicate walks the Gaussians in that order, and after the tile sort every tile's list (in id order)
+// is sorted by depth on its own (launch_tile_depth_sort).  Grouped passes and the small path keep the depth order of the P
+// Gaussians.  Decided from the arguments alone, so that the geometry and the render phase of a pass agree.
+inline bool per_tile_depth_order(const OgsRasterFwdArgs& a) { return a.num_groups <= 1 && a.P > kSmallMaxP; }
+// Every tile's segment of point_list into (depth key, id) order in place, keys gathered by id from depth_keys (the 32-bit keys
+// preprocess wrote); workgroup b takes tiles tile_order[4b .. 4b+3] (b.. when NULL).  Lists up to kWaveSortCap entries are sorted by
+// one wave, up to kTileSortCap by the workgroup in LDS; longer ones run their passes through the same positions of `scratch`
+// (D entries, free after the tile sort).
+constexpr int kTileSortItems = 16;
+constexpr int kTileSortCap = kBlock * kTileSortItems;       // 4096 entries: 32 KB of keys + values, 4 workgroups per CU
+constexpr int kWaveSortCap = kTileSortCap / (kBlock / kWave);   // 1024: lists one wave sorts alone (a quarter of that space)
+int launch_tile_depth_sort(const uint2* ranges, int64_t tiles, const uint32_t* tile_order, uint32_t* point_list,
+                           const uint32_t* depth_keys, uint32_t* scratch, hipStream_t s, int debug);
 inline int num_groups_of(int g) { return g > 1 ? g : 1; }
+// order_ready: the render phase already ran launch_tile_order for this pass (per-tile depth sort), the kernels reuse it
 int launch_group_stats(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& st, const GeomState& gs, const ImageState& is,
-                       hipStream_t s);
+                       hipStream_t s, bool order_ready = false);
 int launch_blend_forward(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& is, int64_t D,
-                         hipStream_t s);
+                         hipStream_t s, bool order_ready = false);
 // The per-Gaussian gradient record is accumulated in fp64 (128 B = one L2 line): with thousands of float atomics per
 // large Gaussian, arriving in a different order every run and cancelling against each other, an fp32 running sum made
 // the gradients differ run to run by ~1e-4 of their maximum (GPUTEST_r01: rotations at S1M); the fp64 sum is

@@ -259,7 +259,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
                                             means3D, colors_precomp, shs, opacities, scales, rotations, cov3D_precomp, viewmatrix,
                                             projmatrix, campos, s_rec + tid * NV, clamped_out, radii, tiles_touched, group_ids,
                                             num_groups);
-        order[idx] = (uint32_t)idx;
+        if (order) order[idx] = (uint32_t)idx;          // the start of the global depth sort (grouped passes only)
     }
     __syncthreads();
     const size_t row0 = (size_t)blockIdx.x * kBlock;
@@ -360,9 +360,10 @@ __global__ __launch_bounds__(kSmallMaxP) void small_geometry_kernel(
     if (idx == 0) { num_rendered[0] = total; num_rendered[1] = (uint32_t)P; }     // word 1: entries of the depth order (GeomTmp::visible)
 }
 
-// Emit one (tile id, Gaussian id) pair per touched tile, Gaussians visited in DEPTH order so that a
-// stable sort by tile id alone reproduces the reference's (tile<<32 | depth_bits) order with ties
-// broken by Gaussian index (DESIGN.md "binning").
+// Emit one (tile id, Gaussian id) pair per touched tile.  Gaussians are visited in INDEX order (order == NULL: the stable
+// tile sort leaves every tile's list in id order, tile_depth_sort_kernel then sorts each list by depth) or, on the grouped and
+// small paths, in DEPTH order, so that the stable sort by tile id alone gives the final order.  Either way the result is the
+// reference's (tile<<32 | depth_bits) order with ties broken by Gaussian index (DESIGN.md "binning").
 template <int NV>
 __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint32_t* __restrict__ n_visible, int W, int H,
                                                            const float4* __restrict__ rec,
@@ -396,16 +397,17 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
     // the tile ranges start from zero (tile_ranges_kernel only writes the tiles that appear): cleared here, by a kernel that
     // runs before the sort anyway, instead of by a memset launch of its own
     if (zero_ranges != nullptr && r < n_zero) zero_ranges[r] = make_uint2(0u, 0u);
-    // the depth order holds the visible Gaussians only (capi.hip: the culled ones left the depth sort in its first pass); the
-    // launch is sized for all of them, workgroups past the count have nothing to emit
-    const int P = min(P_cap, (int)*n_visible);
+    // a depth order holds the visible Gaussians only (capi.hip: the culled ones left the depth sort in its first pass); the
+    // launch is sized for all of them, workgroups past the count have nothing to emit.  Index order (order == NULL): all P,
+    // a culled Gaussian has radius 0 and a zero offset increment, it emits nothing
+    const int P = n_visible ? min(P_cap, (int)*n_visible) : P_cap;
     if ((int)blockIdx.x * kBlock >= P) return;            // block-uniform
     const int gx = (W + kTile - 1) / kTile, gy = (H + kTile - 1) / kTile;
     uint32_t off = 0, cnt = 0, gid = 0, rect = 1u << 24, key0 = 0;
     float4 ctr = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 con = make_float4(1.f, 1.f, 0.f, 0.f);
     if (r < P) {
-        gid = order[r];
+        gid = order ? order[r] : (uint32_t)r;
         off = offsets[r];
         // culled Gaussians (radius 0) may carry any group id: they emit nothing
         if (group_ids != nullptr) key0 = (uint32_t)max(group_ids[gid], 0) * (uint32_t)(gx * gy);
@@ -508,8 +510,8 @@ int launch_preprocess_c(const OgsRasterFwdArgs& a, const GeomState& gs, const Ge
     OGS_LAUNCH_NAMED(chan_name<C>(kNames), preprocess_kernel<C>, dim3(grid), dim3(kBlock), 0, s, a.P, a.W, a.H, a.sh_degree, a.sh_coeffs,
                        a.tanfovx, a.tanfovy, focal_x, focal_y, a.scale_modifier, a.means3D, a.colors_precomp, a.shs,
                        a.opacities, a.scales, a.rotations, a.cov3D_precomp, a.viewmatrix, a.projmatrix, a.campos,
-                       gs.rec, gs.clamped, a.radii, gt.tiles_touched, gt.keys[0], gt.order[0],
-                       a.num_groups > 1 ? a.group_ids : (const int32_t*)nullptr, a.num_groups);
+                       gs.rec, gs.clamped, a.radii, gt.tiles_touched, gt.keys[0],
+                       per_tile_depth_order(a) ? (uint32_t*)nullptr : gt.order[0], a.num_groups > 1 ? a.group_ids : (const int32_t*)nullptr, a.num_groups);
     OGS_LAUNCH_CHECK(a.debug, s);
     return OGS_OK;
 }
@@ -570,7 +572,8 @@ int launch_preprocess(const OgsRasterFwdArgs& a, const GeomState& gs, const Geom
 }
 
 int launch_duplicate(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, uint32_t* tile_keys,
-                     uint32_t* vals, uint32_t capacity, bool drop_unreachable, hipStream_t s, uint2* zero_ranges, int n_zero) {
+                     uint32_t* vals, uint32_t capacity, bool drop_unreachable, bool depth_order, hipStream_t s, uint2* zero_ranges,
+                     int n_zero) {
     if (n_zero > a.P) { set_error("duplicate: %d ranges to clear with %d threads", n_zero, a.P); return OGS_ERR_INVALID_ARG; }
     const int grid = (a.P + kBlock - 1) / kBlock;
     const int32_t* grp = a.num_groups > 1 ? a.group_ids : nullptr;
@@ -578,10 +581,12 @@ int launch_duplicate(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomT
         set_error("image %dx%d exceeds 4095 tiles per side", a.W, a.H);
         return OGS_ERR_UNSUPPORTED;
     }
+    const uint32_t* order = depth_order ? gt.order[0] : nullptr;
+    const uint32_t* n_visible = depth_order ? gt.visible() : nullptr;
     switch (rec_vec4(a.C)) {
-        case 3: OGS_LAUNCH(duplicate_kernel<3>, dim3(grid), dim3(kBlock), 0, s, a.P, (const uint32_t*)gt.visible(), a.W, a.H, gs.rec, gt.order[0], gt.offsets, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
-        case 4: OGS_LAUNCH(duplicate_kernel<4>, dim3(grid), dim3(kBlock), 0, s, a.P, (const uint32_t*)gt.visible(), a.W, a.H, gs.rec, gt.order[0], gt.offsets, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
-        case 5: OGS_LAUNCH(duplicate_kernel<5>, dim3(grid), dim3(kBlock), 0, s, a.P, (const uint32_t*)gt.visible(), a.W, a.H, gs.rec, gt.order[0], gt.offsets, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
+        case 3: OGS_LAUNCH(duplicate_kernel<3>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
+        case 4: OGS_LAUNCH(duplicate_kernel<4>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
+        case 5: OGS_LAUNCH(duplicate_kernel<5>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
         default: set_error("unsupported record size"); return OGS_ERR_UNSUPPORTED;
     }
     OGS_LAUNCH_CHECK(a.debug, s);
