@@ -301,14 +301,18 @@ __global__ __launch_bounds__(kBlock) void kmeans_accum_bf16_kernel(const float* 
 // in fp32 and the sum runs in the MFMA's fp32 accumulator.  K layout (64 slots = two MFMAs; lane group g = lane >> 4
 // owns k = 8g .. 8g+7 of each): group g carries the six products of dimensions 2g and 2g+1 (12 slots) + 3 extra
 // slots: g = 0 / 1 the products of dimension 8, g = 2 the bias -|c|^2/2 (split like everything else, point side = 1).
-// Both operands are shifted by the mean of the active centres first: distances do not change, the magnitudes that
-// drive the cancellation in x.c - |c|^2/2 shrink from "distance to the origin" to "spread of the data".
+// Both operands are shifted first by the centroid of a fixed sample of the rows (kShiftRows rows at equal strides, the same
+// rows and the same summation order in every workgroup, pass and call: the shift is a function of the data alone).
+// Distances do not change, the magnitudes that drive the cancellation in x.c - |c|^2/2 shrink from "distance to the
+// origin" to "spread of the data".  (The shift used to be the mean of the active centres.  Emptied clusters sit at the
+// zero row, kmeans_quantize.py:209, and drag that mean away from data that lies off the origin: DESIGN.md section 2.)
 // Issue-rate background (profiles/r03_valu_issue_price_list.json): the direct-difference loop costs 9 SGPR-operand
 // subtractions (4 cycles each) + 9 FMAs (2) + compare/selects per point-wave and centre = ~66 cycles, 4224 per 64 x 64
 // block; this form: 32 MFMAs (16 cycles each) + ~1100 cycles of operand packing and argmax.
 // First-minimum tie rule: per lane the candidates are scanned in index order with a strict compare, lanes are merged
 // on (score, lower index).  Error of a score: ~1e-6 |x'| |c'| (fp32 accumulation over 64 terms) -- ids agree with the
 // float64 argmin except on near-ties of that size (the reference's own mm-based cdist has the same kind of error).
+constexpr int kShiftRows = 64;       // rows behind the shift (their centroid only has to lie inside the data: a few dozen rows do)
 typedef short bf16x8s __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -336,11 +340,31 @@ __device__ __forceinline__ void frag_centre(const Split3& a, const Split3& b, fl
     f1 = u32x4{pack_hi16(b.l, b.h), pack_hi16(b.m, b.h), pack_hi16(e0, e1), pack_hi16(e2, 0.f)};
 }
 
+// out[0..d) = centroid of the rows 0, step, 2 step, ... (ns = min(N, kShiftRows) rows, step = N / ns); N == 0: zero.  One workgroup;
+// scratch: ns * d floats of LDS.  The rows go through LDS with all their loads in flight at once (one thread summing them
+// straight from global memory ran kShiftRows dependent cache misses: + 7 us per pass), then one thread per column sums them in
+// row order.  The caller synchronises before it reads `out`.
+__device__ __forceinline__ void sample_centroid(const float* __restrict__ feat, int64_t N, int d, float* scratch, float* out) {
+    const int tid = threadIdx.x;
+    const int ns = (int)min(N, (int64_t)kShiftRows);
+    const int64_t step = ns > 0 ? N / ns : 0;
+    for (int e = tid; e < ns * d; e += blockDim.x) {
+        const int i = e / d;
+        scratch[e] = feat[i * step * d + (e - i * d)];
+    }
+    __syncthreads();
+    if (tid < d) {
+        float m = 0.f;
+        for (int i = 0; i < ns; ++i) m += scratch[i * d + tid];
+        out[tid] = ns > 0 ? m / (float)ns : 0.f;
+    }
+}
+
 template <int CB, bool ACCUM, int DT>
 __global__ __launch_bounds__(kBlock) void kmeans_gemm_pass_kernel(const float* __restrict__ feat, int64_t N,
                                                                   const float* __restrict__ centers, int k, int k_active,
                                                                   int64_t* __restrict__ ids_out, int64_t id_offset,
-                                                                  float* __restrict__ partials) {
+                                                                  float* __restrict__ partials, const float* __restrict__ shift) {
     static_assert(DT == 6 || DT == 9, "the K layout covers the reference's two codebook widths");
     constexpr int d = DT;
     extern __shared__ float smem[];
@@ -351,15 +375,17 @@ __global__ __launch_bounds__(kBlock) void kmeans_gemm_pass_kernel(const float* _
     const int g = lane >> 4, j = lane & 15;
     const int da = 2 * g, db = 2 * g + 1;                          // this lane group's two dimensions (>= d: unused, zero)
     const bool has8 = d == 9 && g < 2;
-    // shifted centres c' = c - mean(active centres) and their -|c'|^2 / 2, once per workgroup, through LDS (the rows region
-    // is free until the first trip): cs[c * d + jj] = c'_jj, nb[c] = -|c'|^2 / 2, mu[jj]
+    // shifted centres c' = c - mu (mu: centroid of the sampled rows) and their -|c'|^2 / 2, once per workgroup, through LDS
+    // (the rows region is free until the first trip): cs[c * d + jj] = c'_jj, nb[c] = -|c'|^2 / 2, mu[jj]
     float* cs = rows;
     float* nb = cs + k * d;
     float* mu = nb + k;
-    if (tid < d) {
-        float m = 0.f;
-        for (int c = 0; c < k_active; ++c) m += centers[c * d + tid];
-        mu[tid] = m / (float)k_active;
+    // mu: handed in by the caller (ogs_kmeans_lloyd computes it once per call, in its first launch) or, without one, computed
+    // here -- the same rows summed in the same order, so the same bits either way
+    if (shift) {
+        if (tid < d) mu[tid] = shift[tid];
+    } else {
+        sample_centroid(feat, N, d, mu + d, mu);                   // scratch behind the setup region
     }
     __syncthreads();
     for (int i = tid; i < k * d; i += kBlock) cs[i] = centers[i] - mu[i % d];
@@ -555,6 +581,9 @@ __global__ __launch_bounds__(kBlock) void kmeans_gemm_pass_kernel(const float* _
 }
 
 // ---- fallback for shapes outside the MFMA tiling: per-workgroup LDS accumulators ---------------------------------
+// The accumulate of this kernel uses LDS float atomics: the order in which the rows of a 256-row block reach a table
+// entry is NOT fixed, so its sums (and the centres) can differ in the last bits from run to run.  The fixed summation
+// order of the header holds for the three MFMA kernels only; this one is held to the oracle's tolerances.
 template <bool ACCUM>
 __global__ __launch_bounds__(kBlock) void kmeans_lds_pass_kernel(const float* __restrict__ feat, int64_t N, int d,
                                                                  const float* __restrict__ centers, int k, int k_active,
@@ -725,10 +754,14 @@ __global__ __launch_bounds__(kBlock) void kmeans_reduce_finalize_kernel(const fl
     }
 }
 
-// p[0..n) = v, p[n] = 0 (the reduce kernel's ticket word sits right behind the counts)
-__global__ __launch_bounds__(kBlock) void fill_kernel(float* p, int n, float v) {
+// p[0..n) = v, p[n] = 0 (the reduce kernel's ticket word sits right behind the counts); workgroup 0 also leaves the shift of
+// the GEMM pass (sample_centroid) in shift[0..d), once per Lloyd call instead of once per workgroup and pass
+__global__ __launch_bounds__(kBlock) void fill_kernel(float* p, int n, float v, const float* __restrict__ feat, int64_t N, int d,
+                                                      float* __restrict__ shift) {
+    __shared__ float scratch[kShiftRows * kMaxD];
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i <= n) p[i] = i < n ? v : 0.f;
+    if (blockIdx.x == 0) sample_centroid(feat, N, d, scratch, shift);
 }
 
 __global__ __launch_bounds__(kBlock) void kmeans_gather_kernel(const float* __restrict__ centers,
@@ -770,7 +803,10 @@ size_t fallback_lds(int d, int k, bool accum) {
     return sizeof(float) * ((size_t)k * d + (size_t)kBlock * d + (accum ? (size_t)k * (d + 1) : 0));
 }
 
-// dynamic LDS above the 64 KiB default needs an explicit opt-in (gfx950 has 160 KiB per CU)
+// HIP documents an explicit opt-in for dynamic LDS above 48 KiB (gfx950 has 160 KiB per CU).  DEFENSIVE: the runtime this was
+// developed on launches the largest table of this file (64 KiB at k (d + 1) = OGS_KMEANS_MAX_ACC, + 4 B static) without it,
+// so no test can observe these calls -- tests/test_21_kmeans_edges_gpu.py reaches both finalize kernels at that size and
+// passes with the call removed.  Kept for runtimes that enforce the documented rule.
 template <typename K>
 int allow_lds(K kernel, size_t bytes) {
     if (bytes > 160 * 1024) { set_error("kmeans: %zu bytes of LDS requested (> 160 KiB)", bytes); return OGS_ERR_UNSUPPORTED; }
@@ -781,9 +817,9 @@ int allow_lds(K kernel, size_t bytes) {
 
 template <int CB, bool ACCUM, int DT>
 int launch_mfma_d(int nb, hipStream_t s, const float* feat, int64_t N, int d, const float* centers, int k, int k_active,
-                  int64_t* ids_out, int64_t id_offset, float* partials) {
+                  int64_t* ids_out, int64_t id_offset, float* partials, const float* shift = nullptr) {
     if constexpr ((DT == 6 || DT == 9) && CB <= 4) {
-        const size_t setup = (size_t)k * DT + k + DT;                      // shifted centres, biases, mean (before the first trip)
+        const size_t setup = (size_t)k * DT + k + DT + (size_t)kShiftRows * DT;   // shifted centres, biases, mean, sampled rows (before the first trip)
         size_t body = (size_t)kBlock * DT + kBlock;
         const size_t wtab = ACCUM ? (size_t)4 * CB * 16 * 16 : 0;
         body = body > wtab ? body : wtab;
@@ -792,7 +828,7 @@ int launch_mfma_d(int nb, hipStream_t s, const float* feat, int64_t N, int d, co
         if (rc != OGS_OK) return rc;
         OGS_LAUNCH_NAMED(ACCUM ? "kmeans_gemm_pass_kernel<accum>" : "kmeans_gemm_pass_kernel<assign>",
                          (kmeans_gemm_pass_kernel<CB, ACCUM, DT>), dim3(nb), dim3(kBlock), lds, s, feat, N, centers, k,
-                         k_active, ids_out, id_offset, partials);
+                         k_active, ids_out, id_offset, partials, shift);
     } else if constexpr (DT > 0 && ACCUM) {
         const size_t rows = (size_t)2 * kBlock * DT + 2 * kBlock, wtab = (size_t)4 * CB * 16 * 16;
         const size_t lds = sizeof(float) * (rows > wtab ? rows : wtab);
@@ -814,11 +850,11 @@ int launch_mfma_d(int nb, hipStream_t s, const float* feat, int64_t N, int d, co
 
 template <int CB, bool ACCUM>
 int launch_mfma(int nb, hipStream_t s, const float* feat, int64_t N, int d, const float* centers, int k, int k_active,
-                int64_t* ids_out, int64_t id_offset, float* partials) {
+                int64_t* ids_out, int64_t id_offset, float* partials, const float* shift = nullptr) {
     switch (d) {
-        case 6: return launch_mfma_d<CB, ACCUM, 6>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials);
-        case 9: return launch_mfma_d<CB, ACCUM, 9>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials);
-        default: return launch_mfma_d<CB, ACCUM, 0>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials);
+        case 6: return launch_mfma_d<CB, ACCUM, 6>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials, shift);
+        case 9: return launch_mfma_d<CB, ACCUM, 9>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials, shift);
+        default: return launch_mfma_d<CB, ACCUM, 0>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials, shift);
     }
 }
 
@@ -831,11 +867,11 @@ int launch_mfma(int nb, hipStream_t s, const float* feat, int64_t N, int d, cons
 //   k > 256 or d = 16           kmeans_lds_pass_kernel               kmeans_lds_pass_kernel
 template <bool ACCUM>
 int launch_pass(int nb, hipStream_t s, const float* feat, int64_t N, int d, const float* centers, int k, int k_active,
-                int64_t* ids_out, int64_t id_offset, float* partials) {
+                int64_t* ids_out, int64_t id_offset, float* partials, const float* shift = nullptr) {
     switch (cluster_blocks(d, k)) {
-        case 1: return launch_mfma<1, ACCUM>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials);
-        case 4: return launch_mfma<4, ACCUM>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials);
-        case 16: return launch_mfma<16, ACCUM>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials);
+        case 1: return launch_mfma<1, ACCUM>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials, shift);
+        case 4: return launch_mfma<4, ACCUM>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials, shift);
+        case 16: return launch_mfma<16, ACCUM>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, partials, shift);
         default: break;
     }
     const size_t lds = fallback_lds(d, k, ACCUM);
@@ -856,7 +892,7 @@ extern "C" {
 
 size_t ogs_kmeans_tmp_bytes(int64_t N, int32_t d, int32_t k) {
     return align_up((size_t)pass_blocks(N) * k * (d + 1) * sizeof(float)) + align_up((size_t)(k + 1) * sizeof(float)) +
-           align_up((size_t)kSlices * k * (d + 1) * sizeof(float));
+           align_up((size_t)kSlices * k * (d + 1) * sizeof(float)) + align_up((size_t)kMaxD * sizeof(float));
 }
 
 int ogs_kmeans_assign(const float* feat, int64_t N, int32_t d, const float* centers, int32_t k, int64_t* ids_out,
@@ -885,20 +921,21 @@ int ogs_kmeans_lloyd(const float* feat, int64_t N, int32_t d, float* centers, in
     float* slices = reinterpret_cast<float*>(reinterpret_cast<char*>(counts) + align_up((size_t)(k + 1) * sizeof(float)));
     unsigned int* ticket = reinterpret_cast<unsigned int*>(counts + k);          // zeroed here, reset by each last arriver
     const int stride = k * (d + 1);
-    OGS_LAUNCH(fill_kernel, dim3((k + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, counts, k, 1e-6f);   // counts + ticket = 0
+    float* shift = reinterpret_cast<float*>(reinterpret_cast<char*>(slices) + align_up((size_t)kSlices * stride * sizeof(float)));   // [d], the last region of tmp
+    OGS_LAUNCH(fill_kernel, dim3((k + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, counts, k, 1e-6f, feat, N, (int)d, shift);   // counts + ticket = 0
     OGS_LAUNCH_CHECK(0, s);
     const size_t fin_lds = (size_t)k * (d + 1) * sizeof(float);
     rc = allow_lds(kmeans_reduce_finalize_kernel, fin_lds);
     if (rc != OGS_OK) return rc;
     for (int it = 0; it < iters; ++it) {
-        rc = launch_pass<true>(nb, s, feat, N, d, centers, k, k_active, nullptr, 0, partials);
+        rc = launch_pass<true>(nb, s, feat, N, d, centers, k, k_active, nullptr, 0, partials, shift);
         if (rc != OGS_OK) return rc;
         OGS_LAUNCH(kmeans_reduce_finalize_kernel, dim3((stride + kBlock - 1) / kBlock, kSlices), dim3(kBlock), fin_lds, s,
                    (const float*)partials, nb, k, d, slices, (float)nchunks * 1e-6f, counts, centers, ticket);
         OGS_LAUNCH_CHECK(0, s);
     }
     if (N > 0) {
-        rc = launch_pass<false>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, nullptr);
+        rc = launch_pass<false>(nb, s, feat, N, d, centers, k, k_active, ids_out, id_offset, nullptr, shift);
         if (rc != OGS_OK) return rc;
     }
     return OGS_OK;

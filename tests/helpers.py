@@ -3,6 +3,7 @@ the CPU oracle on identical inputs."""
 from __future__ import annotations
 
 import ctypes as C
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -437,6 +438,39 @@ KM_TIE = 1e-5          # ids exact except rows whose bes
 KM_CENTER_TOL = 1e-4   # north_star tolerance on centres
 
 
+KM_CHUNK_ELEMS = 1 << 22   # float64 elements of one [rows, k, d] difference block (32 MiB); the row chunk follows from it
+
+
+def _km_row_distances(X, C, id_sets):
+    """float64 Euclidean distances of every row of X to every centre of C, evaluated in row chunks so that memory does not
+    grow with N * k * d: returns (row minimum [N], first argmin [N], [distance of row r to centre ids[r]] per entry of
+    id_sets).  Every row's numbers are those of the one-block evaluation (the reduction runs over a row's own k x d block).
+    The chunks run on a small thread pool for wall time only (N = 600 077, k = 256, d = 15 is 2.3 G differences): each
+    writes its own rows, the result does not depend on the schedule; peak memory is 8 blocks of KM_CHUNK_ELEMS + temporaries."""
+    n = len(X)
+    dmin, amin = np.empty(n, np.float64), np.empty(n, np.int64)
+    chosen = [np.empty(n, np.float64) for _ in id_sets]
+    step = max(1, KM_CHUNK_ELEMS // max(C.size, 1))
+
+    def chunk(lo):
+        hi = min(n, lo + step)
+        d = np.sqrt(((X[lo:hi, None, :] - C[None, :, :]) ** 2).sum(-1))
+        dmin[lo:hi], amin[lo:hi] = d.min(1), d.argmin(1)
+        r = np.arange(hi - lo)
+        for out, ids in zip(chosen, id_sets):
+            out[lo:hi] = d[r, ids[lo:hi]]
+
+    with ThreadPoolExecutor(max_workers=8) as ex:        # NumPy releases the GIL in these loops; chunks write disjoint rows
+        list(ex.map(chunk, range(0, n, step)))
+    return dmin, amin, chosen
+
+
+def assert_kmeans_centers_close(got, want, k_note=""):
+    """EVERY centre row within KM_CENTER_TOL of the reference's (no fraction of rows is exempt)."""
+    diff = np.abs(np.asarray(got, np.float64) - np.asarray(want, np.float64)).max(axis=1)
+    assert diff.max() <= KM_CENTER_TOL, f"{int((diff > KM_CENTER_TOL).sum())} centre rows differ by > {KM_CENTER_TOL} {k_note}: {diff.max()}"
+
+
 def kmeans_step_attribution(feat, c_prev, c_next_ref, ids_prev_ref, ids_prev_got, c_next_got, what="", c_prev_got=None):
     """ONE Lloyd iteration, the reference's (from its centres ``c_prev``) against the one under test (from
     ``c_prev_got``; default: the same centres, so that a near-tie flip cannot cascade):
@@ -456,23 +490,27 @@ def kmeans_step_attribution(feat, c_prev, c_next_ref, ids_prev_ref, ids_prev_got
     C = np.asarray(c_prev, np.float64)
     Cg = C if c_prev_got is None else np.asarray(c_prev_got, np.float64)
     delta = float(np.abs(Cg - C).max())
-    dist = lambda cc: np.sqrt(((X[:, None, :] - cc[None, :, :]) ** 2).sum(-1))
-    d_ref = dist(C)
-    d_got = d_ref if c_prev_got is None else dist(Cg)
-    rows = np.arange(len(X))
-    for name, ids, d in (("under test", ids_prev_got, d_got), ("reference", ids_prev_ref, d_ref)):
-        if ids is None:
+    got = np.asarray(ids_prev_got, np.int64)
+    ref_given = None if ids_prev_ref is None else np.asarray(ids_prev_ref, np.int64)
+    # distances under the reference's centres: row minimum, first argmin, distance to each side's chosen centre
+    min_ref, arg_ref, chosen_ref = _km_row_distances(X, C, [got] + ([] if ref_given is None else [ref_given]))
+    if c_prev_got is None:
+        min_got, got_under_got = min_ref, chosen_ref[0]
+    else:
+        min_got, _, (got_under_got,) = _km_row_distances(X, Cg, [got])
+    for name, chosen, dmin in (("under test", got_under_got, min_got),
+                               ("reference", None if ref_given is None else chosen_ref[1], min_ref)):
+        if chosen is None:
             continue
-        ids = np.asarray(ids, np.int64)
-        excess = d[rows, ids] - d.min(1)
+        excess = chosen - dmin
         assert (excess < KM_TIE).all(), (f"{what}: {name} ids are not the f64 nearest centre on rows that are NOT near ties: "
                                          f"rows {np.nonzero(excess >= KM_TIE)[0][:5]} excess {excess.max()}")
-    got = np.asarray(ids_prev_got, np.int64)
-    ref = d_ref.argmin(1) if ids_prev_ref is None else np.asarray(ids_prev_ref, np.int64)
+    ref = arg_ref if ref_given is None else ref_given
+    ref_under_ref = min_ref if ref_given is None else chosen_ref[1]
     k = C.shape[0]
     cg, cr = np.asarray(c_next_got, np.float64), np.asarray(c_next_ref, np.float64)
     flipped = np.nonzero(got != ref)[0]
-    gap = np.abs(d_ref[flipped, got[flipped]] - d_ref[flipped, ref[flipped]])
+    gap = np.abs(chosen_ref[0][flipped] - ref_under_ref[flipped])
     assert (gap < 2 * KM_TIE + 2 * delta).all(), (f"{what}: ids differ on rows whose candidate centres are NOT within "
                                                   f"2*{KM_TIE} + 2*{delta:.2e}: rows {flipped[gap >= 2 * KM_TIE + 2 * delta][:5]}")
     for j in range(k):

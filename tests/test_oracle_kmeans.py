@@ -106,3 +106,113 @@ def test_chunk_boundary_extra_trip():
     c2, i2 = ko.lloyd(feat, feat[:8], iters=2, nchunks=1)
     assert np.array_equal(i1, i2)
     np.testing.assert_allclose(c1, c2, atol=1e-6)
+
+
+def _step_attribution_one_block(feat, c_prev, c_next_ref, ids_prev_ref, ids_prev_got, c_next_got, what="", c_prev_got=None):
+    """helpers.kmeans_step_attribution as it stood before its distances were chunked over rows (one [N, k, d] float64
+    block): kept here as the pin of the chunked form."""
+    from tests.helpers import KM_CENTER_TOL, KM_TIE
+    X = np.asarray(feat, np.float64)
+    C = np.asarray(c_prev, np.float64)
+    Cg = C if c_prev_got is None else np.asarray(c_prev_got, np.float64)
+    delta = float(np.abs(Cg - C).max())
+    dist = lambda cc: np.sqrt(((X[:, None, :] - cc[None, :, :]) ** 2).sum(-1))
+    d_ref = dist(C)
+    d_got = d_ref if c_prev_got is None else dist(Cg)
+    rows = np.arange(len(X))
+    for ids, d in ((ids_prev_got, d_got), (ids_prev_ref, d_ref)):
+        if ids is None:
+            continue
+        ids = np.asarray(ids, np.int64)
+        assert (d[rows, ids] - d.min(1) < KM_TIE).all(), f"{what}: ids are not the f64 nearest centre"
+    got = np.asarray(ids_prev_got, np.int64)
+    ref = d_ref.argmin(1) if ids_prev_ref is None else np.asarray(ids_prev_ref, np.int64)
+    cg, cr = np.asarray(c_next_got, np.float64), np.asarray(c_next_ref, np.float64)
+    flipped = np.nonzero(got != ref)[0]
+    gap = np.abs(d_ref[flipped, got[flipped]] - d_ref[flipped, ref[flipped]])
+    assert (gap < 2 * KM_TIE + 2 * delta).all(), f"{what}: ids differ on rows that are not near ties"
+    for j in range(C.shape[0]):
+        members = got == j
+        n = int(members.sum())
+        if n:
+            assert np.abs(cg[j] - X[members].mean(0)).max() < 2e-5, f"{what}: centre {j} is not the mean of its members"
+        else:
+            assert np.abs(cg[j]).max() < 1e-5, f"{what}: empty cluster {j} must collapse to ~0"
+        touching = flipped[(got[flipped] == j) | (ref[flipped] == j)]
+        allowed = KM_CENTER_TOL + sum(np.abs(X[r] - cr[j]).max() for r in touching) / max(min(n, int((ref == j).sum())), 1)
+        assert np.abs(cg[j] - cr[j]).max() <= allowed, f"{what}: centre {j} off"
+    return len(flipped), float(np.abs(cg - cr).max())
+
+
+def _planted_near_tie_case():
+    """N = 3000 rows, k = 12 centres, one oracle iteration -- and row 0 moved ONTO the bisector of its two nearest centres
+    (then 4e-6 to the far side), so that both forms have a flipped row inside the tie width to attribute."""
+    rng = np.random.default_rng(5)
+    X = rng.random((3000, 6)).astype(np.float32)
+    C = X[rng.permutation(3000)[:12]].copy()
+    d = np.sqrt(((X[0].astype(np.float64) - C.astype(np.float64)) ** 2).sum(-1))
+    a, b = np.argsort(d)[:2]
+    ca, cb = C[a].astype(np.float64), C[b].astype(np.float64)
+    u = (cb - ca) / np.linalg.norm(cb - ca)
+    x = X[0].astype(np.float64)
+    x = x + (np.dot((ca + cb) / 2 - x, u) + 2e-6) * u           # 2e-6 past the bisector: b is nearer by ~4e-6 < KM_TIE
+    X[0] = x.astype(np.float32)
+    ids = ko._argmin_sqdist(X, C)
+    c_next, _ = ko.lloyd(X, C, iters=1)
+    return X, C, ids, c_next, int(a), int(b)
+
+
+def test_chunked_step_attribution_equals_the_one_block_form(monkeypatch):
+    """tests/helpers.py::kmeans_step_attribution evaluates its float64 distances in row chunks.  On N = 3000 it returns what
+    the one-block form returns -- with several chunks, one chunk, own previous centres and a given reference trajectory --
+    and raises on the same planted errors: one row moved across a gap > KM_TIE, one centre off by 1e-3."""
+    from tests import helpers
+    X, C, ids, c_next, a, b = _planted_near_tie_case()
+    flip = ids.copy()
+    flip[0] = a if ids[0] == b else b                            # the other side of a < KM_TIE tie: attributed, not an error
+    member = lambda idv: np.stack([X[idv == j].astype(np.float64).mean(0) for j in range(len(C))])
+    Cg = (C.astype(np.float64) + 1e-6).astype(np.float32)
+    ids_g = ko._argmin_sqdist(X, Cg)
+    variants = [
+        dict(ids_prev_ref=None, ids_prev_got=ids, c_next_got=c_next),
+        dict(ids_prev_ref=ids, ids_prev_got=flip, c_next_got=member(flip)),
+        dict(ids_prev_ref=flip, ids_prev_got=ids, c_next_got=c_next),
+        dict(ids_prev_ref=ids, ids_prev_got=ids_g, c_next_got=member(ids_g), c_prev_got=Cg),
+    ]
+    for elems in (1 << 22, 500 * C.size, 7 * C.size):            # one chunk, six chunks, 429 chunks
+        monkeypatch.setattr(helpers, "KM_CHUNK_ELEMS", elems)
+        for kw in variants:
+            want = _step_attribution_one_block(X, C, c_next, **kw)
+            assert helpers.kmeans_step_attribution(X, C, c_next, **kw) == want
+        assert helpers.kmeans_step_attribution(X, C, c_next, **variants[1])[0] == 1        # the planted flip was seen
+        # planted error 1: a row given to a centre that is farther than its nearest by more than KM_TIE
+        wrong = ids.copy()
+        r = 1234
+        dr = np.sqrt(((X[r].astype(np.float64) - C.astype(np.float64)) ** 2).sum(-1))
+        wrong[r] = int(np.argsort(dr)[1])
+        assert np.sort(dr)[1] - np.sort(dr)[0] > helpers.KM_TIE
+        # planted error 2: one centre coordinate off by 1e-3
+        c_bad = c_next.copy()
+        c_bad[5, 2] += np.float32(1e-3)
+        for fn in (helpers.kmeans_step_attribution, _step_attribution_one_block):
+            with pytest.raises(AssertionError):
+                fn(X, C, c_next, None, wrong, member(wrong))
+            with pytest.raises(AssertionError):
+                fn(X, C, c_next, ids, ids, c_bad)
+
+
+def test_final_ids_attribution_raises_on_planted_errors():
+    """kmeans_final_ids_attribution needs no chunking (it touches the differing rows only); pinned all the same: a flip inside
+    the tie width is counted, a row moved across a gap > KM_TIE raises."""
+    from tests import helpers
+    X, C, ids, _, a, b = _planted_near_tie_case()
+    flip = ids.copy()
+    flip[0] = a if ids[0] == b else b
+    assert helpers.kmeans_final_ids_attribution(X, C, ids, C, ids) == 0
+    assert helpers.kmeans_final_ids_attribution(X, C, ids, C, flip) == 1
+    wrong = ids.copy()
+    dr = np.sqrt(((X[77].astype(np.float64) - C.astype(np.float64)) ** 2).sum(-1))
+    wrong[77] = int(np.argsort(dr)[1])
+    assert np.sort(dr)[1] - np.sort(dr)[0] > helpers.KM_TIE
+    with pytest.raises(AssertionError):
+        helpers.kmeans_final_ids_attribution(X, C, ids, C, wrong)
