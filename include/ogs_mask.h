@@ -58,6 +58,21 @@ int ogs_mask_cohesion(const float* feat, const uint8_t* masks, const float* mean
 int ogs_mask_cohesion_backward(const float* feat, const uint8_t* masks, const float* mean, const float* gl, int32_t C,
                                int32_t N, int64_t HW, float* dfeat, float* dmean, void* stream);
 
+/* Label form of the four calls above, for DISJOINT masks (the masks of one SAM level are the one-hot of one id image,
+ * utils/opengs_utlis.py:134-149): `labels` is one int32 per pixel ([HW]) in place of the [N,HW] byte stack.  Pixel p
+ * lies in mask row labels[p] - 1 when 1 <= labels[p] <= N and in no row otherwise (0 = invalid pixel, negative values,
+ * values above N); an out-of-range label is never used as an address.  Every kernel reads 4 bytes per pixel of masks
+ * whatever N is.  Results, table layout, zeroing, C / with_squares rules and error codes are those of the dense twin. */
+int ogs_label_feature_sums(const float* feat, const int32_t* labels, const float* weight, int32_t C, int32_t N,
+                           int64_t HW, int32_t with_squares, float* table, void* stream);
+int ogs_label_feature_sums_backward(const int32_t* labels, const float* weight, const float* coef, const float* feat,
+                                    const float* coef_cnt, int32_t C, int32_t N, int64_t HW, float* dfeat,
+                                    float* dweight, void* stream);
+int ogs_label_cohesion(const float* feat, const int32_t* labels, const float* mean, int32_t C, int32_t N, int64_t HW,
+                       float* table, void* stream);
+int ogs_label_cohesion_backward(const float* feat, const int32_t* labels, const float* mean, const float* gl, int32_t C,
+                                int32_t N, int64_t HW, float* dfeat, float* dmean, void* stream);
+
 /* separation_loss (train.py:124-155), forward AND gradient in two small launches: means [N, C] (2 <= N <= 1024 masks,
  * C <= 16), late != 0 for iteration > 35 000 (weights below 0.9 become 0.1).  loss[0] = sum_ij inv_ij * w_ij / (N (N-1))
  * with inv_ij = 1 / (|m_i - m_j|^2 + 1), 0 on the diagonal, and w_ij = rank of inv_ij inside row i (ties by column, i.e.

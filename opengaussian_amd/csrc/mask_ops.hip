@@ -6,7 +6,8 @@
 // and the mask stack is walked with one u32 per lane and mask.  A mask with no pixel in the strip costs one
 // ballot; a mask that is present contributes its partial sums through the 16-slot transposed wave fold
 // (wave_fold.h) and ONE float-atomic instruction on a contiguous table row.  HBM-bound: feat + weight once,
-// N bytes per pixel of masks.
+// N bytes per pixel of masks.  The label_* kernels are the same passes over ONE int32 label image (disjoint masks):
+// 4 bytes per pixel of masks whatever N is, and a loop over the distinct labels of the strip in place of the stack walk.
 #include "ogs_common.h"
 #include "wave_fold.h"
 #include "../../include/ogs_mask.h"
@@ -254,6 +255,252 @@ __global__ __launch_bounds__(kBlock) void mask_cohesion_backward_kernel(const fl
     for (int c = 0; c < C; ++c) store4<VEC>(dfeat + (size_t)c * HW, i0, HW, acc[c]);
 }
 
+// ---- label form: ONE int32 label image instead of the [N,H,W] byte stack (the masks of one SAM level are disjoint) ----
+// Pixel p lies in row labels[p] - 1 when 1 <= labels[p] <= N and in no row otherwise (0 = invalid, negative, > N): the
+// same kernels as above with 4 bytes per pixel of masks whatever N is.  row[j] = that row, or -1; only a row that
+// passed the range test is ever used as an address.
+
+// load4 with the bounds test moved from the load to the address: past the end a lane re-reads element 0 (n > 0 in every
+// launch) and zeroes the result, so nothing branches around a load and the C + 2 loads of a lane are all in flight at
+// once.  (The label kernels move so few bytes that a whole 1080p launch is ONE round of resident waves: a chain of
+// load -> wait -> load would be its run time.)
+template <bool VEC, typename T>
+__device__ __forceinline__ void load4_clamped(const T* __restrict__ p, int64_t i0, int64_t n, T out[kPix]) {
+    if (VEC) {
+        typedef T vec4 __attribute__((ext_vector_type(4)));
+        const bool ok = i0 < n;
+        const vec4 v = *reinterpret_cast<const vec4*>(p + (ok ? i0 : 0));
+        out[0] = ok ? v.x : T(0); out[1] = ok ? v.y : T(0); out[2] = ok ? v.z : T(0); out[3] = ok ? v.w : T(0);
+    } else {
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) {
+            const bool ok = i0 + j < n;
+            const T v = p[ok ? i0 + j : 0];
+            out[j] = ok ? v : T(0);
+        }
+    }
+}
+
+__device__ __forceinline__ int label_row(int l, int N) {
+    const uint32_t r = (uint32_t)l - 1u;                  // unsigned: no label value can overflow
+    return (r < (uint32_t)N) ? (int)r : -1;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void load_rows(const int32_t* __restrict__ labels, int64_t i0, int64_t n, int N, int row[kPix]) {
+    int l[kPix];
+    load4_clamped<VEC>(labels, i0, n, l);
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) row[j] = label_row(l[j], N);
+}
+
+// `body(n, hit)` runs (wave-uniformly) once for every distinct row n present in the wave's strip; bit j of `hit` is set
+// where this lane's pixel j lies in row n.  Each lane keeps a 4-bit set of its pixels still pending; a trip takes the
+// first pending row of the first pending lane and every lane retires all of its pixels in that row, so a trip retires
+// at least one pixel and the loop ends after at most 256 trips whatever the labels hold.
+template <typename F>
+__device__ __forceinline__ void for_each_present_row(const int row[kPix], F&& body) {
+    uint32_t pending = 0u;
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) pending |= (row[j] >= 0 ? 1u : 0u) << j;
+    for (;;) {
+        const unsigned long long live = __ballot(pending != 0u);
+        if (live == 0ull) break;
+        const int src = __ffsll(live) - 1;
+        const int first = (pending & 1u) ? row[0] : (pending & 2u) ? row[1] : (pending & 4u) ? row[2] : row[3];
+        const int n = __builtin_amdgcn_readlane(first, src);          // wave-uniform: row reads go the scalar way
+        uint32_t hit = 0u;
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) hit |= (row[j] == n ? 1u : 0u) << j;
+        pending &= ~hit;
+        body(n, hit);
+    }
+}
+
+template <int C, bool SQ, bool VEC>
+__global__ __launch_bounds__(kBlock) void label_feature_sums_kernel(const float* __restrict__ feat,
+                                                                    const int32_t* __restrict__ labels,
+                                                                    const float* __restrict__ weight, int N, int64_t HW,
+                                                                    float* __restrict__ table) {
+    constexpr int WIDTH = SQ ? 2 * C + 1 : C + 1;
+    static_assert(WIDTH <= 16, "table row must fit the 16-slot fold");
+    const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPix;
+    float f[C][kPix], w[kPix];
+    int row[kPix];
+#pragma unroll
+    for (int c = 0; c < C; ++c) load4_clamped<VEC>(feat + (size_t)c * HW, i0, HW, f[c]);
+    if (weight) load4_clamped<VEC>(weight, i0, HW, w);
+    else {
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) w[j] = 1.f;
+    }
+    load_rows<VEC>(labels, i0, HW, N, row);
+    const int lane = lane_id();
+    for_each_present_row(row, [&](int n, uint32_t hit) {
+        float v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = 0.f;
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) {
+            const float wj = ((hit >> j) & 1u) ? w[j] : 0.f;
+            v[C] += wj;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float t = wj * f[c][j];
+                v[c] += t;
+                if (SQ) v[C + 1 + c] += t * f[c][j];
+            }
+        }
+        const float y = wave_fold16(v);
+        const int slot = lane >> 2;
+        if ((lane & 3) == 0 && slot < WIDTH) atomicAdd(table + (size_t)n * kRow + slot, y);
+    });
+}
+
+// Per pixel, no loop: dfeat[c,pix] = w[pix] * coef[row,c], dweight[pix] = sum_c coef[row,c] * feat[c,pix] + coef_cnt[row],
+// a gather by the pixel's own row (neighbouring lanes mostly share it); zeros where the pixel lies in no row.
+template <int C, bool VEC, bool DW>
+__global__ __launch_bounds__(kBlock) void label_feature_sums_backward_kernel(const int32_t* __restrict__ labels,
+                                                                             const float* __restrict__ weight,
+                                                                             const float* __restrict__ coef,
+                                                                             const float* __restrict__ feat,
+                                                                             const float* __restrict__ coef_cnt, int N,
+                                                                             int64_t HW, float* __restrict__ dfeat,
+                                                                             float* __restrict__ dweight) {
+    const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPix;
+    float acc[C][kPix], w[kPix], dw[kPix];
+    int row[kPix];
+    load_rows<VEC>(labels, i0, HW, N, row);
+    if (weight) load4_clamped<VEC>(weight, i0, HW, w);
+    else {
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) w[j] = 1.f;
+    }
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) {
+        const bool in = row[j] >= 0;
+        const size_t r = in ? (size_t)row[j] : 0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float v = coef[r * C + c];            // row 0 where the pixel has none (N > 0): loaded, not used
+            acc[c][j] = in ? v : 0.f;
+        }
+        if (DW) {
+            const float v = coef_cnt[r];
+            dw[j] = in ? v : 0.f;
+        }
+    }
+    if (DW) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            float f[kPix];
+            load4_clamped<VEC>(feat + (size_t)c * HW, i0, HW, f);
+#pragma unroll
+            for (int j = 0; j < kPix; ++j) dw[j] += f[j] * acc[c][j];
+        }
+        store4<VEC>(dweight, i0, HW, dw);
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) acc[c][j] *= w[j];
+        store4<VEC>(dfeat + (size_t)c * HW, i0, HW, acc[c]);
+    }
+}
+
+template <int C, bool VEC>
+__global__ __launch_bounds__(kBlock) void label_cohesion_kernel(const float* __restrict__ feat,
+                                                                const int32_t* __restrict__ labels,
+                                                                const float* __restrict__ mean, int N, int64_t HW,
+                                                                float* __restrict__ table) {
+    const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPix;
+    float f[C][kPix];
+    int row[kPix];
+#pragma unroll
+    for (int c = 0; c < C; ++c) load4_clamped<VEC>(feat + (size_t)c * HW, i0, HW, f[c]);
+    load_rows<VEC>(labels, i0, HW, N, row);
+    const int lane = lane_id();
+    for_each_present_row(row, [&](int n, uint32_t hit) {
+        float mu[C];                                   // wave-uniform row -> scalar loads
+#pragma unroll
+        for (int c = 0; c < C; ++c) mu[c] = mean[(size_t)n * C + c];
+        float v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = 0.f;
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) {
+            float d2 = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float d = f[c][j] - mu[c];
+                d2 += d * d;
+            }
+            const bool in = (hit >> j) & 1u;
+            v[0] += in ? sqrtf(d2) : 0.f;
+            v[1] += in ? 1.f : 0.f;
+        }
+        const float y = wave_fold16(v);
+        const int slot = lane >> 2;
+        if ((lane & 3) == 0 && slot < 2) atomicAdd(table + (size_t)n * kRow + slot, y);
+    });
+}
+
+// dfeat is per pixel (mean and gl gathered by the pixel's own row, written in place of the feature registers); dmean is
+// minus the sum of those same terms over the pixels of a row, so the row loop only folds what the pixels already hold.
+template <int C, bool VEC>
+__global__ __launch_bounds__(kBlock) void label_cohesion_backward_kernel(const float* __restrict__ feat,
+                                                                         const int32_t* __restrict__ labels,
+                                                                         const float* __restrict__ mean,
+                                                                         const float* __restrict__ gl, int N, int64_t HW,
+                                                                         float* __restrict__ dfeat,
+                                                                         float* __restrict__ dmean) {
+    const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPix;
+    float f[C][kPix];
+    int row[kPix];
+#pragma unroll
+    for (int c = 0; c < C; ++c) load4_clamped<VEC>(feat + (size_t)c * HW, i0, HW, f[c]);
+    load_rows<VEC>(labels, i0, HW, N, row);
+    float mu[C][kPix], g[kPix];
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) {                    // all gathers first: nothing below waits on a load of its own
+        const bool in = row[j] >= 0;
+        const size_t r = in ? (size_t)row[j] : 0;       // row 0 where the pixel has none (N > 0): g = 0 there
+#pragma unroll
+        for (int c = 0; c < C; ++c) mu[c][j] = mean[r * C + c];
+        const float v = gl[r];
+        g[j] = in ? v : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < kPix; ++j) {
+        float d[C], d2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            d[c] = f[c][j] - mu[c][j];
+            d2 += d[c] * d[c];
+        }
+        const float dist = sqrtf(d2);
+        // d||x|| / dx = x / ||x||, defined as 0 at x = 0 (torch.norm's subgradient)
+        const float s = (row[j] >= 0 && dist > 0.f) ? g[j] / dist : 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) f[c][j] = d[c] * s;
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) store4<VEC>(dfeat + (size_t)c * HW, i0, HW, f[c]);
+    const int lane = lane_id();
+    for_each_present_row(row, [&](int n, uint32_t hit) {
+        float v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = 0.f;
+#pragma unroll
+        for (int j = 0; j < kPix; ++j)
+#pragma unroll
+            for (int c = 0; c < C; ++c) v[c] -= ((hit >> j) & 1u) ? f[c][j] : 0.f;
+        const float y = wave_fold16(v);
+        const int slot = lane >> 2;
+        if ((lane & 3) == 0 && slot < C) atomicAdd(dmean + (size_t)n * kRow + slot, y);
+    });
+}
+
 int check(int C, int N, int64_t HW, const void* a, const void* b, const void* c) {
     if (C != 3 && C != 6) { set_error("mask ops: C=%d unsupported (3 or 6)", C); return OGS_ERR_UNSUPPORTED; }
     if (N < 0 || HW < 0 || HW >= ((int64_t)1 << 40)) { set_error("mask ops: bad sizes N=%d HW=%lld", N, (long long)HW); return OGS_ERR_INVALID_ARG; }
@@ -458,6 +705,93 @@ int ogs_mask_cohesion_backward(const float* feat, const uint8_t* masks, const fl
     const bool vec = vec_ok(HW, feat, masks, dfeat);
 #define CALL(CC, VV)                                                                                              \
     OGS_LAUNCH((mask_cohesion_backward_kernel<CC, VV>), dim3(strips(HW)), dim3(kBlock), 0, s, feat, masks, mean, gl, \
+               N, HW, dfeat, dmean)
+    OGS_MASK_DISPATCH(CALL);
+#undef CALL
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
+}
+
+// ---- label twins of the four entry points above: same checks, same tables, labels [HW] int32 in place of the stack ----
+int ogs_label_feature_sums(const float* feat, const int32_t* labels, const float* weight, int32_t C, int32_t N,
+                           int64_t HW, int32_t with_squares, float* table, void* stream_) {
+    int rc = check(C, N, HW, feat, labels, table);
+    if (rc != OGS_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (N == 0) return OGS_OK;
+    OGS_HIP_CHECK(hipMemsetAsync(table, 0, (size_t)N * kRow * sizeof(float), s));
+    if (HW == 0) return OGS_OK;
+    const bool vec = vec_ok(HW, feat, nullptr, weight, labels);
+#define CALL(CC, VV)                                                                                                  \
+    if (with_squares) OGS_LAUNCH((label_feature_sums_kernel<CC, true, VV>), dim3(strips(HW)), dim3(kBlock), 0, s, feat, \
+                                 labels, weight, N, HW, table);                                                       \
+    else OGS_LAUNCH((label_feature_sums_kernel<CC, false, VV>), dim3(strips(HW)), dim3(kBlock), 0, s, feat, labels,    \
+                    weight, N, HW, table)
+    OGS_MASK_DISPATCH(CALL);
+#undef CALL
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
+}
+
+int ogs_label_feature_sums_backward(const int32_t* labels, const float* weight, const float* coef, const float* feat,
+                                    const float* coef_cnt, int32_t C, int32_t N, int64_t HW, float* dfeat,
+                                    float* dweight, void* stream_) {
+    int rc = check(C, N, HW, labels, coef, dfeat);
+    if (rc != OGS_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (HW == 0) return OGS_OK;
+    if (!dfeat) { set_error("mask ops: NULL pointer"); return OGS_ERR_INVALID_ARG; }
+    if (dweight && N > 0 && (!feat || !coef_cnt)) { set_error("mask ops: dweight needs feat and coef_cnt"); return OGS_ERR_INVALID_ARG; }
+    if (N == 0) {
+        OGS_HIP_CHECK(hipMemsetAsync(dfeat, 0, (size_t)C * HW * sizeof(float), s));
+        if (dweight) OGS_HIP_CHECK(hipMemsetAsync(dweight, 0, (size_t)HW * sizeof(float), s));
+        return OGS_OK;
+    }
+    const bool vec = vec_ok(HW, dfeat, nullptr, weight, feat) && vec_ok(HW, dweight, nullptr, labels);
+#define CALL(CC, VV)                                                                                                   \
+    if (dweight) OGS_LAUNCH((label_feature_sums_backward_kernel<CC, VV, true>), dim3(strips(HW)), dim3(kBlock), 0, s,    \
+                            labels, weight, coef, feat, coef_cnt, N, HW, dfeat, dweight);                              \
+    else OGS_LAUNCH((label_feature_sums_backward_kernel<CC, VV, false>), dim3(strips(HW)), dim3(kBlock), 0, s, labels,  \
+                    weight, coef, feat, coef_cnt, N, HW, dfeat, dweight)
+    OGS_MASK_DISPATCH(CALL);
+#undef CALL
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
+}
+
+int ogs_label_cohesion(const float* feat, const int32_t* labels, const float* mean, int32_t C, int32_t N, int64_t HW,
+                       float* table, void* stream_) {
+    int rc = check(C, N, HW, feat, labels, table);
+    if (rc != OGS_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (N == 0) return OGS_OK;
+    if (!mean) { set_error("mask ops: NULL pointer"); return OGS_ERR_INVALID_ARG; }
+    OGS_HIP_CHECK(hipMemsetAsync(table, 0, (size_t)N * kRow * sizeof(float), s));
+    if (HW == 0) return OGS_OK;
+    const bool vec = vec_ok(HW, feat, nullptr, labels);
+#define CALL(CC, VV) \
+    OGS_LAUNCH((label_cohesion_kernel<CC, VV>), dim3(strips(HW)), dim3(kBlock), 0, s, feat, labels, mean, N, HW, table)
+    OGS_MASK_DISPATCH(CALL);
+#undef CALL
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
+}
+
+int ogs_label_cohesion_backward(const float* feat, const int32_t* labels, const float* mean, const float* gl, int32_t C,
+                                int32_t N, int64_t HW, float* dfeat, float* dmean, void* stream_) {
+    int rc = check(C, N, HW, feat, labels, dfeat);
+    if (rc != OGS_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (N > 0) {
+        if (!mean || !gl || !dmean) { set_error("mask ops: NULL pointer"); return OGS_ERR_INVALID_ARG; }
+        OGS_HIP_CHECK(hipMemsetAsync(dmean, 0, (size_t)N * kRow * sizeof(float), s));
+    }
+    if (HW == 0) return OGS_OK;
+    if (!dfeat) { set_error("mask ops: NULL pointer"); return OGS_ERR_INVALID_ARG; }
+    if (N == 0) { OGS_HIP_CHECK(hipMemsetAsync(dfeat, 0, (size_t)C * HW * sizeof(float), s)); return OGS_OK; }
+    const bool vec = vec_ok(HW, feat, nullptr, labels, dfeat);
+#define CALL(CC, VV)                                                                                               \
+    OGS_LAUNCH((label_cohesion_backward_kernel<CC, VV>), dim3(strips(HW)), dim3(kBlock), 0, s, feat, labels, mean, gl, \
                N, HW, dfeat, dmean)
     OGS_MASK_DISPATCH(CALL);
 #undef CALL

@@ -6,6 +6,7 @@ Same names, arguments and results as the reference's
   utils/opengs_utlis.py:240-283   mask_feature_mean
   train.py:102-122                cohesion_loss
   train.py:124-155                separation_loss
+  utils/opengs_utlis.py:125-182   get_SAM_mask_and_feat   (returns a LabelMasks in place of the one-hot stack)
 but without the [num_mask, C, H, W] expansions: the two hot ones (mask_feature_mean, cohesion_loss, called every
 stage-1 step, train.py:450-452) are segmented reductions in HIP (include/ogs_mask.h) with hand-written
 backward passes; the others are small and stay plain torch on the GPU.  No CPU path: CPU tensors raise.
@@ -38,6 +39,62 @@ def _mask_bytes(masks: torch.Tensor) -> torch.Tensor:
     if masks.dtype == torch.uint8 and masks.is_contiguous():
         return masks
     return (masks != 0).to(torch.uint8).contiguous()
+
+
+class LabelMasks:
+    """A disjoint [N, H, W] mask stack held as ONE int32 label image: pixel (y, x) lies in mask labels[y, x] - 1 when
+    1 <= labels[y, x] <= num_mask and in no mask otherwise (0 = invalid pixel).  mask_feature_mean and cohesion_loss
+    take it in place of the stack and then read 4 bytes per pixel of masks whatever N is; `dense()` gives the rows to
+    any other consumer.  Not a tensor."""
+
+    def __init__(self, labels: torch.Tensor, num_mask: int):
+        if labels.dim() != 2:
+            raise RuntimeError(f"LabelMasks: labels must be [H, W], got {tuple(labels.shape)}")
+        self.labels = labels.to(torch.int32).contiguous()
+        self.num_mask = int(num_mask)
+
+    @property
+    def shape(self):
+        return (self.num_mask, int(self.labels.shape[0]), int(self.labels.shape[1]))
+
+    def __len__(self):
+        return self.num_mask
+
+    def to(self, device):
+        return LabelMasks(self.labels.to(device), self.num_mask)
+
+    def dense(self) -> torch.Tensor:
+        """The bool stack [N, H, W]."""
+        ids = torch.arange(1, self.num_mask + 1, dtype=torch.int32, device=self.labels.device)
+        return self.labels[None] == ids[:, None, None]
+
+
+def get_SAM_mask_and_feat(gt_sam_mask, level=3, filter_th=50, original_mask_feat=None, sample_mask=False):
+    """The reference's per-iteration mask preparation (utils/opengs_utlis.py:125-182; train.py:441) without its
+    [H, W, num_mask + 1] int64 one-hot (1.6 GB written and read back per step at 1080p with 96 masks).
+    gt_sam_mask [4, H, W]: mask ids, each level's ids continuing after the previous level's maximum, -1 = no mask.
+    Returns (mask_id [H, W] int64 with 0 = invalid, masks, invalid_pix [H, W] bool), or with `original_mask_feat`
+    (mask_id, masks, mask_feat, invalid_pix), values as the reference's -- except that `masks` is a LabelMasks with
+    num_mask = mask_id.max() where the reference returns mask_bool [num_mask, H, W]: mask_feature_mean and
+    cohesion_loss take it as it is, `masks.dense()` is the stack.  Nothing of size num_mask * H * W is allocated; the
+    two maxima it needs come back in ONE device-to-host read.  Runs on the device of its input (CPU included).
+    filter_th / sample_mask are accepted and unused, as in the reference."""
+    cur = gt_sam_mask[level]
+    if level > 0:
+        prev_max, cur_max = torch.stack([gt_sam_mask[level - 1].max(), cur.max()]).tolist()
+    else:
+        prev_max, cur_max = None, cur.max().item()
+    # ids of this level: -1, 0 .. num_mask-1  ->  0 (invalid), 1 .. num_mask
+    offset = 0 if prev_max is None else prev_max + 1
+    mask_id = ((cur - offset).clamp_min(-1) + 1).to(torch.int64)
+    num_mask = max(int(cur_max - offset), -1) + 1
+    invalid_pix = mask_id == 0
+    masks = LabelMasks(mask_id, num_mask)
+    if original_mask_feat is not None:
+        min_ind = 0 if prev_max is None else int(prev_max) + 1
+        mask_feat = original_mask_feat[min_ind:int(cur_max) + 1, :].clone()
+        return mask_id, masks, mask_feat, invalid_pix
+    return mask_id, masks, invalid_pix
 
 
 class _MaskSums(torch.autograd.Function):
@@ -81,21 +138,64 @@ class _MaskSums(torch.autograd.Function):
                 dweight.reshape(ctx.weight_shape) if need_w else None, None)
 
 
+class _LabelSums(torch.autograd.Function):
+    """_MaskSums over a label image (ogs_label_feature_sums): same table, same saved tensors, same gradients."""
+
+    @staticmethod
+    def forward(ctx, feat_map, labels, num_mask, weight, with_squares):
+        lib = _lib.lib()
+        f = feat_map.detach().to(torch.float32).contiguous()
+        C, H, W = (int(x) for x in f.shape)
+        N = int(num_mask)
+        w = None if weight is None else weight.detach().to(torch.float32).reshape(H, W).contiguous()
+        width = (2 * C + 1) if with_squares else (C + 1)
+        table = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)   # 64-byte rows (ogs_mask.h)
+        check(lib.ogs_label_feature_sums(ptr(f), ptr(labels), ptr(w), C, N, H * W, int(bool(with_squares)),
+                                         ptr(table), _stream()), "ogs_label_feature_sums")
+        ctx.save_for_backward(labels, w, f)
+        ctx.shape = (C, H, W, N)
+        ctx.weight_shape = None if weight is None else tuple(weight.shape)
+        ctx.with_squares = bool(with_squares)
+        return table[:, :width]
+
+    @staticmethod
+    def backward(ctx, g_table):
+        if ctx.with_squares:
+            raise RuntimeError("mask_feature_mean(return_var=True) is not differentiable here (the reference only "
+                               "uses it under no_grad, train.py:689)")
+        labels, w, f = ctx.saved_tensors
+        C, H, W, N = ctx.shape
+        coef = g_table[:, :C].to(torch.float32).contiguous()
+        need_w = w is not None and ctx.needs_input_grad[3]
+        coef_cnt = g_table[:, C].to(torch.float32).contiguous() if need_w else None
+        dfeat = torch.empty(C, H, W, dtype=torch.float32, device=g_table.device)
+        dweight = torch.empty(H, W, dtype=torch.float32, device=g_table.device) if need_w else None
+        check(_lib.lib().ogs_label_feature_sums_backward(ptr(labels), ptr(w), ptr(coef), ptr(f), ptr(coef_cnt), C, N,
+                                                         H * W, ptr(dfeat), ptr(dweight), _stream()),
+              "ogs_label_feature_sums_backward")
+        return (dfeat if ctx.needs_input_grad[0] else None, None, None,
+                dweight.reshape(ctx.weight_shape) if need_w else None, None)
+
+
 def mask_feature_mean(feat_map, gt_masks, image_mask=None, return_var=False):
     """Average instance feature inside each mask (utils/opengs_utlis.py:240-283).
-    feat_map [C=3|6, H, W]; gt_masks [num_mask, H, W] (0/1 of any dtype); image_mask [1,H,W] / [H,W] weights
+    feat_map [C=3|6, H, W]; gt_masks [num_mask, H, W] (0/1 of any dtype) or a LabelMasks; image_mask [1,H,W] / [H,W] weights
     (the rendered silhouette, train.py:450) or None.  Returns [num_mask, C]; with return_var=True
     (mean [N,C], variance [N], pixel count [N]) as the reference."""
     _need_gpu(feat_map, "feat_map")
     C, H, W = (int(x) for x in feat_map.shape)
-    m = _mask_bytes(gt_masks.to(feat_map.device))
+    labelled = isinstance(gt_masks, LabelMasks)
+    m = gt_masks.to(feat_map.device) if labelled else _mask_bytes(gt_masks.to(feat_map.device))
     if tuple(m.shape[1:]) != (H, W):
         raise RuntimeError(f"gt_masks must be [num_mask, {H}, {W}], got {tuple(gt_masks.shape)}")
     if image_mask is not None:
         if image_mask.numel() != H * W:
             raise RuntimeError(f"image_mask must have H*W = {H * W} elements, got {tuple(image_mask.shape)}")
         image_mask = image_mask.to(feat_map.device)
-    table = _MaskSums.apply(feat_map, m, image_mask, bool(return_var))
+    if labelled:
+        table = _LabelSums.apply(feat_map, m.labels, m.num_mask, image_mask, bool(return_var))
+    else:
+        table = _MaskSums.apply(feat_map, m, image_mask, bool(return_var))
     counts = table[:, C].clamp(min=1)
     mean = table[:, :C] / counts[:, None]
     if not return_var:
@@ -134,10 +234,44 @@ class _Cohesion(torch.autograd.Function):
         return dfeat, None, dmean[:, :C]
 
 
+class _LabelCohesion(torch.autograd.Function):
+    """_Cohesion over a label image (ogs_label_cohesion)."""
+
+    @staticmethod
+    def forward(ctx, feat_map, labels, num_mask, mean):
+        lib = _lib.lib()
+        f = feat_map.detach().to(torch.float32).contiguous()
+        mu = mean.detach().to(torch.float32).contiguous()
+        C, H, W = (int(x) for x in f.shape)
+        N = int(num_mask)
+        table = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)
+        check(lib.ogs_label_cohesion(ptr(f), ptr(labels), ptr(mu), C, N, H * W, ptr(table), _stream()),
+              "ogs_label_cohesion")
+        cnt = table[:, 1].clamp(min=1)
+        ctx.save_for_backward(f, labels, mu, cnt)
+        ctx.num_mask = N
+        return (table[:, 0] / cnt).mean() if N > 0 else table.sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        f, labels, mu, cnt = ctx.saved_tensors
+        C, H, W = (int(x) for x in f.shape)
+        N = ctx.num_mask
+        gl = (g.to(torch.float32) / (max(N, 1) * cnt)).contiguous()
+        dfeat = torch.empty(C, H, W, dtype=torch.float32, device=f.device)
+        dmean = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)
+        check(_lib.lib().ogs_label_cohesion_backward(ptr(f), ptr(labels), ptr(mu), ptr(gl), C, N, H * W, ptr(dfeat),
+                                                     ptr(dmean), _stream()), "ogs_label_cohesion_backward")
+        return dfeat, None, None, dmean[:, :C]
+
+
 def cohesion_loss(feat_map, gt_mask, feat_mean_stack):
     """Intra-mask smoothing loss, Eq. (1) of the paper (train.py:102-122): mean over masks of the mean L2 distance
     between the pixels of a mask and that mask's mean feature."""
     _need_gpu(feat_map, "feat_map")
+    if isinstance(gt_mask, LabelMasks):
+        m = gt_mask.to(feat_map.device)
+        return _LabelCohesion.apply(feat_map, m.labels, m.num_mask, feat_mean_stack)
     m = _mask_bytes(gt_mask.to(feat_map.device))
     return _Cohesion.apply(feat_map, m, feat_mean_stack)
 
