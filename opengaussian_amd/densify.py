@@ -212,8 +212,9 @@ class DensifyState:
 
 
 def prune_points(state: DensifyState, mask: torch.Tensor) -> Dict[str, nn.Parameter]:
-    """scene/gaussian_model.py:391-410: remove the rows where `mask` is True (parameters, moments, statistics)."""
-    params, (acc, den, rad) = prune_optimizer(state.optimizer, ~mask.reshape(-1),
+    """scene/gaussian_model.py:391-410: remove the rows where `mask` is True (parameters, moments, statistics).
+    `mask` is read as truth values whatever its dtype (`~` on a uint8 mask would flip bits and keep every row)."""
+    params, (acc, den, rad) = prune_optimizer(state.optimizer, mask.reshape(-1) == 0,
                                               extras=(state.xyz_gradient_accum, state.denom, state.max_radii2D.reshape(-1, 1)))
     state.xyz_gradient_accum, state.denom, state.max_radii2D = acc, den, rad.reshape(-1)
     return params
