@@ -1,4 +1,4 @@
-"""ctypes binding of libogs_hip.so (C ABI: include/ogs_raster.h, include/ogs_kmeans.h).
+"""ctypes binding of libogs_hip.so (C ABI: include/ogs_raster.h, include/ogs_kmeans.h, ...).
 
 The product path has NO CPU fallback: if the HIP library is missing or fails to load, ``lib()`` raises.
 """
@@ -126,6 +126,19 @@ SIGNATURES = {
     "ogs_kmeans_accumulate": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "ogs_kmeans_update": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "ogs_kmeans_gather": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp]),
+    "ogs_refine_wave_table_capacity": (C.c_size_t, []),
+    "ogs_refine_wave_max_pixels": (C.c_size_t, []),
+    "ogs_refine_block_scratch_words": (C.c_size_t, [C.c_int32]),
+    "ogs_refine_visibility": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_float, C.c_float, _vp,
+                                        C.c_float, C.c_float, _vp, _vp]),
+    "ogs_refine_footprint_labels": (C.c_int, [C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp,
+                                              _vp]),
+    "ogs_refine_footprint_labels_block": (C.c_int, [C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp,
+                                                    _vp, _vp, _vp]),
+    "ogs_refine_vote": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp]),
+    "ogs_refine_expand": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp,
+                                    C.c_int32, _vp]),
+    "ogs_refine_finalize": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_float, _vp, _vp]),
 }
 
 _lib = None

@@ -26,6 +26,8 @@ EXTRA = {
     # k-means argmin: same sum-of-squares operation order as oracle/kmeans_oracle.py (HBM-bound, FMA buys nothing)
     "kmeans.hip": ["-ffp-contract=off"],
     "adam.hip": ["-ffp-contract=off"],
+    # footprint alpha and the uint8 pixel made of it: the bits of a P = 1 pass through the blend kernels
+    "refine.hip": ["-ffp-contract=off"],
 }
 
 
