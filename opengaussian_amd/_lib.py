@@ -139,6 +139,14 @@ SIGNATURES = {
     "ogs_refine_expand": (C.c_int, [C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp,
                                     C.c_int32, _vp]),
     "ogs_refine_finalize": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_float, _vp, _vp]),
+    "ogs_loss_photometric_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "ogs_loss_photometric_forward": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, _vp, _vp, _vp]),
+    "ogs_loss_photometric_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_float, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                                _vp]),
+    "ogs_loss_masked_tmp_bytes": (C.c_size_t, []),
+    "ogs_loss_masked_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
+    "ogs_loss_masked_backward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp,
+                                           _vp]),
 }
 
 _lib = None
