@@ -31,11 +31,18 @@ extern "C" {
 
 /* table[n, 0:C]   = sum_pix mask[n,pix] * w[pix] * feat[:,pix]
  * table[n, C]     = sum_pix mask[n,pix] * w[pix]                      (w = 1 when weight == NULL)
- * with_squares != 0 (C == 6 or 3): additionally table[n, C+1 : 2C+1] = sum mask*w*feat^2
- * (variance path of mask_feature_mean(return_var=True), opengs_utlis.py:272-283).
+ * with_squares != 0 (C == 6 or 3): additionally table[n, C+1 : 2C+1] = sum mask*w*feat^2.  A variance formed from these
+ * raw moments cancels (sum f^2 - 2 mean sum f + n mean^2); mask_feature_mean(return_var=True) takes
+ * ogs_mask_feature_sqdev below instead.
  * The table is zeroed by the call.  mask_feature_mean = table[:, :C] / clamp(table[:, C], min=1). */
 int ogs_mask_feature_sums(const float* feat, const uint8_t* masks, const float* weight, int32_t C, int32_t N,
                           int64_t HW, int32_t with_squares, float* table, void* stream);
+
+/* Second pass of the variance of mask_feature_mean(return_var=True) (opengs_utlis.py:272-283), once the means are known:
+ * table[n, 0:C] = sum_pix mask[n,pix] * w[pix] * (feat[:,pix] - mean[n,:])^2   (w = 1 when weight == NULL), mean [N, C]
+ * contiguous.  The table (rows OGS_MASK_TABLE_STRIDE apart) is zeroed by the call. */
+int ogs_mask_feature_sqdev(const float* feat, const uint8_t* masks, const float* weight, const float* mean, int32_t C,
+                           int32_t N, int64_t HW, float* table, void* stream);
 
 /* Backward of the sums table, given g = dL/dtable ([N, C+1], host side: coef = g[:, :C] contiguous [N,C],
  * coef_cnt = g[:, C] contiguous [N]):
@@ -58,13 +65,15 @@ int ogs_mask_cohesion(const float* feat, const uint8_t* masks, const float* mean
 int ogs_mask_cohesion_backward(const float* feat, const uint8_t* masks, const float* mean, const float* gl, int32_t C,
                                int32_t N, int64_t HW, float* dfeat, float* dmean, void* stream);
 
-/* Label form of the four calls above, for DISJOINT masks (the masks of one SAM level are the one-hot of one id image,
+/* Label form of the five calls above, for DISJOINT masks (the masks of one SAM level are the one-hot of one id image,
  * utils/opengs_utlis.py:134-149): `labels` is one int32 per pixel ([HW]) in place of the [N,HW] byte stack.  Pixel p
  * lies in mask row labels[p] - 1 when 1 <= labels[p] <= N and in no row otherwise (0 = invalid pixel, negative values,
  * values above N); an out-of-range label is never used as an address.  Every kernel reads 4 bytes per pixel of masks
  * whatever N is.  Results, table layout, zeroing, C / with_squares rules and error codes are those of the dense twin. */
 int ogs_label_feature_sums(const float* feat, const int32_t* labels, const float* weight, int32_t C, int32_t N,
                            int64_t HW, int32_t with_squares, float* table, void* stream);
+int ogs_label_feature_sqdev(const float* feat, const int32_t* labels, const float* weight, const float* mean, int32_t C,
+                            int32_t N, int64_t HW, float* table, void* stream);
 int ogs_label_feature_sums_backward(const int32_t* labels, const float* weight, const float* coef, const float* feat,
                                     const float* coef_cnt, int32_t C, int32_t N, int64_t HW, float* dfeat,
                                     float* dweight, void* stream);

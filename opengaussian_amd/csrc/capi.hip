@@ -149,7 +149,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 402; }
+int ogs_version(void) { return 403; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 

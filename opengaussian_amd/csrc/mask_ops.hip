@@ -205,6 +205,47 @@ __global__ __launch_bounds__(kBlock) void mask_cohesion_kernel(const float* __re
     });
 }
 
+// Second pass of the variance of mask_feature_mean(return_var=True): table[n, c] = sum_pix mask * w * (feat[c] - mean[n, c])^2,
+// the deviations formed per pixel from means that are already known.  (The one-pass form sum f^2 - 2 mean sum f + n mean^2
+// cancels: on a mask whose features sit at 0.9 +- 0.05 it keeps three of the seven digits of its fp32 sums.)
+template <int C, bool VEC>
+__global__ __launch_bounds__(kBlock) void mask_feature_sqdev_kernel(const float* __restrict__ feat,
+                                                                    const uint8_t* __restrict__ masks,
+                                                                    const float* __restrict__ weight,
+                                                                    const float* __restrict__ mean, int N, int64_t HW,
+                                                                    float* __restrict__ table) {
+    const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPix;
+    float f[C][kPix], w[kPix];
+#pragma unroll
+    for (int c = 0; c < C; ++c) load4<VEC>(feat + (size_t)c * HW, i0, HW, f[c]);
+    if (weight) load4<VEC>(weight, i0, HW, w);
+    else {
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) w[j] = 1.f;
+    }
+    const int lane = lane_id();
+    for_each_present_mask<VEC>(masks, N, HW, i0, [&](int n, uint32_t word) {
+        float mu[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) mu[c] = mean[(size_t)n * C + c];
+        float v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = 0.f;
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) {
+            const float wj = in_mask(word, j) ? w[j] : 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float d = f[c][j] - mu[c];
+                v[c] += wj * d * d;
+            }
+        }
+        const float y = wave_fold16(v);
+        const int slot = lane >> 2;
+        if ((lane & 3) == 0 && slot < C) atomicAdd(table + (size_t)n * kRow + slot, y);
+    });
+}
+
 template <int C, bool VEC>
 __global__ __launch_bounds__(kBlock) void mask_cohesion_backward_kernel(const float* __restrict__ feat,
                                                                         const uint8_t* __restrict__ masks,
@@ -445,6 +486,46 @@ __global__ __launch_bounds__(kBlock) void label_cohesion_kernel(const float* __r
     });
 }
 
+template <int C, bool VEC>
+__global__ __launch_bounds__(kBlock) void label_feature_sqdev_kernel(const float* __restrict__ feat,
+                                                                     const int32_t* __restrict__ labels,
+                                                                     const float* __restrict__ weight,
+                                                                     const float* __restrict__ mean, int N, int64_t HW,
+                                                                     float* __restrict__ table) {
+    const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPix;
+    float f[C][kPix], w[kPix];
+    int row[kPix];
+#pragma unroll
+    for (int c = 0; c < C; ++c) load4_clamped<VEC>(feat + (size_t)c * HW, i0, HW, f[c]);
+    if (weight) load4_clamped<VEC>(weight, i0, HW, w);
+    else {
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) w[j] = 1.f;
+    }
+    load_rows<VEC>(labels, i0, HW, N, row);
+    const int lane = lane_id();
+    for_each_present_row(row, [&](int n, uint32_t hit) {
+        float mu[C];                                   // wave-uniform row -> scalar loads
+#pragma unroll
+        for (int c = 0; c < C; ++c) mu[c] = mean[(size_t)n * C + c];
+        float v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = 0.f;
+#pragma unroll
+        for (int j = 0; j < kPix; ++j) {
+            const float wj = ((hit >> j) & 1u) ? w[j] : 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float d = f[c][j] - mu[c];
+                v[c] += wj * d * d;
+            }
+        }
+        const float y = wave_fold16(v);
+        const int slot = lane >> 2;
+        if ((lane & 3) == 0 && slot < C) atomicAdd(table + (size_t)n * kRow + slot, y);
+    });
+}
+
 // dfeat is per pixel (mean and gl gathered by the pixel's own row, written in place of the feature registers); dmean is
 // minus the sum of those same terms over the pixels of a row, so the row loop only folds what the pixels already hold.
 template <int C, bool VEC>
@@ -536,6 +617,11 @@ using namespace ogs;
 constexpr int kSepMaxN = 1024, kSepMaxC = 16;
 __global__ __launch_bounds__(kBlock) void separation_rows_kernel(const float* __restrict__ means, int N, int C, int late,
                                                                  float* __restrict__ weights, float* __restrict__ row_loss) {
+    // The rank weights are compared bit for bit with the reference's float32 expression, and the late rule is an exact
+    // decision on them.  The pragma keeps every product written in this body rounded on its own; __fmul_rn / __fadd_rn
+    // would not (plain * and + in HIP's headers, compiled there under the default -ffp-contract=fast, they fuse once
+    // inlined -- (rank / (N-1)) * 0.9 + 0.1 came out as one v_fmamk_f32, off by an ulp for 299 of the 1024 ranks of N = 1024).
+#pragma clang fp contract(off)
     __shared__ float s_inv[kSepMaxN];
     __shared__ float s_mi[kSepMaxC];
     __shared__ float s_part[kBlock];
@@ -546,7 +632,7 @@ __global__ __launch_bounds__(kBlock) void separation_rows_kernel(const float* __
         float d2 = 0.f;
         for (int c = 0; c < C; ++c) {
             const float d = s_mi[c] - means[(size_t)j * C + c];
-            d2 = __fadd_rn(d2, __fmul_rn(d, d));            // pow(2) then sum(2): no contraction
+            d2 = d2 + d * d;                                // pow(2) then sum(2): no contraction
         }
         s_inv[j] = j == i ? 0.f : 1.0f / (d2 + 1.0f);
     }
@@ -559,10 +645,10 @@ __global__ __launch_bounds__(kBlock) void separation_rows_kernel(const float* __
             const float u = s_inv[k];                          // wave-uniform address: broadcast read
             rank += (u < v || (u == v && k < j)) ? 1 : 0;
         }
-        float w = __fadd_rn(__fmul_rn((float)rank / (float)(N - 1), 0.9f), 0.1f);   // (rank / (N-1)) * (1.0 - 0.1) + 0.1
+        float w = ((float)rank / (float)(N - 1)) * 0.9f + 0.1f;     // (rank / (N-1)) * (1.0 - 0.1) + 0.1
         if (late && w < 0.9f) w = 0.1f;                         // iteration > 35 000 (train.py:148-149)
         weights[(size_t)i * N + j] = w;
-        part = __fadd_rn(part, __fmul_rn(v, w));
+        part = part + v * w;
     }
     s_part[tid] = part;
     __syncthreads();
@@ -690,6 +776,25 @@ int ogs_mask_cohesion(const float* feat, const uint8_t* masks, const float* mean
     return OGS_OK;
 }
 
+int ogs_mask_feature_sqdev(const float* feat, const uint8_t* masks, const float* weight, const float* mean, int32_t C,
+                           int32_t N, int64_t HW, float* table, void* stream_) {
+    int rc = check(C, N, HW, feat, masks, table);
+    if (rc != OGS_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (N == 0) return OGS_OK;
+    if (!mean) { set_error("mask ops: NULL pointer"); return OGS_ERR_INVALID_ARG; }
+    OGS_HIP_CHECK(hipMemsetAsync(table, 0, (size_t)N * kRow * sizeof(float), s));
+    if (HW == 0) return OGS_OK;
+    const bool vec = vec_ok(HW, feat, masks, weight);
+#define CALL(CC, VV)                                                                                                  \
+    OGS_LAUNCH((mask_feature_sqdev_kernel<CC, VV>), dim3(strips(HW)), dim3(kBlock), 0, s, feat, masks, weight, mean, N, \
+               HW, table)
+    OGS_MASK_DISPATCH(CALL);
+#undef CALL
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
+}
+
 int ogs_mask_cohesion_backward(const float* feat, const uint8_t* masks, const float* mean, const float* gl, int32_t C,
                                int32_t N, int64_t HW, float* dfeat, float* dmean, void* stream_) {
     int rc = check(C, N, HW, feat, masks, dfeat);
@@ -771,6 +876,25 @@ int ogs_label_cohesion(const float* feat, const int32_t* labels, const float* me
     const bool vec = vec_ok(HW, feat, nullptr, labels);
 #define CALL(CC, VV) \
     OGS_LAUNCH((label_cohesion_kernel<CC, VV>), dim3(strips(HW)), dim3(kBlock), 0, s, feat, labels, mean, N, HW, table)
+    OGS_MASK_DISPATCH(CALL);
+#undef CALL
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
+}
+
+int ogs_label_feature_sqdev(const float* feat, const int32_t* labels, const float* weight, const float* mean, int32_t C,
+                            int32_t N, int64_t HW, float* table, void* stream_) {
+    int rc = check(C, N, HW, feat, labels, table);
+    if (rc != OGS_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (N == 0) return OGS_OK;
+    if (!mean) { set_error("mask ops: NULL pointer"); return OGS_ERR_INVALID_ARG; }
+    OGS_HIP_CHECK(hipMemsetAsync(table, 0, (size_t)N * kRow * sizeof(float), s));
+    if (HW == 0) return OGS_OK;
+    const bool vec = vec_ok(HW, feat, nullptr, weight, labels);
+#define CALL(CC, VV)                                                                                                    \
+    OGS_LAUNCH((label_feature_sqdev_kernel<CC, VV>), dim3(strips(HW)), dim3(kBlock), 0, s, feat, labels, weight, mean, N, \
+               HW, table)
     OGS_MASK_DISPATCH(CALL);
 #undef CALL
     OGS_LAUNCH_CHECK(0, s);

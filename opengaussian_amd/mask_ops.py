@@ -98,28 +98,28 @@ def get_SAM_mask_and_feat(gt_sam_mask, level=3, filter_th=50, original_mask_feat
 
 
 class _MaskSums(torch.autograd.Function):
-    """table [N, C+1] (or [N, 2C+1] with squares) of weighted per-mask feature sums | weighted counts."""
+    """table [N, C+1] of weighted per-mask feature sums | weighted counts.  `for_var`: the call belongs to
+    mask_feature_mean(return_var=True), which is not differentiable."""
 
     @staticmethod
-    def forward(ctx, feat_map, masks_u8, weight, with_squares):
+    def forward(ctx, feat_map, masks_u8, weight, for_var):
         lib = _lib.lib()
         f = feat_map.detach().to(torch.float32).contiguous()
         C, H, W = (int(x) for x in f.shape)
         N = int(masks_u8.shape[0])
         w = None if weight is None else weight.detach().to(torch.float32).reshape(H, W).contiguous()
-        width = (2 * C + 1) if with_squares else (C + 1)
         table = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)   # 64-byte rows (ogs_mask.h)
-        check(lib.ogs_mask_feature_sums(ptr(f), ptr(masks_u8), ptr(w), C, N, H * W, int(bool(with_squares)),
+        check(lib.ogs_mask_feature_sums(ptr(f), ptr(masks_u8), ptr(w), C, N, H * W, 0,
                                         ptr(table), _stream()), "ogs_mask_feature_sums")
         ctx.save_for_backward(masks_u8, w, f)
         ctx.shape = (C, H, W, N)
         ctx.weight_shape = None if weight is None else tuple(weight.shape)
-        ctx.with_squares = bool(with_squares)
-        return table[:, :width]
+        ctx.for_var = bool(for_var)
+        return table[:, :C + 1]
 
     @staticmethod
     def backward(ctx, g_table):
-        if ctx.with_squares:
+        if ctx.for_var:
             raise RuntimeError("mask_feature_mean(return_var=True) is not differentiable here (the reference only "
                                "uses it under no_grad, train.py:689)")
         masks_u8, w, f = ctx.saved_tensors
@@ -142,25 +142,24 @@ class _LabelSums(torch.autograd.Function):
     """_MaskSums over a label image (ogs_label_feature_sums): same table, same saved tensors, same gradients."""
 
     @staticmethod
-    def forward(ctx, feat_map, labels, num_mask, weight, with_squares):
+    def forward(ctx, feat_map, labels, num_mask, weight, for_var):
         lib = _lib.lib()
         f = feat_map.detach().to(torch.float32).contiguous()
         C, H, W = (int(x) for x in f.shape)
         N = int(num_mask)
         w = None if weight is None else weight.detach().to(torch.float32).reshape(H, W).contiguous()
-        width = (2 * C + 1) if with_squares else (C + 1)
         table = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)   # 64-byte rows (ogs_mask.h)
-        check(lib.ogs_label_feature_sums(ptr(f), ptr(labels), ptr(w), C, N, H * W, int(bool(with_squares)),
+        check(lib.ogs_label_feature_sums(ptr(f), ptr(labels), ptr(w), C, N, H * W, 0,
                                          ptr(table), _stream()), "ogs_label_feature_sums")
         ctx.save_for_backward(labels, w, f)
         ctx.shape = (C, H, W, N)
         ctx.weight_shape = None if weight is None else tuple(weight.shape)
-        ctx.with_squares = bool(with_squares)
-        return table[:, :width]
+        ctx.for_var = bool(for_var)
+        return table[:, :C + 1]
 
     @staticmethod
     def backward(ctx, g_table):
-        if ctx.with_squares:
+        if ctx.for_var:
             raise RuntimeError("mask_feature_mean(return_var=True) is not differentiable here (the reference only "
                                "uses it under no_grad, train.py:689)")
         labels, w, f = ctx.saved_tensors
@@ -200,10 +199,22 @@ def mask_feature_mean(feat_map, gt_masks, image_mask=None, return_var=False):
     mean = table[:, :C] / counts[:, None]
     if not return_var:
         return mean
-    # sum mask*(f - mean)^2 = sum f^2 - 2 mean sum f + count mean^2   (masked_for_variance, :272-276)
-    raw_count = table[:, C]
-    var_c = (table[:, C + 1:] - 2.0 * mean * table[:, :C] + raw_count[:, None] * mean * mean) / counts[:, None]
-    return mean, var_c.clamp_min(0).mean(dim=1), counts
+    # sum mask*(f - mean)^2 in a second pass over the map, now that the means are known (masked_for_variance, :272-276).
+    # Expanded into sum f^2 - 2 mean sum f + count mean^2 it needs one pass only, but cancels: the fp32 atomic sums of a
+    # 196 k pixel mask at 0.9 +- 0.05 left the variance anywhere between 8e-6 and 1.4e-4 off from call to call (DESIGN.md
+    # section 6b); the deviations from a known mean keep it at 3e-7.
+    f = feat_map.detach().to(torch.float32).contiguous()
+    w = None if image_mask is None else image_mask.detach().to(torch.float32).reshape(H, W).contiguous()
+    mu = mean.detach().contiguous()
+    N = int(mu.shape[0])
+    sq = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)
+    if labelled:
+        check(_lib.lib().ogs_label_feature_sqdev(ptr(f), ptr(m.labels), ptr(w), ptr(mu), C, N, H * W, ptr(sq), _stream()),
+              "ogs_label_feature_sqdev")
+    else:
+        check(_lib.lib().ogs_mask_feature_sqdev(ptr(f), ptr(m), ptr(w), ptr(mu), C, N, H * W, ptr(sq), _stream()),
+              "ogs_mask_feature_sqdev")
+    return mean, (sq[:, :C] / counts[:, None]).mean(dim=1), counts
 
 
 class _Cohesion(torch.autograd.Function):

@@ -3,9 +3,10 @@
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module; the product path
 (opengaussian_amd/mask_ops.py -> include/ogs_mask.h) never does.
 
-PINNED: tests/test_oracle_mask.py checks every function below against tests/golden/mask_golden.npz, produced by
-tests/golden/make_mask_golden.py from the reference's own function bodies
-(/root/reference/utils/opengs_utlis.py, /root/reference/train.py) run on the CPU in the build container.
+PINNED: tests/test_oracle_mask.py checks every function below against tests/golden/mask_golden.npz and
+tests/golden/separation_golden.npz, produced by tests/golden/make_mask_golden.py and make_separation_golden.py from the
+reference's own function bodies (/root/reference/utils/opengs_utlis.py, /root/reference/train.py) run on the CPU in the
+build container.
 
 The restatement is deliberately the segmented form (sum over the pixels of each mask), not a copy of the
 reference's [num_mask, C, H, W] expansion, so that it scales to the test sizes; float64 accumulation is
@@ -61,3 +62,36 @@ def calculate_iou(masks1, masks2, base=None):
     else:
         union = a.sum(dim=1)[None, :] + b.sum(dim=1)[:, None] - inter + 1e-6
     return (inter / union).float()
+
+
+def separation_weights(rank, iteration):
+    """train.py:146-149: the weight of rank r among N, in float32 whatever the means are (`sorted_indices.float()`), and
+    evaluated as the reference writes it -- the late threshold is an exact float32 decision."""
+    N = rank.shape[-1]
+    w = (rank.float() / (N - 1)) * (1.0 - 0.1) + 0.1
+    if iteration > 35_000:
+        w = torch.where(w < 0.9, torch.full_like(w, 0.1), w)
+    return w
+
+
+def separation_inverse_distance(feat_mean_stack, dtype=torch.float64):
+    """train.py:130-141: 1 / (|m_i - m_j|^2 + 1), 0 on the diagonal."""
+    m = feat_mean_stack.to(dtype)
+    N = m.shape[0]
+    inv = 1.0 / ((m.unsqueeze(1) - m.unsqueeze(0)).pow(2).sum(2) + 1)
+    return inv.masked_fill(torch.eye(N, dtype=torch.bool), 0)
+
+
+def separation_loss(feat_mean_stack, iteration, dtype=torch.float64, weights=None):
+    """train.py:124-155.  The reference ranks with argsort().argsort(), whose order among EQUAL inverse distances is
+    implementation defined; here the first sort is stable, i.e. ties rank by column index -- the rule
+    include/ogs_mask.h documents for ogs_separation_loss.  (The second argsort is of a permutation: no ties.)  Within a
+    tie group the weights are a fixed set and the inverse distances are equal, so the VALUE does not depend on the rule;
+    the gradient of a tied row does.  `weights` [N, N]: use these in place of the ranks' (they carry no gradient either
+    way)."""
+    N = feat_mean_stack.shape[0]
+    inv = separation_inverse_distance(feat_mean_stack, dtype)
+    if weights is None:
+        rank = inv.detach().argsort(dim=1, stable=True).argsort(dim=1)
+        weights = separation_weights(rank, iteration)
+    return (inv * weights.to(dtype)).sum() / (N * (N - 1))

@@ -7,8 +7,10 @@ import pytest
 import torch
 
 from tests.golden.make_mask_golden import CASES, case_inputs
+from tests.golden import make_separation_golden as sg
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "mask_golden.npz"))
+SEP_GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "separation_golden.npz"))
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"s{c[0]}")
@@ -69,3 +71,50 @@ def test_mask_ops_refuse_cpu_tensors():
         mask_ops.cohesion_loss(feat, masks, torch.zeros(masks.shape[0], feat.shape[0]))
     with pytest.raises(RuntimeError):
         mask_ops.calculate_iou(masks, masks)
+
+
+@pytest.mark.parametrize("mode", list(sg.ITERATIONS))
+@pytest.mark.parametrize("N,C", sg.CASES, ids=lambda v: str(v))
+def test_separation_oracle_and_torch_formulation_match_reference(N, C, mode):
+    """separation_golden.npz (the reference's separation_loss in float64, early and late weights; N - 1 divisible by 9
+    puts a rank exactly on the late threshold) against the float64 oracle restatement -- to float64 rounding, value and
+    gradient -- and against the product's torch formulation, in float64 likewise and in float32 at the bars of the GPU
+    test: value 2e-6 relative, gradient max(1e-5, 4 * e32) of the largest entry, e32 = the deviation of the reference's
+    own float32 gradient, read from the file."""
+    from oracle import mask_oracle as mo
+    from opengaussian_amd.mask_ops import _separation_loss_torch
+    it = sg.ITERATIONS[mode]
+    base = sg.case_means(N, C)
+    assert float(sg.rank_gap(base).min()) >= sg.GAP               # input condition: no rank hangs on a float32 rounding
+    k = f"n{N}_c{C}_{mode}"
+    value, grad, e32 = float(SEP_GOLD[k + "_value"]), SEP_GOLD[k + "_grad"], float(SEP_GOLD[k + "_e32"])
+    assert grad.shape == (N, C) and grad.dtype == np.float64 and 0.0 < e32 < 1e-6
+    for f, dtype, vtol, gtol in ((lambda m: mo.separation_loss(m, it), torch.float64, 1e-13, 1e-12),
+                                 (lambda m: _separation_loss_torch(m, it), torch.float64, 1e-13, 1e-12),
+                                 (lambda m: _separation_loss_torch(m, it), torch.float32, 2e-6, max(1e-5, 4 * e32))):
+        m = base.clone().to(dtype).requires_grad_(True)
+        loss = f(m)
+        loss.backward()
+        assert loss.dtype == dtype
+        assert abs(float(loss.detach()) - value) <= vtol * abs(value)
+        assert np.abs(m.grad.double().numpy() - grad).max() <= gtol * np.abs(grad).max()
+
+
+def test_separation_late_threshold_is_kept_on_the_boundary():
+    """(8/9) * 0.9 + 0.1 rounds to 0.90000004 in float32: rank 8 (N-1) / 9 keeps its weight under the late rule"""
+    from oracle import mask_oracle as mo
+    for N in (10, 19, 37, 1000):
+        r = torch.arange(N)
+        early, late = mo.separation_weights(r, 1000), mo.separation_weights(r, 40000)
+        b = 8 * (N - 1) // 9
+        assert float(early[b]) == float(np.float32(0.90000004)) and float(late[b]) == float(early[b])
+        assert float(late[b - 1]) == float(np.float32(0.1)) and bool((late[b:] == early[b:]).all())
+        assert bool((early[1:] > early[:-1]).all())
+
+
+def test_separation_no_rank_weight_equals_the_late_threshold():
+    """for no N the kernel serves (2 .. 1024) is a rank weight float32(0.9) itself, so `< 0.9` and `<= 0.9` decide alike and
+    the only exact decision of the late rule is the one above, on the kept side"""
+    from oracle import mask_oracle as mo
+    for N in range(2, 1025):
+        assert not bool((mo.separation_weights(torch.arange(N), 1000) == torch.tensor(0.9)).any()), N
