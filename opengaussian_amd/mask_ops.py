@@ -97,22 +97,31 @@ def get_SAM_mask_and_feat(gt_sam_mask, level=3, filter_th=50, original_mask_feat
     return mask_id, masks, invalid_pix
 
 
-class _MaskSums(torch.autograd.Function):
-    """table [N, C+1] of weighted per-mask feature sums | weighted counts.  `for_var`: the call belongs to
-    mask_feature_mean(return_var=True), which is not differentiable."""
+def _membership(masks, device):
+    """(membership tensor, N, form) of a mask argument, as the ogs_{form}_* entry points take it: the int32 label image
+    of a LabelMasks ("label"), or the contiguous uint8 stack of anything else ("mask")"""
+    if isinstance(masks, LabelMasks):
+        m = masks.to(device)
+        return m.labels, m.num_mask, "label"
+    m = _mask_bytes(masks.to(device))
+    return m, int(m.shape[0]), "mask"
+
+
+class _Sums(torch.autograd.Function):
+    """table [N, C+1] of weighted per-mask feature sums | weighted counts (ogs_{form}_feature_sums).  `for_var`: the call
+    belongs to mask_feature_mean(return_var=True), which is not differentiable."""
 
     @staticmethod
-    def forward(ctx, feat_map, masks_u8, weight, for_var):
-        lib = _lib.lib()
+    def forward(ctx, feat_map, member, N, form, weight, for_var):
         f = feat_map.detach().to(torch.float32).contiguous()
         C, H, W = (int(x) for x in f.shape)
-        N = int(masks_u8.shape[0])
         w = None if weight is None else weight.detach().to(torch.float32).reshape(H, W).contiguous()
         table = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)   # 64-byte rows (ogs_mask.h)
-        check(lib.ogs_mask_feature_sums(ptr(f), ptr(masks_u8), ptr(w), C, N, H * W, 0,
-                                        ptr(table), _stream()), "ogs_mask_feature_sums")
-        ctx.save_for_backward(masks_u8, w, f)
+        name = f"ogs_{form}_feature_sums"
+        check(getattr(_lib.lib(), name)(ptr(f), ptr(member), ptr(w), C, N, H * W, 0, ptr(table), _stream()), name)
+        ctx.save_for_backward(member, w, f)
         ctx.shape = (C, H, W, N)
+        ctx.form = form
         ctx.weight_shape = None if weight is None else tuple(weight.shape)
         ctx.for_var = bool(for_var)
         return table[:, :C + 1]
@@ -122,57 +131,19 @@ class _MaskSums(torch.autograd.Function):
         if ctx.for_var:
             raise RuntimeError("mask_feature_mean(return_var=True) is not differentiable here (the reference only "
                                "uses it under no_grad, train.py:689)")
-        masks_u8, w, f = ctx.saved_tensors
+        member, w, f = ctx.saved_tensors
         C, H, W, N = ctx.shape
         # d table[n, c] / d feat[c, pix] = mask * w ;  d table[n, c] / d w[pix] = mask * feat[c, pix] ;
         # d table[n, C] / d w[pix] = mask
         coef = g_table[:, :C].to(torch.float32).contiguous()
-        need_w = w is not None and ctx.needs_input_grad[2]
+        need_w = w is not None and ctx.needs_input_grad[4]
         coef_cnt = g_table[:, C].to(torch.float32).contiguous() if need_w else None
         dfeat = torch.empty(C, H, W, dtype=torch.float32, device=g_table.device)
         dweight = torch.empty(H, W, dtype=torch.float32, device=g_table.device) if need_w else None
-        check(_lib.lib().ogs_mask_feature_sums_backward(ptr(masks_u8), ptr(w), ptr(coef), ptr(f), ptr(coef_cnt), C, N,
-                                                        H * W, ptr(dfeat), ptr(dweight), _stream()),
-              "ogs_mask_feature_sums_backward")
-        return (dfeat if ctx.needs_input_grad[0] else None, None,
-                dweight.reshape(ctx.weight_shape) if need_w else None, None)
-
-
-class _LabelSums(torch.autograd.Function):
-    """_MaskSums over a label image (ogs_label_feature_sums): same table, same saved tensors, same gradients."""
-
-    @staticmethod
-    def forward(ctx, feat_map, labels, num_mask, weight, for_var):
-        lib = _lib.lib()
-        f = feat_map.detach().to(torch.float32).contiguous()
-        C, H, W = (int(x) for x in f.shape)
-        N = int(num_mask)
-        w = None if weight is None else weight.detach().to(torch.float32).reshape(H, W).contiguous()
-        table = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)   # 64-byte rows (ogs_mask.h)
-        check(lib.ogs_label_feature_sums(ptr(f), ptr(labels), ptr(w), C, N, H * W, 0,
-                                         ptr(table), _stream()), "ogs_label_feature_sums")
-        ctx.save_for_backward(labels, w, f)
-        ctx.shape = (C, H, W, N)
-        ctx.weight_shape = None if weight is None else tuple(weight.shape)
-        ctx.for_var = bool(for_var)
-        return table[:, :C + 1]
-
-    @staticmethod
-    def backward(ctx, g_table):
-        if ctx.for_var:
-            raise RuntimeError("mask_feature_mean(return_var=True) is not differentiable here (the reference only "
-                               "uses it under no_grad, train.py:689)")
-        labels, w, f = ctx.saved_tensors
-        C, H, W, N = ctx.shape
-        coef = g_table[:, :C].to(torch.float32).contiguous()
-        need_w = w is not None and ctx.needs_input_grad[3]
-        coef_cnt = g_table[:, C].to(torch.float32).contiguous() if need_w else None
-        dfeat = torch.empty(C, H, W, dtype=torch.float32, device=g_table.device)
-        dweight = torch.empty(H, W, dtype=torch.float32, device=g_table.device) if need_w else None
-        check(_lib.lib().ogs_label_feature_sums_backward(ptr(labels), ptr(w), ptr(coef), ptr(f), ptr(coef_cnt), C, N,
-                                                         H * W, ptr(dfeat), ptr(dweight), _stream()),
-              "ogs_label_feature_sums_backward")
-        return (dfeat if ctx.needs_input_grad[0] else None, None, None,
+        name = f"ogs_{ctx.form}_feature_sums_backward"
+        check(getattr(_lib.lib(), name)(ptr(member), ptr(w), ptr(coef), ptr(f), ptr(coef_cnt), C, N, H * W, ptr(dfeat),
+                                        ptr(dweight), _stream()), name)
+        return (dfeat if ctx.needs_input_grad[0] else None, None, None, None,
                 dweight.reshape(ctx.weight_shape) if need_w else None, None)
 
 
@@ -183,18 +154,14 @@ def mask_feature_mean(feat_map, gt_masks, image_mask=None, return_var=False):
     (mean [N,C], variance [N], pixel count [N]) as the reference."""
     _need_gpu(feat_map, "feat_map")
     C, H, W = (int(x) for x in feat_map.shape)
-    labelled = isinstance(gt_masks, LabelMasks)
-    m = gt_masks.to(feat_map.device) if labelled else _mask_bytes(gt_masks.to(feat_map.device))
-    if tuple(m.shape[1:]) != (H, W):
+    if tuple(gt_masks.shape[1:]) != (H, W):
         raise RuntimeError(f"gt_masks must be [num_mask, {H}, {W}], got {tuple(gt_masks.shape)}")
+    member, N, form = _membership(gt_masks, feat_map.device)
     if image_mask is not None:
         if image_mask.numel() != H * W:
             raise RuntimeError(f"image_mask must have H*W = {H * W} elements, got {tuple(image_mask.shape)}")
         image_mask = image_mask.to(feat_map.device)
-    if labelled:
-        table = _LabelSums.apply(feat_map, m.labels, m.num_mask, image_mask, bool(return_var))
-    else:
-        table = _MaskSums.apply(feat_map, m, image_mask, bool(return_var))
+    table = _Sums.apply(feat_map, member, N, form, image_mask, bool(return_var))
     counts = table[:, C].clamp(min=1)
     mean = table[:, :C] / counts[:, None]
     if not return_var:
@@ -206,85 +173,47 @@ def mask_feature_mean(feat_map, gt_masks, image_mask=None, return_var=False):
     f = feat_map.detach().to(torch.float32).contiguous()
     w = None if image_mask is None else image_mask.detach().to(torch.float32).reshape(H, W).contiguous()
     mu = mean.detach().contiguous()
-    N = int(mu.shape[0])
     sq = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)
-    if labelled:
-        check(_lib.lib().ogs_label_feature_sqdev(ptr(f), ptr(m.labels), ptr(w), ptr(mu), C, N, H * W, ptr(sq), _stream()),
-              "ogs_label_feature_sqdev")
-    else:
-        check(_lib.lib().ogs_mask_feature_sqdev(ptr(f), ptr(m), ptr(w), ptr(mu), C, N, H * W, ptr(sq), _stream()),
-              "ogs_mask_feature_sqdev")
+    name = f"ogs_{form}_feature_sqdev"
+    check(getattr(_lib.lib(), name)(ptr(f), ptr(member), ptr(w), ptr(mu), C, N, H * W, ptr(sq), _stream()), name)
     return mean, (sq[:, :C] / counts[:, None]).mean(dim=1), counts
 
 
 class _Cohesion(torch.autograd.Function):
+    """mean over the masks of the mean distance to the mask's mean (ogs_{form}_cohesion)"""
+
     @staticmethod
-    def forward(ctx, feat_map, masks_u8, mean):
-        lib = _lib.lib()
+    def forward(ctx, feat_map, member, N, form, mean):
         f = feat_map.detach().to(torch.float32).contiguous()
         mu = mean.detach().to(torch.float32).contiguous()
         C, H, W = (int(x) for x in f.shape)
-        N = int(masks_u8.shape[0])
         table = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)
-        check(lib.ogs_mask_cohesion(ptr(f), ptr(masks_u8), ptr(mu), C, N, H * W, ptr(table), _stream()),
-              "ogs_mask_cohesion")
+        name = f"ogs_{form}_cohesion"
+        check(getattr(_lib.lib(), name)(ptr(f), ptr(member), ptr(mu), C, N, H * W, ptr(table), _stream()), name)
         cnt = table[:, 1].clamp(min=1)
-        ctx.save_for_backward(f, masks_u8, mu, cnt)
+        ctx.save_for_backward(f, member, mu, cnt)
+        ctx.num_mask, ctx.form = N, form
         return (table[:, 0] / cnt).mean() if N > 0 else table.sum()
 
     @staticmethod
     def backward(ctx, g):
-        f, masks_u8, mu, cnt = ctx.saved_tensors
-        C, H, W = (int(x) for x in f.shape)
-        N = int(masks_u8.shape[0])
-        gl = (g.to(torch.float32) / (max(N, 1) * cnt)).contiguous()
-        dfeat = torch.empty(C, H, W, dtype=torch.float32, device=f.device)
-        dmean = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)
-        check(_lib.lib().ogs_mask_cohesion_backward(ptr(f), ptr(masks_u8), ptr(mu), ptr(gl), C, N, H * W, ptr(dfeat),
-                                                    ptr(dmean), _stream()), "ogs_mask_cohesion_backward")
-        return dfeat, None, dmean[:, :C]
-
-
-class _LabelCohesion(torch.autograd.Function):
-    """_Cohesion over a label image (ogs_label_cohesion)."""
-
-    @staticmethod
-    def forward(ctx, feat_map, labels, num_mask, mean):
-        lib = _lib.lib()
-        f = feat_map.detach().to(torch.float32).contiguous()
-        mu = mean.detach().to(torch.float32).contiguous()
-        C, H, W = (int(x) for x in f.shape)
-        N = int(num_mask)
-        table = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)
-        check(lib.ogs_label_cohesion(ptr(f), ptr(labels), ptr(mu), C, N, H * W, ptr(table), _stream()),
-              "ogs_label_cohesion")
-        cnt = table[:, 1].clamp(min=1)
-        ctx.save_for_backward(f, labels, mu, cnt)
-        ctx.num_mask = N
-        return (table[:, 0] / cnt).mean() if N > 0 else table.sum()
-
-    @staticmethod
-    def backward(ctx, g):
-        f, labels, mu, cnt = ctx.saved_tensors
+        f, member, mu, cnt = ctx.saved_tensors
         C, H, W = (int(x) for x in f.shape)
         N = ctx.num_mask
         gl = (g.to(torch.float32) / (max(N, 1) * cnt)).contiguous()
         dfeat = torch.empty(C, H, W, dtype=torch.float32, device=f.device)
         dmean = torch.empty(N, TABLE_STRIDE, dtype=torch.float32, device=f.device)
-        check(_lib.lib().ogs_label_cohesion_backward(ptr(f), ptr(labels), ptr(mu), ptr(gl), C, N, H * W, ptr(dfeat),
-                                                     ptr(dmean), _stream()), "ogs_label_cohesion_backward")
-        return dfeat, None, None, dmean[:, :C]
+        name = f"ogs_{ctx.form}_cohesion_backward"
+        check(getattr(_lib.lib(), name)(ptr(f), ptr(member), ptr(mu), ptr(gl), C, N, H * W, ptr(dfeat), ptr(dmean),
+                                        _stream()), name)
+        return dfeat, None, None, None, dmean[:, :C]
 
 
 def cohesion_loss(feat_map, gt_mask, feat_mean_stack):
     """Intra-mask smoothing loss, Eq. (1) of the paper (train.py:102-122): mean over masks of the mean L2 distance
     between the pixels of a mask and that mask's mean feature."""
     _need_gpu(feat_map, "feat_map")
-    if isinstance(gt_mask, LabelMasks):
-        m = gt_mask.to(feat_map.device)
-        return _LabelCohesion.apply(feat_map, m.labels, m.num_mask, feat_mean_stack)
-    m = _mask_bytes(gt_mask.to(feat_map.device))
-    return _Cohesion.apply(feat_map, m, feat_mean_stack)
+    return _Cohesion.apply(feat_map, *_membership(gt_mask, feat_map.device), feat_mean_stack)
 
 
 class _Separation(torch.autograd.Function):

@@ -293,3 +293,40 @@ def test_variance_of_smooth_features(gpu_device, levels):
               f"device, two calls {[e.tolist() for e in errs]}")
         for e in errs:
             assert float(e.max()) <= BAR
+
+
+# ---- the raw second moments of the C ABI -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("weighted", [False, True], ids=["plain", "weighted"])
+@pytest.mark.parametrize("C", [3, 6])
+@pytest.mark.parametrize("HW", [257, 1025, 1028])
+def test_feature_sums_with_squares(gpu_device, HW, C, weighted):
+    """ogs_mask_feature_sums / ogs_label_feature_sums with with_squares = 1 (no caller in the package passes it; the one-pass
+    variance of scripts/mask_bench.py --variance does): row n = sum w f[c] | sum w | sum w f[c]^2 over the pixels of mask n,
+    all 2C + 1 columns against float64 on the same inputs.  257: two waves; 1025: two workgroups on the scalar path; 1028:
+    two on the vector path; N = 9 disjoint masks, one past the stack walk's unroll of 8.  The bound of a row is the worst
+    case of ANY order of summing its n_pix terms in fp32 -- n_pix - 1 additions and the two roundings of w * f * f:
+    (n_pix + 2) * 2^-24 * sum |term|."""
+    from opengaussian_amd import _lib, mask_ops as mk
+    H, W = SHAPES[HW]
+    N = 9
+    g = torch.Generator().manual_seed(4000 + 35 * HW + C)
+    feat = torch.rand(C, H, W, generator=g) * 2 - 1
+    sil = torch.rand(H, W, generator=g) * 0.9 + 0.05 if weighted else None
+    labels = torch.randint(0, N + 1, (H, W), generator=g, dtype=torch.int32)       # 0: in no mask
+    stack = torch.stack([labels == n + 1 for n in range(N)])
+    f64 = feat.double().flatten(1)                                                 # [C, HW]
+    w64 = (torch.ones(HW, dtype=torch.float64) if sil is None else sil.double().flatten())
+    terms = torch.cat([w64 * f64, w64[None], w64 * f64 * f64])                     # [2C+1, HW], the table's column order
+    member = stack.flatten(1).double()                                             # [N, HW]
+    want = member @ terms.t()                                                      # [N, 2C+1]
+    bound = (member.sum(1, keepdim=True) + 2) * 2.0 ** -24 * (member @ terms.abs().t())
+    fg, wg = feat.to(gpu_device), None if sil is None else sil.to(gpu_device)
+    lib, ptr = _lib.lib(), _lib.ptr
+    for name, m in (("ogs_mask_feature_sums", stack.to(gpu_device).view(torch.uint8)),
+                    ("ogs_label_feature_sums", labels.to(gpu_device))):
+        table = torch.full((N, mk.TABLE_STRIDE), float("nan"), device=gpu_device)
+        _lib.check(getattr(lib, name)(ptr(fg), ptr(m), ptr(wg), C, N, HW, 1, ptr(table),
+                                      torch.cuda.current_stream().cuda_stream), name)
+        err = (table[:, :2 * C + 1].double().cpu() - want).abs()
+        print(f"{name} HW={HW} C={C} weighted={weighted}: worst error / bound {float((err / bound.clamp_min(1e-300)).max()):.3f}")
+        assert bool((err <= bound).all()), (name, err, bound)

@@ -1,6 +1,6 @@
 """CPU: mask_ops.get_SAM_mask_and_feat / LabelMasks against tests/golden/sam_labels_golden.npz (the reference's own
 get_SAM_mask_and_feat run on the CPU, tests/golden/make_sam_labels_golden.py), everything exact; the label path of the
-loss functions refuses CPU tensors like the stack path; the four label entry points are part of the C ABI."""
+loss functions refuses CPU tensors like the stack path; the five label entry points are part of the C ABI."""
 import os
 
 import numpy as np
@@ -11,7 +11,7 @@ from tests.golden.make_sam_labels_golden import CASES, LEVELS, case_id, case_inp
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "sam_labels_golden.npz"))
 LABEL_SYMBOLS = ("ogs_label_feature_sums", "ogs_label_feature_sums_backward", "ogs_label_cohesion",
-                 "ogs_label_cohesion_backward")
+                 "ogs_label_cohesion_backward", "ogs_label_feature_sqdev")
 
 
 @pytest.mark.parametrize("level", LEVELS)
