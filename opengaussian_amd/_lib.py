@@ -149,6 +149,8 @@ SIGNATURES = {
     "ogs_loss_masked_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp]),
     "ogs_loss_masked_backward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp,
                                            _vp]),
+    "ogs_knn_tile_points": (C.c_size_t, []),
+    "ogs_knn_group_ksum": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

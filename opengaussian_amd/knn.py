@@ -1,0 +1,140 @@
+"""Exact k-nearest-distance sums on the GPU (include/ogs_knn.h) and the two things the reference builds on them.
+
+``outlier_mask``  the keep-mask of render()'s ``post_process`` block (gaussian_renderer/__init__.py:292-309) and of
+                  scripts/render_by_click.py:170-189 (``k_scale=2, std_weight=0.1``); there ``pytorch3d.ops.knn_points``.
+``distCUDA2``     drop-in for ``simple_knn._C.distCUDA2`` / the scipy KDTree form of scene/gaussian_model.py:28-36.
+``group_ksum``    the raw call: per row, the K-th smallest squared distance inside the row's group and the fp64 sums of the
+                  K smallest and of their squares.
+
+All groups go through one launch; nothing here reads a value back from the device, and no n x n or n x K buffer exists.
+CPU tensors raise: there is no CPU path.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+from ._lib import check, ptr
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _need_gpu(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must live on the GPU (got {t.device}); the k-nearest-distance kernel has no CPU path")
+
+
+def isqrt(n: torch.Tensor) -> torch.Tensor:
+    """floor(sqrt(n)) of an integer tensor, exact: the fp64 root, then one integer correction step either way
+    (``int(n ** 0.5)`` of the reference at every n a group can have)."""
+    n = n.to(torch.int64)
+    r = torch.sqrt(n.to(torch.float64)).to(torch.int64)
+    r = torch.where(r * r > n, r - 1, r)
+    return torch.where((r + 1) * (r + 1) <= n, r + 1, r)
+
+
+def _ksum_sorted(points, group, num_groups, k, want_kth=True):
+    """The launch, in GROUP-SORTED row order.  Returns (order, gid, begin, k, kth, sum1, sum2): sorted row r is the
+    caller's row order[r] (None: identity) and lies in group gid[r] (-1: none; None: all in group 0); begin [G + 1] int64
+    row offsets, k [G] int32 as handed to the kernel; kth is None unless wanted."""
+    _need_gpu(points, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [n, 3], got {tuple(points.shape)}")
+    n, dev, G = points.shape[0], points.device, int(num_groups)
+    pts = points.detach().to(torch.float32).contiguous()
+    if group is None:
+        if G != 1:
+            raise ValueError("group=None means one group")
+        order = gid = None
+        begin = torch.tensor([0, n], dtype=torch.int64, device=dev)
+    else:
+        _need_gpu(group, "group")
+        if group.shape != (n,):
+            raise ValueError(f"group must be [{n}], got {tuple(group.shape)}")
+        key = torch.where((group < 0) | (group >= G), -1, group).to(torch.int32)
+        gid, order = torch.sort(key, stable=True)                   # rows of no group first, then group by group
+        del key
+        pts = pts[order]
+        # begin[g] = sorted rows with a key below g (torch.bincount would read its bin count back to the host)
+        begin = torch.searchsorted(gid, torch.arange(G + 1, dtype=torch.int32, device=dev))
+    if callable(k):
+        kk = k(begin[1:] - begin[:-1])
+    elif isinstance(k, torch.Tensor):
+        kk = k.to(dev)
+    else:
+        kk = torch.full((G,), int(k), dtype=torch.int64, device=dev)
+    kk = kk.to(torch.int32).contiguous()
+    if kk.shape != (G,):
+        raise ValueError(f"k must be a number or [{G}] values")
+    begin32 = begin.to(torch.int32)
+    kth = torch.zeros(n, dtype=torch.float32, device=dev) if want_kth else None
+    sum1 = torch.zeros(n, dtype=torch.float64, device=dev)
+    sum2 = torch.zeros(n, dtype=torch.float64, device=dev)
+    check(_lib.lib().ogs_knn_group_ksum(n, ptr(pts), G, ptr(begin32), ptr(kk), ptr(kth), ptr(sum1), ptr(sum2), _stream()),
+          "ogs_knn_group_ksum")
+    return order, gid, begin, kk, kth, sum1, sum2
+
+
+def _unsort(t, order):
+    if order is None:
+        return t
+    out = torch.empty_like(t)
+    out[order] = t
+    return out
+
+
+def group_ksum(points: torch.Tensor, group, num_groups: int, k):
+    """(kth [n] fp32, sum1 [n] fp64, sum2 [n] fp64) in the caller's row order.
+
+    points [n, 3]; group [n] integer ids (rows with an id < 0 or >= num_groups belong to no group and get zeros), or None
+    for one group of all rows; k: one K for all groups, a [num_groups] tensor, or a function of the group sizes.  K is
+    clamped to the group's size.  Distances are fp32 ``(dx*dx + dy*dy) + dz*dz`` over the whole group, the row itself
+    included; ties at the K-th value are counted exactly; two identical calls give the same bits."""
+    order, _, _, _, kth, sum1, sum2 = _ksum_sorted(points, group, num_groups, k)
+    return _unsort(kth, order), _unsort(sum1, order), _unsort(sum2, order)
+
+
+def outlier_mask(points: torch.Tensor, group=None, num_groups: int = 1, k_scale: int = 1, std_weight: float = 1.0):
+    """Keep-mask [n] of the reference's kNN outlier filter, every group filtered on its own, in one launch.
+
+    Per group of n_g rows: K = int(n_g ** 0.5) * k_scale (clamped to n_g), a row's value is the mean of its K smallest
+    squared distances (itself included), and the row is kept when that lies below mean + std_weight * std over ALL n_g * K
+    values of the group (unbiased std, as ``Tensor.std()``).  Rows of no group are not kept.  A group of one row has
+    std = nan and keeps nothing, as in the reference; so does a group whose K nearest distances are all zero.
+
+    Mean and std come from the fp64 totals S1 = sum of values, S2 = sum of squares: var = (S2 - S1^2 / N) / (N - 1).
+    That form cancels: its relative error is about 1e-16 * mean^2 / var, so it has no correct digit left once
+    var / mean^2 falls below about 1e-10 -- all n_g * K distances equal to five digits, which distinct points cannot
+    produce (the self-distance 0 is among them).  The group totals are fp64 atomic adds, whose order moves the last bits
+    only."""
+    order, gid, begin, kk, _, sum1, sum2 = _ksum_sorted(points, group, num_groups,
+                                                        lambda sizes: isqrt(sizes) * int(k_scale), want_kth=False)
+    G, dev = int(num_groups), points.device
+    sizes = begin[1:] - begin[:-1]
+    kd = torch.minimum(kk.to(torch.int64), sizes).to(torch.float64)                # the K the kernel used
+    N = sizes.to(torch.float64) * kd
+    if gid is None:
+        S1, S2 = sum1.sum().reshape(1), sum2.sum().reshape(1)
+    else:
+        slot = gid + 1                                                             # slot 0 collects the rows of no group
+        S1 = torch.zeros(G + 1, dtype=torch.float64, device=dev).index_add_(0, slot, sum1)[1:]
+        S2 = torch.zeros(G + 1, dtype=torch.float64, device=dev).index_add_(0, slot, sum2)[1:]
+    del sum2
+    mean = S1 / N
+    std = torch.sqrt(torch.clamp_min((S2 - S1 * S1 / N) / (N - 1.0), 0.0))         # 0 / 0 = nan stays nan
+    limit = mean + float(std_weight) * std
+    if gid is None:
+        return sum1 / kd < limit
+    nan = torch.full((1,), float("nan"), dtype=torch.float64, device=dev)          # slot 0: nothing is below nan
+    row_mean = sum1.div_(torch.cat((nan, kd)).index_select(0, slot))
+    keep = row_mean < torch.cat((nan, limit)).index_select(0, slot)
+    return _unsort(keep, order)
+
+
+def distCUDA2(points: torch.Tensor) -> torch.Tensor:
+    """Mean squared distance to the three nearest OTHER points, fp32 [n] in the input's order: the 4 smallest squared
+    distances with the row itself (0) among them, summed, over 3.  The caller keeps its own ``clamp_min``."""
+    _, _, _, _, _, sum1, _ = _ksum_sorted(points, None, 1, 4, want_kth=False)
+    return (sum1 / 3.0).to(torch.float32)

@@ -21,6 +21,7 @@ import math
 
 import torch
 
+from . import knn as _knn
 from . import rasterizer as _rasterizer
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_fused, rasterize_groups
 
@@ -56,7 +57,10 @@ def eval_sh(deg, sh, dirs):
 
 def _knn_mean_filter(points: torch.Tensor) -> torch.Tensor:
     """Outlier mask of the `post_process` branch (:293-309): mean squared distance to the K = sqrt(n) nearest
-    neighbours (self included, as pytorch3d.ops.knn_points(x, x) returns it) below mean + std."""
+    neighbours (self included, as pytorch3d.ops.knn_points(x, x) returns it) below mean + std.
+
+    The torch stand-in render() used before knn.outlier_mask (an n x n distance matrix, one call per leaf): no longer called
+    by render(), kept as the baseline of scripts/knn_filter_bench.py and of the equivalence test."""
     n = points.shape[0]
     K = max(1, int(n ** 0.5))
     # direct differences, as pytorch3d's kernel computes them (the default cdist goes through a matmul for > 25 rows and
@@ -332,10 +336,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, iteration,
             gid = torch.where((scales < 0.1).all(dim=1), gid, none_of(gid))
             cnt = torch.bincount(gid[gid >= 0], minlength=n_sub)
             gid = torch.where((cnt >= 100)[gid.clamp_min(0)], gid, none_of(gid))
-        if post_process:                                                         # per-leaf kNN outlier filter (:297-309)
-            for g_ in torch.unique(gid[gid >= 0]).tolist():
-                rows = torch.nonzero(gid == g_).flatten()
-                gid[rows[~_knn_mean_filter(means3D[rows])]] = -1
+        if post_process:                                      # per-leaf kNN outlier filter (:297-309), all leaves in one launch
+            gid = torch.where(_knn.outlier_mask(means3D, gid, n_sub), gid, none_of(gid))
         kept, imgs, sils = _render_subsets(gid, n_sub, 10, raster_settings, means3D, means2D, opacity, scales, rotations,
                                            cov3D_precomp, colors=None if seg_rgb else ins_feat,
                                            shs=shs if seg_rgb else None, groups_per_pass=per_pass)
