@@ -18,7 +18,7 @@
  * Forward is split in two calls because the size of the per-(Gaussian,tile) list
  * (`num_rendered`) is only known after the geometry phase:
  *
- *   ogs_raster_forward_geometry()  preprocess -> scan                     (A.1, first half of A.2)
+ *   ogs_raster_forward_geometry()  preprocess -> scan (P > 1024, default binning: per-workgroup sums -> offsets)   (A.1, first half of A.2)
  *        -> host learns num_rendered, allocates point_list / binning scratch
  *   ogs_raster_forward_render()    duplicate -> tile sort -> ranges -> per-tile depth sort -> blend   (A.2, A.3)
  *   (grouped passes and P <= 1024 sort the Gaussians by depth in the geometry phase instead of each tile's list)
@@ -104,6 +104,14 @@ typedef struct OgsRasterFwdArgs {
                                   * (images and gradients do not change: those pairs contribute nothing).  != 0: the reference's
                                   * full list (every tile of every footprint rectangle), the unreachable pairs flagged in bit 31
                                   * of point_list.  (Occupies what used to be tail padding: the struct size is unchanged.) */
+    /* Optional (render phase): a range the forward blend zeroes on the way -- the gradient record ogs_raster_backward would
+     * otherwise clear with a fill launch of its own between two kernels that cannot overlap it (128 B per Gaussian, 17 us at
+     * 1 M Gaussians), written here by a kernel that is not bandwidth-bound.  NULL: nothing is cleared.  Non-NULL: 16-byte
+     * aligned, bwd_clear_bytes a multiple of 16; when ogs_raster_forward_render / _deferred returns OGS_OK the range will be
+     * zero in stream order, whatever the pass looks like (an empty list and the passes whose blend does not host the stores
+     * clear it with a fill).  The caller then sets OgsRasterBwdArgs.bwd_tmp_is_clear.  Ignored by every other entry point. */
+    void* bwd_clear;
+    size_t bwd_clear_bytes;
 } OgsRasterFwdArgs;
 
 /* Arguments of the backward pass.  Mirrors upstream rasterize_gaussians_backward(bg, means3D,
@@ -148,7 +156,7 @@ typedef struct OgsRasterBwdArgs {
     const uint32_t* point_list;
     const void* sorted_rec;      /* from forward */
     const void* quad_list;       /* from forward */
-    void* bwd_tmp;               /* ogs_raster_backward_tmp_bytes(P): zeroed by the call.  P * 16 must stay below 2^32 (the blend
+    void* bwd_tmp;               /* ogs_raster_backward_tmp_bytes(P): zeroed by the call (unless bwd_tmp_is_clear).  P * 16 must stay below 2^32 (the blend
                                     kernels address the record array with 32-bit element offsets): P < 2^28 = 268 M Gaussians,
                                     larger P is rejected with OGS_ERR_UNSUPPORTED.  Holds the per-Gaussian gradient
                                     record, 16 fp64 running sums = 128 B (float atomics arrive in a different order every
@@ -169,6 +177,10 @@ typedef struct OgsRasterBwdArgs {
                                     dL_dsh_rgb[p,:] (rank 1), so a data-parallel caller can pass dL_dsh = NULL,
                                     exchange these 3 floats instead of 3*M and rebuild the sum over views with
                                     ogs_sh_grad_from_views().  dL_dmeans3D still includes the view-direction term. */
+    int32_t bwd_tmp_is_clear;    /* != 0: the caller vouches that the bytes of bwd_tmp this pass uses (P * 128, or P * 64 in a
+                                    features-only pass with at most 8 feature sums) are zero already -- OgsRasterFwdArgs.bwd_clear
+                                    of the forward, and nothing wrote them since -- and the call skips its fill.  0: the call
+                                    clears them (the behaviour without this field). */
 } OgsRasterBwdArgs;
 
 int ogs_version(void);

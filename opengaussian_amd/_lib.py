@@ -28,6 +28,7 @@ class OgsRasterFwdArgs(C.Structure):
         ("geom_buffer", _vp), ("geom_tmp", _vp), ("image_buffer", _vp), ("point_list", _vp),
         ("binning_tmp", _vp), ("sorted_rec", _vp), ("quad_list", _vp), ("group_ids", _vp), ("num_groups", C.c_int32),
         ("full_binning", C.c_int32),
+        ("bwd_clear", _vp), ("bwd_clear_bytes", C.c_size_t),
     ]
 
 
@@ -44,6 +45,7 @@ class OgsRasterBwdArgs(C.Structure):
         ("geom_buffer", _vp), ("image_buffer", _vp), ("point_list", _vp), ("sorted_rec", _vp), ("quad_list", _vp), ("bwd_tmp", _vp),
         ("dL_dmeans2D", _vp), ("dL_dcolors", _vp), ("dL_dopacity", _vp), ("dL_dmeans3D", _vp),
         ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dscales", _vp), ("dL_drotations", _vp), ("num_groups", C.c_int32), ("dL_dsh_rgb", _vp),
+        ("bwd_tmp_is_clear", C.c_int32),
     ]
 
 

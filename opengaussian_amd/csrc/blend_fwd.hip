@@ -390,7 +390,11 @@ void pack_blend_chunked_kernel(
     float4* __restrict__ stream, uint32_t* __restrict__ quad_list, uint32_t* __restrict__ qcount, int W, int H, int gx, int tiles,
     const float* __restrict__ bg, float* __restrict__ out_color, float* __restrict__ out_depth, float* __restrict__ out_alpha,
     uint32_t* __restrict__ n_contrib, float* __restrict__ final_T, const uint32_t* __restrict__ tile_order,
-    GroupStatsOut st = GroupStatsOut{}) {
+    uint4* __restrict__ clear, unsigned long long clear_units, GroupStatsOut st = GroupStatsOut{}) {
+    // clear / clear_units (optional, not STATS): a range of 16-byte units this launch zeroes for a later kernel
+    // (OgsRasterFwdArgs.bwd_clear: the gradient record of the backward).  Workgroup b takes slice b of gridDim.x equal slices,
+    // whatever its tile's list looks like, at its exit: stores nothing waits for, in a kernel that is not bandwidth-bound.  (At
+    // workgroup entry, in front of the first gather, the same stores cost the S1M step 0.005 ms more: DESIGN.md section 3d)
     constexpr int NV = rec_vec4(C);
     constexpr int SV = stream_vec4(C);
     constexpr int kListLen = kRowListLen;
@@ -649,6 +653,11 @@ void pack_blend_chunked_kernel(
             out_alpha[pix] = wacc;
             n_contrib[pix] = last;
             final_T[pix] = T;
+        }
+        if (clear != nullptr) {           // kernel-uniform
+            const unsigned long long per = (clear_units + gridDim.x - 1) / gridDim.x;
+            const unsigned long long u0 = min(clear_units, (unsigned long long)blockIdx.x * per), u1 = min(clear_units, u0 + per);
+            for (unsigned long long u = u0 + (unsigned)tid; u < u1; u += kBlock) clear[u] = uint4{0u, 0u, 0u, 0u};
         }
     }
 }
@@ -911,6 +920,10 @@ int launch_c(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& i
     const int gx = (a.W + kTile - 1) / kTile, gy = (a.H + kTile - 1) / kTile;
     const int tiles = gx * gy;
     const unsigned vtiles = (unsigned)tiles * (unsigned)num_groups_of(a.num_groups);
+    // the range the caller wants zeroed (OgsRasterFwdArgs.bwd_clear): stores hosted by the chunked kernel on the ungrouped
+    // streaming path, a fill launch everywhere else
+    const bool host_clear = a.bwd_clear != nullptr && D > 0 && per_tile_depth_order(a);
+    if (a.bwd_clear != nullptr && !host_clear) OGS_HIP_CHECK(hipMemsetAsync(a.bwd_clear, 0, a.bwd_clear_bytes, s));
     if (D > 0) {
         const uint32_t* order = order_ready ? tile_order_of(is, vtiles, a.P) : launch_tile_order(is, vtiles, a.P, s, a.debug);
         static constexpr const char* const kChunked[4] = {"pack_blend_chunked_kernel<3>", "pack_blend_chunked_kernel<6>",
@@ -918,7 +931,8 @@ int launch_c(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& i
         OGS_LAUNCH_NAMED(chan_name<C>(kChunked), pack_blend_chunked_kernel<C>, dim3(vtiles), dim3(kBlock), 0, s,
                          (const uint2*)is.ranges, (const uint32_t*)a.point_list, (const float4*)gs.rec, stream_base<C>(a.sorted_rec),
                          quad_base(a.quad_list), is.qcount, a.W, a.H, gx, tiles, a.bg, a.out_color, a.out_depth, a.out_alpha,
-                         is.n_contrib, is.final_T, order);
+                         is.n_contrib, is.final_T, order, host_clear ? static_cast<uint4*>(a.bwd_clear) : (uint4*)nullptr,
+                         (unsigned long long)(a.bwd_clear_bytes / 16));
         OGS_LAUNCH_CHECK(a.debug, s);
         return OGS_OK;
     }
@@ -960,7 +974,7 @@ int stats_c(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& sa, const GeomSt
     OGS_LAUNCH_NAMED(chan_name<C>(kStats), (pack_blend_chunked_kernel<C, true>), dim3(vtiles), dim3(kBlock), 0, s,
                      (const uint2*)is.ranges, (const uint32_t*)a.point_list, (const float4*)gs.rec, (float4*)nullptr,
                      (uint32_t*)nullptr, (uint32_t*)nullptr, a.W, a.H, gx, tiles, a.bg, (float*)nullptr, (float*)nullptr,
-                     (float*)nullptr, (uint32_t*)nullptr, (float*)nullptr, order, st);
+                     (float*)nullptr, (uint32_t*)nullptr, (float*)nullptr, order, (uint4*)nullptr, 0ull, st);
     OGS_LAUNCH_CHECK(a.debug, s);
     const size_t n = rows * C;
     OGS_LAUNCH(group_stats_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const long long*)fixed,

@@ -149,7 +149,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 403; }
+int ogs_version(void) { return 404; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 
@@ -233,9 +233,13 @@ int ogs_raster_forward_geometry(const OgsRasterFwdArgs* a, void* stream_, int64_
         // no depth sort: duplicate walks the Gaussians in index order and every tile's list is sorted by depth in the render
         // phase (tile_depth_sort_kernel, which gathers keys[0] as preprocess leaves it).  A culled Gaussian has tiles_touched 0,
         // so the scan and duplicate pass over it.  offsets[i] = exclusive scan of tiles_touched; total = num_rendered
+        // (full-list passes; a default pass leaves offsets[] unwritten, see below)
         rc = launch_preprocess(*a, gs, gt, s);
         if (rc != OGS_OK) return rc;
-        rc = exclusive_scan_u32(gt.tiles_touched, nullptr, gt.offsets, a->P, gt.num_rendered, gt.sort_tmp, s, a->debug);
+        // default mode: preprocess left one sum per workgroup, one small launch makes them offsets and the total, and duplicate
+        // scans its own 256 counts (block_sum_offsets); the full-list export keeps the scan
+        rc = block_sum_offsets(*a) ? launch_block_offsets(*a, gt, s)
+                                   : exclusive_scan_u32(gt.tiles_touched, nullptr, gt.offsets, a->P, gt.num_rendered, gt.sort_tmp, s, a->debug);
         if (rc != OGS_OK) return rc;
     } else {
         rc = launch_preprocess(*a, gs, gt, s);
@@ -296,6 +300,9 @@ static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipS
     int rc = validate_fwd(a, stats == nullptr);
     if (rc != OGS_OK) return rc;
     if (!a->image_buffer) { set_error("image_buffer == NULL"); return OGS_ERR_INVALID_ARG; }
+    if (a->bwd_clear && !stats && (((uintptr_t)a->bwd_clear | a->bwd_clear_bytes) & 15u) != 0) {
+        set_error("bwd_clear / bwd_clear_bytes must be multiples of 16"); return OGS_ERR_INVALID_ARG;
+    }
     const int G = num_groups_of(a->num_groups);
     const ImageState is = stats ? ImageState::carve_stats(a->image_buffer, a->W, a->H, G)
                                 : ImageState::carve(a->image_buffer, a->W, a->H, G);
@@ -480,7 +487,8 @@ int ogs_raster_backward(const OgsRasterBwdArgs* a, void* stream_) {
     // features-only pass: a record is the feature sums alone, 64 bytes when they fit (feat_grad_stride) -- half the fill.  (A strided
     // hipMemset2DAsync over the front halves of full-size records cost 0.1 ms against 0.016 ms for a contiguous fill: measured.)
     const int rec_doubles = feat_only ? feat_grad_stride(a->C, a->shs ? 3 : 0) : grad_stride(a->C);
-    OGS_HIP_CHECK(hipMemsetAsync(grad_rec, 0, (size_t)a->P * rec_doubles * sizeof(double), s));
+    // bwd_tmp_is_clear: the forward blend of this pass zeroed the record on its way (OgsRasterFwdArgs.bwd_clear)
+    if (!a->bwd_tmp_is_clear) OGS_HIP_CHECK(hipMemsetAsync(grad_rec, 0, (size_t)a->P * rec_doubles * sizeof(double), s));
     if (a->num_rendered > 0 && (!a->sorted_rec || !a->quad_list)) { set_error("backward: sorted_rec / quad_list == NULL"); return OGS_ERR_INVALID_ARG; }
     int rc = launch_blend_backward(*a, is, grad_rec, s);
     if (rc != OGS_OK) return rc;

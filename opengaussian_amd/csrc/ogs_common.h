@@ -275,12 +275,16 @@ struct GeomTmp {        // transient, but must survive from forward_geometry to 
     uint32_t* keys[2];         // [P] depth bits ping-pong; keys[0] by Gaussian index as preprocess wrote it on the per-tile path
                                // (per_tile_depth_order: nothing sorts it, tile_depth_sort_kernel gathers from it)
     uint32_t* order[2];        // [P] Gaussian ids ping-pong; order[0] holds the depth order at the end (depth-sorted paths only)
-    uint32_t* offsets;         // [P] exclusive scan of tiles_touched in the order duplicate walks (index or depth order)
+    uint32_t* offsets;         // [P] exclusive scan of tiles_touched in the order duplicate walks (index or depth order); not
+                               // written by a pass that takes its offsets from block_sum (block_sum_offsets)
     uint32_t* num_rendered;    // [64] word 0: num_rendered; word 1 (`visible()`, depth-sorted paths only): Gaussians in the depth
                                // order -- the culled ones (key kDropKey: behind the near plane, outside every group, empty tile
                                // rect) leave the depth sort in its first pass, so the later passes, the scan and duplicate only
                                // see what is drawn
     void* sort_tmp;
+    uint32_t* block_sum;       // [ceil(P / kBlock)] block-sum scheme (block_sum_offsets): preprocess leaves the sum of tiles_touched
+                               // of each of its workgroups here, block_offsets_kernel turns the sums into their exclusive prefix
+                               // in place, and the workgroup of duplicate_kernel with the same index starts its range there
     uint32_t* visible() const { return num_rendered + 1; }
     static GeomTmp carve(void* p, int P) {
         Carver c(p);
@@ -293,6 +297,7 @@ struct GeomTmp {        // transient, but must survive from forward_geometry to 
         g.offsets = c.take<uint32_t>(P);
         g.num_rendered = c.take<uint32_t>(64);
         g.sort_tmp = c.take<char>(sort_tmp_bytes(P));
+        g.block_sum = c.take<uint32_t>((size_t)(P + kBlock - 1) / kBlock);
         return g;
     }
     static size_t bytes(int P) {
@@ -300,6 +305,7 @@ struct GeomTmp {        // transient, but must survive from forward_geometry to 
         for (int i = 0; i < 6; ++i) c.take<uint32_t>(P);
         c.take<uint32_t>(64);
         c.take<char>(sort_tmp_bytes(P));
+        c.take<uint32_t>((size_t)(P + kBlock - 1) / kBlock);
         return c.off;
     }
 };
@@ -330,6 +336,9 @@ struct BinTmp {         // transient, render phase
 
 // kernels launched by capi.hip ------------------------------------------------------------------
 int launch_preprocess(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s);
+// block-sum scheme: gt.block_sum (one sum of tiles_touched per preprocess workgroup) -> exclusive prefix in place, total ->
+// gt.num_rendered[0]; one workgroup
+int launch_block_offsets(const OgsRasterFwdArgs& a, const GeomTmp& gt, hipStream_t s);
 int launch_tiny_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, uint32_t* order, hipStream_t s);
 int launch_small_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s);
 int launch_tiny_blend(const OgsRasterFwdArgs& a, const GeomState& gs, const uint32_t* order, hipStream_t s);
@@ -351,6 +360,11 @@ int launch_tile_ranges(const uint32_t* tile_keys_sorted, int64_t D, uint2* range
 // is sorted by depth on its own (launch_tile_depth_sort).  Grouped passes and the small path keep the depth order of the P
 // Gaussians.  Decided from the arguments alone, so that the geometry and the render phase of a pass agree.
 inline bool per_tile_depth_order(const OgsRasterFwdArgs& a) { return a.num_groups <= 1 && a.P > kSmallMaxP; }
+// The default-mode passes among those need no scan over the P Gaussians either: preprocess_kernel and duplicate_kernel cut the
+// Gaussians into the same 256-wide workgroups, so preprocess leaves one sum of tiles_touched per workgroup, one small launch
+// turns the sums into offsets, and every workgroup of duplicate scans its own 256 counts in LDS.  A full_binning pass (the
+// parity export) keeps the scan and offsets[].  Also decided from the arguments alone.
+inline bool block_sum_offsets(const OgsRasterFwdArgs& a) { return per_tile_depth_order(a) && a.full_binning == 0; }
 // Every tile's segment of point_list into (depth key, id) order in place, keys gathered by id from depth_keys (the 32-bit keys
 // preprocess wrote); workgroup b takes tiles tile_order[4b .. 4b+3] (b.. when NULL).  Lists up to kWaveSortCap entries are sorted by
 // one wave, up to kTileSortCap by the workgroup in LDS; longer ones run their passes through the same positions of `scratch`

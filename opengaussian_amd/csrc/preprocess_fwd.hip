@@ -100,7 +100,7 @@ __device__ __forceinline__ uint32_t preprocess_one(
     const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, const float* __restrict__ viewmatrix,
     const float* __restrict__ projmatrix, const float* __restrict__ campos, float4* __restrict__ rec_row,
     uint32_t* __restrict__ clamped_out, int32_t* __restrict__ radii, uint32_t* __restrict__ tiles_touched,
-    const int32_t* __restrict__ group_ids, int num_groups) {
+    const int32_t* __restrict__ group_ids, int num_groups, uint32_t* touched_ret = nullptr) {
     // rec_row: where this Gaussian's record goes (its row of the record array, or of the workgroup's LDS staging tile)
     constexpr int NV = rec_vec4(C);
     // camera matrices: wave-uniform addresses -> scalar loads
@@ -235,6 +235,7 @@ __device__ __forceinline__ uint32_t preprocess_one(
     clamped_out[idx] = clamped;
     radii[idx] = radius;
     if (tiles_touched) tiles_touched[idx] = touched;
+    if (touched_ret) *touched_ret = touched;
     return ok ? __float_as_uint(depth) : 0xFFFFFFFFu;
 }
 
@@ -247,21 +248,38 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     const float* __restrict__ projmatrix, const float* __restrict__ campos, float4* __restrict__ rec,
     uint32_t* __restrict__ clamped_out, int32_t* __restrict__ radii, uint32_t* __restrict__ tiles_touched,
     uint32_t* __restrict__ depth_keys, uint32_t* __restrict__ order, const int32_t* __restrict__ group_ids,
-    int num_groups) {
+    int num_groups, uint32_t* __restrict__ block_sum) {
     // The workgroup's records are staged in LDS and written as ONE contiguous range: a thread storing its own 48..80-byte
     // record makes every store instruction touch 64 different cache lines.
     constexpr int NV = rec_vec4(C);
     __shared__ float4 s_rec[kBlock * NV];
+    __shared__ uint32_t s_wave_sum[kBlock / kWave];
     const int tid = threadIdx.x;
     const int idx = blockIdx.x * kBlock + tid;
+    uint32_t touched = 0;
     if (idx < P) {
         depth_keys[idx] = preprocess_one<C>(idx, W, H, sh_degree, sh_coeffs, tanfovx, tanfovy, focal_x, focal_y, scale_modifier,
                                             means3D, colors_precomp, shs, opacities, scales, rotations, cov3D_precomp, viewmatrix,
                                             projmatrix, campos, s_rec + tid * NV, clamped_out, radii, tiles_touched, group_ids,
-                                            num_groups);
+                                            num_groups, &touched);
         if (order) order[idx] = (uint32_t)idx;          // the start of the global depth sort (grouped passes only)
     }
+    // block-sum scheme (block_sum_offsets): this workgroup's sum of tiles_touched, the share of the scan that duplicate_kernel's
+    // workgroup of the same index cannot form itself.  Wave reduction, then the four wave sums through LDS behind the barrier
+    // the record staging needs anyway
+    if (block_sum != nullptr) {           // kernel-uniform
+        uint32_t t = touched;
+#pragma unroll
+        for (int d = kWave / 2; d >= 1; d >>= 1) t += __shfl_down(t, d, kWave);
+        if ((tid & (kWave - 1)) == 0) s_wave_sum[tid / kWave] = t;
+    }
     __syncthreads();
+    if (block_sum != nullptr && tid == 0) {
+        uint32_t t = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) t += s_wave_sum[w];
+        block_sum[blockIdx.x] = t;
+    }
     const size_t row0 = (size_t)blockIdx.x * kBlock;
     const int n4 = min(kBlock, P - (int)row0) * NV;
     float4* __restrict__ out = rec + row0 * NV;
@@ -369,6 +387,8 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
                                                            const float4* __restrict__ rec,
                                                            const uint32_t* __restrict__ order,
                                                            const uint32_t* __restrict__ offsets,
+                                                           const uint32_t* __restrict__ tiles_touched,
+                                                           const uint32_t* __restrict__ block_base,
                                                            uint32_t* __restrict__ tile_keys,
                                                            uint32_t* __restrict__ vals, uint32_t capacity,
                                                            const int32_t* __restrict__ group_ids, bool drop_unreachable,
@@ -385,6 +405,11 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
     // thread -- perfectly coalesced 4-byte stores -- and finds the owning Gaussian of a slot by binary search in
     // LDS.  (One thread per Gaussian looping over its own tiles wrote 64 scattered dwords per store instruction
     // and ran as long as the wave's largest footprint: 121 us instead of ~35 us at S1M-1080p.)
+    //
+    // Where the range starts: offsets[] (the scan of the geometry phase, in the order of this walk), or -- block_base != NULL,
+    // index order only (block_sum_offsets) -- block_base[blockIdx.x], the exclusive prefix of the sums preprocess_kernel's
+    // workgroups left, plus the exclusive prefix of this workgroup's own 256 tiles_touched, scanned here.
+    __shared__ uint32_t s_wave_sum[kBlock / kWave];
     __shared__ uint32_t s_off[kBlock];      // output offset relative to the workgroup's first slot
     __shared__ uint32_t s_gid[kBlock];
     __shared__ uint32_t s_rect[kBlock];     // rminx | rminy << 12 | width << 24   (grids up to 4095 tiles a side)
@@ -403,12 +428,14 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
     const int P = n_visible ? min(P_cap, (int)*n_visible) : P_cap;
     if ((int)blockIdx.x * kBlock >= P) return;            // block-uniform
     const int gx = (W + kTile - 1) / kTile, gy = (H + kTile - 1) / kTile;
-    uint32_t off = 0, cnt = 0, gid = 0, rect = 1u << 24, key0 = 0;
+    uint32_t off = 0, cnt = 0, gid = 0, rect = 1u << 24, key0 = 0, touched = 0;
     float4 ctr = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 con = make_float4(1.f, 1.f, 0.f, 0.f);
+    int wide_x0 = 0, wide_x1 = 0, wide_y0 = 0, wide_y1 = 0;      // tile rect of a footprint wider than 255 tiles (else empty)
     if (r < P) {
         gid = order ? order[r] : (uint32_t)r;
-        off = offsets[r];
+        if (block_base != nullptr) touched = tiles_touched[r];
+        else off = offsets[r];
         // culled Gaussians (radius 0) may carry any group id: they emit nothing
         if (group_ids != nullptr) key0 = (uint32_t)max(group_ids[gid], 0) * (uint32_t)(gx * gy);
         const float4 a = rec[(size_t)gid * NV];
@@ -432,23 +459,43 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
                 cnt = (uint32_t)(w * h);
                 // width field is 8 bits: wider footprints (> 255 tiles = 4080 px) keep the per-thread loop below
                 rect = (uint32_t)rminx | ((uint32_t)rminy << 12) | ((uint32_t)min(w, 255) << 24);
-                if (w > 255) {
-                    uint32_t o = off;
-                    for (int ty = rminy; ty < rmaxy; ++ty)
-                        for (int tx = rminx; tx < rmaxx; ++tx) {
-                            // footprints wider than 4080 px: flagged without a test (pack tests the quadrants)
-                            if (o < capacity) { tile_keys[o] = key0 + (uint32_t)(ty * gx + tx); vals[o] = gid | (1u << kReachBit); }
-                            ++o;
-                        }
-                    rect |= 0u;            // slots of this Gaussian are skipped in the cooperative walk (marked below)
-                    gid |= 0x80000000u;    // P < 2^31: the top bit is free
-                }
+                if (w > 255) { wide_x0 = rminx; wide_x1 = rmaxx; wide_y0 = rminy; wide_y1 = rmaxy; }
             }
         }
     }
-    if (tid == 0) s_first = off;
+    uint32_t before = 0;                   // block_base: tiles_touched of the workgroup's Gaussians in front of this one
+    if (block_base != nullptr) {           // kernel-uniform
+        const int lane = tid & (kWave - 1);
+        uint32_t incl = touched;
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const uint32_t o = __shfl_up(incl, d, kWave);
+            if (lane >= d) incl += o;
+        }
+        if (lane == kWave - 1) s_wave_sum[tid / kWave] = incl;
+        before = incl - touched;
+        if (tid == 0) s_first = block_base[blockIdx.x];
+    } else if (tid == 0) {
+        s_first = off;
+    }
     __syncthreads();
     const uint32_t first = s_first;
+    if (block_base != nullptr) {
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w)
+            if (w < tid / kWave) before += s_wave_sum[w];
+        off = first + before;
+    }
+    if (wide_x1 > wide_x0) {
+        uint32_t o = off;
+        for (int ty = wide_y0; ty < wide_y1; ++ty)
+            for (int tx = wide_x0; tx < wide_x1; ++tx) {
+                // footprints wider than 4080 px: flagged without a test (pack tests the quadrants)
+                if (o < capacity) { tile_keys[o] = key0 + (uint32_t)(ty * gx + tx); vals[o] = gid | (1u << kReachBit); }
+                ++o;
+            }
+        gid |= 0x80000000u;    // P < 2^31: the top bit is free; the cooperative walk below skips this Gaussian's slots
+    }
     // Gaussians past P (last workgroup) sit at the end of the range with zero slots
     s_off[tid] = (r < P) ? off - first : 0xFFFFFFFFu;
     s_gid[tid] = gid;
@@ -491,6 +538,56 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
     }
 }
 
+// Block-sum scheme: the sums preprocess_kernel's workgroups left (nb = ceil(P / 256) words, a few KB) into their exclusive prefix,
+// in place, and their total into num_rendered[0] -- what is left of the scan over the P Gaussians.  One workgroup of 1024
+// threads, 8192 sums (2 M Gaussians) per trip: coalesced loads into LDS, all in flight at once (a thread walking its own run
+// through global memory waited for one load after the other: 6.4 us for 3 907 sums), eight sums per thread from there, wave
+// scan, sixteen wave totals.  32-bit sums, as the scan's (num_rendered >= 2^31 is refused by the render phase).
+constexpr int kOffsThreads = 1024, kOffsItems = 8, kOffsChunk = kOffsThreads * kOffsItems;
+__global__ __launch_bounds__(kOffsThreads) void block_offsets_kernel(uint32_t* __restrict__ block_sum, int nb,
+                                                                     uint32_t* __restrict__ total_out) {
+    __shared__ uint32_t s_val[kOffsChunk];
+    __shared__ uint32_t s_wave_sum[kOffsThreads / kWave];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    uint32_t carry = 0;
+    for (int c0 = 0; c0 < nb; c0 += kOffsChunk) {
+        const int n = min(kOffsChunk, nb - c0);
+#pragma unroll
+        for (int k = 0; k < kOffsItems; ++k) {
+            const int e = k * kOffsThreads + tid;
+            s_val[e] = e < n ? block_sum[c0 + e] : 0u;
+        }
+        __syncthreads();
+        uint32_t v[kOffsItems], sum = 0;
+#pragma unroll
+        for (int k = 0; k < kOffsItems; ++k) { v[k] = s_val[tid * kOffsItems + k]; sum += v[k]; }
+        uint32_t incl = sum;
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const uint32_t o = __shfl_up(incl, d, kWave);
+            if (lane >= d) incl += o;
+        }
+        if (lane == kWave - 1) s_wave_sum[wave] = incl;
+        __syncthreads();
+        uint32_t run = carry + incl - sum, total = 0;
+#pragma unroll
+        for (int w = 0; w < kOffsThreads / kWave; ++w) {
+            const uint32_t t = s_wave_sum[w];
+            if (w < wave) run += t;
+            total += t;
+        }
+#pragma unroll
+        for (int k = 0; k < kOffsItems; ++k) {
+            const int e = tid * kOffsItems + k;
+            if (e < n) block_sum[c0 + e] = run;
+            run += v[k];
+        }
+        carry += total;
+        __syncthreads();                  // s_val and s_wave_sum are rewritten by the next trip
+    }
+    if (tid == 0) total_out[0] = carry;
+}
+
 __global__ __launch_bounds__(kBlock) void mark_visible_kernel(int P, const float* __restrict__ means3D,
                                                               const float* __restrict__ V,
                                                               uint8_t* __restrict__ present) {
@@ -511,7 +608,8 @@ int launch_preprocess_c(const OgsRasterFwdArgs& a, const GeomState& gs, const Ge
                        a.tanfovx, a.tanfovy, focal_x, focal_y, a.scale_modifier, a.means3D, a.colors_precomp, a.shs,
                        a.opacities, a.scales, a.rotations, a.cov3D_precomp, a.viewmatrix, a.projmatrix, a.campos,
                        gs.rec, gs.clamped, a.radii, gt.tiles_touched, gt.keys[0],
-                       per_tile_depth_order(a) ? (uint32_t*)nullptr : gt.order[0], a.num_groups > 1 ? a.group_ids : (const int32_t*)nullptr, a.num_groups);
+                       per_tile_depth_order(a) ? (uint32_t*)nullptr : gt.order[0], a.num_groups > 1 ? a.group_ids : (const int32_t*)nullptr, a.num_groups,
+                       block_sum_offsets(a) ? gt.block_sum : (uint32_t*)nullptr);
     OGS_LAUNCH_CHECK(a.debug, s);
     return OGS_OK;
 }
@@ -571,9 +669,17 @@ int launch_preprocess(const OgsRasterFwdArgs& a, const GeomState& gs, const Geom
     }
 }
 
+int launch_block_offsets(const OgsRasterFwdArgs& a, const GeomTmp& gt, hipStream_t s) {
+    OGS_LAUNCH(block_offsets_kernel, dim3(1), dim3(kOffsThreads), 0, s, gt.block_sum, (a.P + kBlock - 1) / kBlock, gt.num_rendered);
+    OGS_LAUNCH_CHECK(a.debug, s);
+    return OGS_OK;
+}
+
 int launch_duplicate(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, uint32_t* tile_keys,
                      uint32_t* vals, uint32_t capacity, bool drop_unreachable, bool depth_order, hipStream_t s, uint2* zero_ranges,
                      int n_zero) {
+    // as the geometry phase of this pass decided: the ranges start at the block sums' prefix instead of at offsets[]
+    const uint32_t* base = (!depth_order && block_sum_offsets(a)) ? gt.block_sum : nullptr;
     if (n_zero > a.P) { set_error("duplicate: %d ranges to clear with %d threads", n_zero, a.P); return OGS_ERR_INVALID_ARG; }
     const int grid = (a.P + kBlock - 1) / kBlock;
     const int32_t* grp = a.num_groups > 1 ? a.group_ids : nullptr;
@@ -584,9 +690,9 @@ int launch_duplicate(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomT
     const uint32_t* order = depth_order ? gt.order[0] : nullptr;
     const uint32_t* n_visible = depth_order ? gt.visible() : nullptr;
     switch (rec_vec4(a.C)) {
-        case 3: OGS_LAUNCH(duplicate_kernel<3>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
-        case 4: OGS_LAUNCH(duplicate_kernel<4>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
-        case 5: OGS_LAUNCH(duplicate_kernel<5>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
+        case 3: OGS_LAUNCH(duplicate_kernel<3>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, gt.tiles_touched, base, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
+        case 4: OGS_LAUNCH(duplicate_kernel<4>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, gt.tiles_touched, base, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
+        case 5: OGS_LAUNCH(duplicate_kernel<5>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, gt.tiles_touched, base, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
         default: set_error("unsupported record size"); return OGS_ERR_UNSUPPORTED;
     }
     OGS_LAUNCH_CHECK(a.debug, s);

@@ -169,6 +169,23 @@ class full_binning:
         return False
 
 
+# The forward blend zeroes the backward's gradient record on its way (OgsRasterFwdArgs.bwd_clear) instead of a fill launch at the
+# start of ogs_raster_backward.  False withholds the pointer: the backward clears the record itself (A-B runs, tests).
+HOST_BWD_CLEAR = True
+
+
+def _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov) -> int:
+    """Bytes of the gradient record ogs_raster_backward uses (and clears) for the gradient families `need` selects: 64 per
+    Gaussian when only dL/dcolors_precomp of at most 8 channels is produced (features-only pass), else 128 (csrc/ogs_common.h
+    grad_stride / feat_grad_stride; the backward supports Cn <= 9)."""
+    want_cols = bool(need[3]) and cols is not None
+    other = (need[0] or need[1] or (need[2] and shs is not None) or need[4] or (need[5] and scl is not None)
+             or (need[6] and rot is not None) or (need[7] and cov is not None))
+    feat_only = want_cols and not other
+    feat_sums = Cn - (3 if shs is not None else 0)
+    return P * (64 if (feat_only and feat_sums <= 8) else 128)
+
+
 def _fwd_args(rs, P, Cn, m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, color, depth, alpha, radii, group_ids, G):
     a = OgsRasterFwdArgs()
     a.P, a.W, a.H, a.C = P, int(rs.image_width), int(rs.image_height), Cn
@@ -321,6 +338,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         radii = alloc(P, dtype=torch.int32, device=dev)
         ctx.raster_settings = rs
         ctx.P, ctx.Cn, ctx.num_rendered, ctx.tiny = P, Cn, 0, False
+        ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
         ctx.full_binning = bool(FULL_BINNING)
         if P == 0:
             # reference behaviour: zero images, nothing launched (SURVEY.md section 8(b) "Errors")
@@ -343,8 +361,17 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.mark_non_differentiable(radii)
             return color, radii, depth, alpha
 
+        need = ctx.needs_input_grad
+        if HOST_BWD_CLEAR and G == 1 and not rs.debug and any(need[:8]):
+            # the gradient record of this pass' backward: allocated here, zeroed by the render phase on its way, held until the
+            # backward runs.  How much of it the backward uses is known from the requires_grad flags
+            bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
+            a.bwd_clear, a.bwd_clear_bytes = ptr(bwd_tmp), _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov)
         geom, image, point_list, sorted_rec, quad_list, D = _streaming_render(a, dev, lib, rs.debug)
         ctx.num_rendered = D
+        if a.bwd_clear:
+            # every render call of _streaming_render carried the pointer: the range is zero in stream order
+            ctx.bwd_tmp, ctx.bwd_clear_bytes = bwd_tmp, int(a.bwd_clear_bytes)
         ctx.save_for_backward(m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, radii, alpha, geom, image,
                               point_list, sorted_rec, quad_list)
         ctx.mark_non_differentiable(radii)
@@ -402,9 +429,17 @@ class _RasterizeGaussians(torch.autograd.Function):
             gc = torch.zeros(*((ctx.num_groups,) if ctx.num_groups > 1 else ()), Cn, H, W, dtype=torch.float32, device=dev)
         gd = _f32c(grad_depth)
         ga = _f32c(grad_alpha)
-        bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
+        # the record the forward left zeroed, once: after this backward it is dirty, a second backward over a retained graph
+        # takes a fresh buffer and the fill
+        bwd_tmp, is_clear = ctx.bwd_tmp, False
+        if bwd_tmp is not None:
+            is_clear = ctx.bwd_clear_bytes >= _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov)
+            ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
+        else:
+            bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
 
         b = OgsRasterBwdArgs()
+        b.bwd_tmp_is_clear = int(is_clear)
         b.P, b.W, b.H, b.C = P, W, H, Cn
         b.sh_degree = int(rs.sh_degree)
         b.sh_coeffs = 0 if shs is None else int(shs.shape[1])
