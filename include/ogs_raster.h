@@ -352,6 +352,13 @@ int ogs_prof_collect(char* buf, size_t n);
 /* Test hook, not part of the reference boundary: runs the wave64 16-slot transposed reduction (mask reductions,
  * include/ogs_mask.h) on in[64][16]; out[lane] = sum over lanes of slot (lane >> 2). */
 int ogs_selftest_wave_fold16(const float* in, float* out, void* stream);
+/* Test hook: the accumulation step of the forward blend's walk as a matrix instruction (not used by the kernels: DESIGN.md section 3e).
+ * One wave chains `steps` updates  acc[b][i][j] += w[t][16 b + i] * f[t][16 b + j]  (b < 4 blocks, i < 16 pixels, j < 16
+ * channels; w, f: [steps][64]) starting from acc0 [4][16][16], once with the 4-block K = 1 fp32 MFMA (out_mfma, through the
+ * accumulator layout written down in csrc/blend_fwd.hip) and once as one fmaf per element and step (out_fma).  The two must be
+ * equal bit for bit. */
+int ogs_selftest_mfma_rank1(const float* w, const float* f, const float* acc0, int32_t steps, float* out_mfma, float* out_fma,
+                            void* stream);
 /* Test hook: the heaviest-first workgroup order of the pack / blend kernels for tile ranges[vtiles][2] (start, end):
  * order[vtiles] = a permutation of the tiles, non-increasing in the length class of their lists -- or the identity
  * when the longest list is at most twice the mean (and for more than 65536 tiles). */

@@ -98,6 +98,7 @@ SIGNATURES = {
     "ogs_sh_grad_from_views": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "ogs_raster_export_binning": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.c_int64, _vp, _vp, _vp, _vp]),
     "ogs_selftest_wave_fold16": (C.c_int, [_vp, _vp, _vp]),
+    "ogs_selftest_mfma_rank1": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp, _vp]),
     "ogs_selftest_tile_order": (C.c_int, [_vp, C.c_int64, _vp, _vp]),
     "ogs_selftest_radix_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "ogs_selftest_radix_sort": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),

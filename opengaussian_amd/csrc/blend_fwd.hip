@@ -14,7 +14,9 @@
 // pack_blend_chunked_kernel does both for a tile in one workgroup, chunk by chunk, and stops when every pixel is done (the
 // default forward).  blend_forward_rows_kernel blends streams that are already packed: a pass with an empty list, and the
 // re-blend of a kept pass.  DESIGN.md section 3 has the history of this design and of the kernels it replaced.
-// No MFMA: the loop is a per-pixel recurrence, not a contraction.
+// No MFMA: the recurrence (T, the stop) is per pixel, and the one part of a step that IS a product -- the rank-one update
+// sums[pixel][channel] += w[pixel] * f[channel] per 4x4 block -- was built on v_mfma_f32_16x16x1_4b_f32 and measured slower than
+// the packed FMAs it replaced (rank1_update below).
 #include "ogs_common.h"
 
 namespace ogs {
@@ -257,6 +259,39 @@ __global__ __launch_bounds__(kBlock) void blend_forward_rows_kernel(
                            bg, out_color, out_depth, out_alpha, n_contrib, final_T, pf_lines, lds, feats);
 }
 
+// ---- the step's accumulation as a matrix instruction (NOT used by the kernels: DESIGN.md section 3e) ---------------------------
+// sums[pixel][channel] += w[pixel] * f[channel] for the four 4x4 blocks of a quadrant at once: v_mfma_f32_16x16x1_4b_f32 is four
+// independent 16x16 outer products, block b taking its A column and its B row from lanes 16b..16b+15 -- the walk's own layout
+// (DPP row = block, lane in row = pixel for A, = channel for B).  K = 1: every element gets one fused multiply-add per call, no
+// summation order exists, and a chain of calls is bit for bit the chain of fmaf() the kernels run (ogs_selftest_mfma_rank1 holds
+// it to that: denormals, signed zeros, cancellation).  Register 4b + m of lane 16q + j holds block b, pixel 4q + m, channel j.
+// A pack_blend_chunked_kernel built on it issued fewer vector and LDS instructions and ran slower: the instruction has the rate
+// of the packed FMAs, works on a 16-channel tile of which C + 2 are needed, and holds the SIMD's vector issue while it starts
+// (numbers: DESIGN.md section 3e).  Kept as the tested statement of what the instruction computes.
+typedef float v16f __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ v16f rank1_update(float w, float f, v16f acc) {
+    return __builtin_amdgcn_mfma_f32_16x16x1f32(w, f, acc, 0, 0, 0);
+}
+// test hook (ogs_selftest_mfma_rank1): `steps` chained updates of the 4 x 16 x 16 sums, w / f [steps][64] as the lanes of a
+// wave hold them, acc0 / out [4][16][16] = [block][pixel][channel]; once on the matrix pipe, once as fmaf per element
+__global__ __launch_bounds__(kWave) void mfma_rank1_test_kernel(const float* __restrict__ w, const float* __restrict__ f,
+                                                                const float* __restrict__ acc0, int steps, float* __restrict__ out) {
+    const int lane = threadIdx.x, q = lane >> 4, j = lane & 15;
+    v16f acc;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = acc0[((k >> 2) * 16 + 4 * q + (k & 3)) * 16 + j];
+    for (int t = 0; t < steps; ++t) acc = rank1_update(w[t * kWave + lane], f[t * kWave + lane], acc);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) out[((k >> 2) * 16 + 4 * q + (k & 3)) * 16 + j] = acc[k];
+}
+__global__ __launch_bounds__(256) void fma_rank1_test_kernel(const float* __restrict__ w, const float* __restrict__ f,
+                                                             const float* __restrict__ acc0, int steps, float* __restrict__ out) {
+    const int b = blockIdx.x, i = threadIdx.x >> 4, j = threadIdx.x & 15;
+    float a = acc0[b * 256 + threadIdx.x];
+    for (int t = 0; t < steps; ++t) a = fmaf(w[t * kWave + 16 * b + i], f[t * kWave + 16 * b + j], a);
+    out[b * 256 + threadIdx.x] = a;
+}
+
 // ---- pack + forward blend of a tile, CHUNK BY CHUNK with a workgroup-wide exit (the default forward) -------------------
 // The reference's forward fetches a tile's list 256 entries at a time and the whole block stops once every pixel is done
 // (SURVEY.md section 2.1 `renderCUDA`, Appendix A.3).  On a ScanNet-class view (2 M Gaussians behind a 648 x 484 image, culled
@@ -378,8 +413,12 @@ __global__ __launch_bounds__(256) void group_stats_finish_kernel(const long long
 
 // Six waves per SIMD: the kernel is sensitive to occupancy (probe: 24 KB more LDS per workgroup, three workgroups per CU instead of
 // six: 0.402 -> 0.514 ms) and its 26 KB of LDS allow six workgroups per CU, but at C = 9 the register allocator settles at 92 VGPRs
-// = five waves.  Asking for six costs six spilled dwords (80 VGPRs) and gives 0.402 -> 0.390 ms (A-B-A-B on one box); C = 12
-// cannot fit and stays where it was.
+// = five waves.  Asking for six gives 0.402 -> 0.390 ms (A-B-A-B on one box); C = 12 cannot fit (its 30 KB of LDS allow five
+// workgroups) and stays where it was.  This file is compiled without the SLP vectoriser (build.py): left to it, the compiler
+// pairs the scalar multiplies of the box tests into ~80 v_pk_mul / v_pk_fma per kernel, whose even-aligned register pairs cost
+// the C = 9 kernel three spilled dwords at 80 VGPRs; without it, 78 VGPRs and no scratch (AMD clang 22.0.0git, roc-7.2.0: the
+// figures depend on the compiler's register allocation; table and timings in DESIGN.md section 3e).  The packed operations
+// written out below (v2f) are not affected.
 // STATS (ogs_raster_forward_group_stats): the same walk -- same packing, same per-pixel arithmetic, same exit -- with the
 // image epilogue replaced by group_stats_epilogue (per-(group, label) statistics, nothing of size G*W*H) and the write-outs
 // kept for the backward (records, quadrant streams, qcount) compiled out.  `st` is unused when STATS is false.
@@ -1087,6 +1126,14 @@ const uint32_t* launch_tile_order(const ImageState& is, int64_t vtiles, int P, h
 int launch_tile_order_test(const uint32_t* ranges, int64_t vtiles, uint32_t* order, hipStream_t s) {
     if (vtiles > kOrderMaxTiles) { set_error("selftest: more than %lld tiles", (long long)kOrderMaxTiles); return OGS_ERR_UNSUPPORTED; }
     OGS_LAUNCH(tile_order_kernel, dim3(1), dim3(kOrderThreads), 0, s, (const uint2*)ranges, (uint32_t)vtiles, order);
+    OGS_LAUNCH_CHECK(1, s);
+    return OGS_OK;
+}
+
+int launch_mfma_rank1_test(const float* w, const float* f, const float* acc0, int steps, float* out_mfma, float* out_fma,
+                           hipStream_t s) {
+    OGS_LAUNCH(mfma_rank1_test_kernel, dim3(1), dim3(kWave), 0, s, w, f, acc0, steps, out_mfma);
+    OGS_LAUNCH(fma_rank1_test_kernel, dim3(4), dim3(256), 0, s, w, f, acc0, steps, out_fma);
     OGS_LAUNCH_CHECK(1, s);
     return OGS_OK;
 }

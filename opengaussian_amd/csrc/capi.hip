@@ -149,7 +149,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 404; }
+int ogs_version(void) { return 405; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 
@@ -519,6 +519,14 @@ int ogs_sh_grad_from_views(int32_t P, int32_t V, int32_t sh_degree, int32_t sh_c
 int ogs_selftest_wave_fold16(const float* in, float* out, void* stream_) {
     if (!in || !out) { set_error("selftest: NULL pointer"); return OGS_ERR_INVALID_ARG; }
     return launch_wave_fold16_test(in, out, static_cast<hipStream_t>(stream_));
+}
+
+/* test hook: the forward walk's per-step accumulation as a matrix instruction (4 rank-one 16x16 updates per MFMA, K = 1) chained
+ * `steps` times, and the same chain as one fmaf per element; the two outputs must agree bit for bit. */
+int ogs_selftest_mfma_rank1(const float* w, const float* f, const float* acc0, int32_t steps, float* out_mfma, float* out_fma,
+                            void* stream_) {
+    if (!w || !f || !acc0 || !out_mfma || !out_fma || steps < 0) { set_error("selftest: NULL pointer / steps < 0"); return OGS_ERR_INVALID_ARG; }
+    return launch_mfma_rank1_test(w, f, acc0, steps, out_mfma, out_fma, static_cast<hipStream_t>(stream_));
 }
 
 int ogs_selftest_tile_order(const uint32_t* ranges, int64_t vtiles, uint32_t* order, void* stream_) {
