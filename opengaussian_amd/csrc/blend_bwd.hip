@@ -617,12 +617,8 @@ int launch_c(const OgsRasterBwdArgs& a, const ImageState& is, void* grad_rec_, h
 
 int launch_blend_backward(const OgsRasterBwdArgs& a, const ImageState& is, void* grad_rec, hipStream_t s) {
     if (a.num_rendered <= 0) return OGS_OK;
-    switch (a.C) {
-        case 3: return launch_c<3>(a, is, grad_rec, s);
-        case 6: return launch_c<6>(a, is, grad_rec, s);
-        case 9: return launch_c<9>(a, is, grad_rec, s);
-        default: set_error("backward: unsupported channel count C=%d (3, 6 or 9)", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<9>(a.C, "backward: unsupported channel count C=%d (3, 6 or 9)",
+                                [&](auto c) { return launch_c<c()>(a, is, grad_rec, s); });
 }
 
 int launch_wave_fold16_test(const float* in, float* out, hipStream_t s) {

@@ -9,11 +9,16 @@
 //     order inside a stream is preserved with a block-wide prefix sum over per-quadrant counters packed in one u64.  The
 //     reference-visible binning state (sorted keys, point list, tile ranges) is untouched and stays bit-exact; dropped
 //     entries are exactly those every lane of the quadrant would have skipped.
-//   * blend: each wave64 owns one quadrant and walks its index stream in chunks of 64 entries, per 4x4 pixel block
-//     (blend_rows_tile), with every operand of the per-pixel arithmetic in VGPRs.
-// pack_blend_chunked_kernel does both for a tile in one workgroup, chunk by chunk, and stops when every pixel is done (the
-// default forward).  blend_forward_rows_kernel blends streams that are already packed: a pass with an empty list, and the
-// re-blend of a kept pass.  DESIGN.md section 3 has the history of this design and of the kernels it replaced.
+//   * blend: each wave64 owns one quadrant and walks its index stream in sub-chunks of 64 entries, per 4x4 pixel block, with
+//     every operand of the per-pixel arithmetic in VGPRs.
+// The walk exists ONCE, as QuadWalk<C>: the per-pixel state, the arithmetic of one (pixel, entry) pair, the sub-chunk step and
+// the image epilogue.  Two kernels feed it 64 records at a time in LDS:
+//   * pack_blend_chunked_kernel packs a tile chunk by chunk in one workgroup, blends each chunk straight from its staging
+//     buffer, and stops when every pixel is done (the default forward, and the statistics pass);
+//   * blend_forward_rows_kernel gathers records that are already packed: a pass with an empty list, and the re-blend of a
+//     kept pass.
+// Both therefore give the same bits on the same streams.  DESIGN.md section 3 has the history of this design and of the
+// kernels it replaced.
 // No MFMA: the recurrence (T, the stop) is per pixel, and the one part of a step that IS a product -- the rank-one update
 // sums[pixel][channel] += w[pixel] * f[channel] per 4x4 block -- was built on v_mfma_f32_16x16x1_4b_f32 and measured slower than
 // the packed FMAs it replaced (rank1_update below).
@@ -33,27 +38,11 @@ __device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
 
 // blend record (one per tile-list entry that reaches some quadrant, at the entry's list position):
 //   [0] x  [1] y  [2] -0.5*A  [3] -0.5*C  [4] -B  [5] h=-thr/2  [6] opacity  [7] Gaussian id (bit pattern)
-//   (round 4: -0.5*C moved next to -0.5*A -- (x, y) and (-A/2, -C/2) are even-aligned SGPR pairs, so the quadrant walks form the
+//   (round 4: -0.5*C moved next to -0.5*A -- (x, y) and (-A/2, -C/2) are even-aligned pairs, so the quadrant walks form the
 //   pixel offset and the two products a2*dx, c2*dy with ONE packed instruction each)
 //   [8..8+C) features  [8+C] view depth, rest zero padding to a multiple of 4 floats.
 // The depth sits right behind the features so that the (feature, feature) / (feature, depth) operand pairs of
-// the blend loops' packed FMAs are even-aligned SGPR pairs straight out of s_load (no s_mov shuffles).
-
-// ---- forward blend, one list per 4x4 pixel block ----------------------------------------------------------------------
-// A wave owns a quadrant and walks its index stream in CHUNKS of 64 entries.  (Walking it one entry at a time with the
-// record in SGPRs keeps ~51 % of the lanes busy and pays 4 issue cycles for nearly every vector instruction:
-// profiles/r03_valu_issue_price_list.json, any SGPR operand halves the issue rate.)
-//   1. lane e gathers record e of the chunk with vector loads (L2 hits: the prefetch at kernel entry pulled the tile's
-//      records in), tests it against the four 4x4 blocks of the quadrant (the exact box-vs-ellipse test of pack, on a
-//      4x4 box) and parks the record in the wave's LDS region;
-//   2. four ballots + prefix popcounts turn the test bits into four compacted lists (LDS), one per DPP row;
-//   3. the four rows of the wave -- row r = the 16 pixels of block r -- walk THEIR lists side by side: per step a row reads
-//      its next record from LDS into VGPRs (four different records per ds_read_b128, one LDS cycle per row) and every
-//      operand of the per-pixel arithmetic is a VGPR.
-// A skipped (entry, block) pair is one every pixel of the block would have skipped.  n_contrib is the 1-based position of
-// the pixel's last contributor in the QUADRANT stream (the backward walks the same streams).  A finished or outside pixel is
-// parked far away (fxe = kFar): its power becomes hugely negative and the candidate compare fails, so no `done` flag enters
-// the control flow; `all_done` is a wave-uniform flag in the loop condition.
+// the blend loops' packed FMAs are even-aligned pairs (no shuffles).
 template <int C>
 struct RowRec {          // one record in VGPRs
     static constexpr int NV4 = stream_vec4(C);
@@ -69,29 +58,200 @@ struct RowRec {          // one record in VGPRs
     __device__ __forceinline__ float feat(int c) const { return at(8 + c); }
 };
 
-constexpr int kRowSlots = 65;                // 64 chunk entries + the dummy that a finished row keeps reading
-constexpr int kRowListLen = 72;              // 64 + slack for the two-ahead index reads
+// the record a finished row keeps reading: h < 0 makes |power + h| <= h false for every pixel
 template <int C>
-struct RowsLds {
-    float4 s_rec[kBlock / kWave][kRowSlots * stream_vec4(C)];
-    uint32_t s_list[kBlock / kWave][4][kRowListLen];
+__device__ __forceinline__ void write_dummy_record(float4* __restrict__ slot) {
+#pragma unroll
+    for (int k = 0; k < stream_vec4(C); ++k) slot[k] = float4{0.f, 0.f, 0.f, 0.f};
+    slot[1] = float4{0.f, -1.f, 0.f, 0.f};                    // fields 4..7: b2, h = -1, opacity, id
+}
+
+constexpr int kRowListLen = 72;              // 64 sub-chunk entries + slack for the two-ahead index reads
+
+// ---- the quadrant walk ------------------------------------------------------------------------------------------------
+// A wave owns an 8x8 quadrant and takes its index stream in SUB-CHUNKS of 64 entries whose records sit in LDS.  (Walking it one
+// entry at a time with the record in SGPRs keeps ~51 % of the lanes busy and pays 4 issue cycles for nearly every vector
+// instruction: profiles/r03_valu_issue_price_list.json, any SGPR operand halves the issue rate.)  One step():
+//   1. lane e tests record e of the sub-chunk against the four 4x4 blocks of the quadrant (the exact box-vs-ellipse test of
+//      pack, on a 4x4 box);
+//   2. four ballots + prefix popcounts turn the test bits into four compacted lists (LDS), one per DPP row;
+//   3. the four rows of the wave -- row r = the 16 pixels of block r -- walk THEIR lists side by side: per trip a row reads its
+//      next two records from LDS into VGPRs (four different records per ds_read_b128, one LDS cycle per row) and every operand
+//      of the per-pixel arithmetic is a VGPR;
+//   4. the pixel's last contributor in the sub-chunk becomes its stream index (settle).
+// A skipped (entry, block) pair is one every pixel of the block would have skipped.  n_contrib is the 1-based position of
+// the pixel's last contributor in the QUADRANT stream (the backward walks the same streams).  A finished or outside pixel is
+// parked far away (fxe = kFar): its power becomes hugely negative and the candidate compare fails, so no `done` flag enters
+// the per-pixel arithmetic.
+template <int C>
+struct QuadWalk {
+    static constexpr int NPF = (C + 2) / 2;
+    static constexpr uint32_t kNoEntry = 0xFFFFFFFFu;
+    float fxe, fy, T, wacc;
+    v2f accp[NPF];           // channels 0..C-1, then the depth
+    uint32_t last;           // 1-based stream index of the pixel's last contributor (n_contrib)
+    uint32_t last_e;         // list entry of the pixel's last contributor in the current sub-chunk
+    // pixels still blending, as a wave-uniform 64-bit mask (an SGPR pair: a `bool all_done` went through a VGPR and back on every
+    // walk step); a quadrant outside the image starts with none and its feeder skips the stream
+    uint64_t alive;
+
+    __device__ __forceinline__ void init(int px, int py, bool inside) {
+        fxe = inside ? (float)px : kFar;
+        fy = (float)py;
+        T = 1.0f;
+        wacc = 0.f;
+#pragma unroll
+        for (int k = 0; k < NPF; ++k) accp[k] = (v2f){0.f, 0.f};
+        last = 0;
+        last_e = kNoEntry;
+        alive = __ballot(inside);
+    }
+
+    __device__ __forceinline__ void consume(const RowRec<C>& r, uint32_t entry) {
+        // blend_power(a2, b2, c2, dx, dy) with its subtractions and its first two products as PACKED operations on the record's
+        // register pairs (x, y) and (a2, c2) -- v_pk_add_f32 / v_pk_mul_f32: one issue slot for two results, and this walk is
+        // bound by vector issue.  Same operations, same roundings, same bits as blend_power() (ogs_common.h)
+        const v2f d = (v2f){r.at(0), r.at(1)} - (v2f){fxe, fy};
+        const v2f m = (v2f){r.at(2), r.at(3)} * d;                  // a2 * dx, c2 * dy
+        const float u = fmaf(r.at(4), d.y, m.x);                    // a2*dx + b2*dy
+        const float power = fmaf(m.y, d.y, u * d.x);
+        const float h = r.at(5);
+        const bool cand = fabsf(power + h) <= h;
+        if (__ballot(cand) != 0ull) {
+            // straight-line for all 64 lanes (no exec-mask region: a lane that is no candidate gets alpha = 0, which leaves
+            // every one of its accumulators, its T and its `last` untouched -- w = 0, test_T = T >= 1e-4)
+            const float araw = fminf(0.99f, r.at(6) * __expf(power));
+            const bool act = cand && araw >= kAlphaMin;
+            const float alpha = act ? araw : 0.f;
+            const float test_T = T * (1.0f - alpha);
+            const bool stop = test_T < 0.0001f;
+            float w = alpha * T;
+            // the pixel's last contributor: this entry iff it contributes, w > 0 <=> act && !stop (alpha >= 1/255, T >= 1e-4).
+            // The condition is a lane mask the step already has (SGPR pair), and what is recorded is the step's LIST ENTRY as it
+            // sits in a VGPR (slot << 16 | LDS offset) -- one select per step; it becomes the stream index once per sub-chunk
+            // (settle), instead of an index add, a compare and a select per step
+            bool contributes = act;
+            // a pixel saturates once: the three selects of the stop (weight, T, parking) only run in a step in which some lane
+            // stops; every other step takes the values straight (same bits: the selects would have picked them)
+            if (__ballot(stop) != 0ull) {
+                w = stop ? 0.f : w;
+                T = stop ? T : test_T;
+                fxe = stop ? kFar : fxe;
+                alive = __ballot(fxe < kFarTest);
+                contributes = act && !stop;
+            } else {
+                T = test_T;
+            }
+            const v2f w2 = {w, w};
+#pragma unroll
+            for (int k = 0; k < NPF; ++k)
+                accp[k] = __builtin_elementwise_fma((v2f){r.feat(2 * k), r.feat(2 * k + 1)}, w2, accp[k]);
+            wacc += w;
+            last_e = contributes ? entry : last_e;
+        }
+    }
+
+    // One sub-chunk: lane e < 64 holds entry e of it.  g0, g1: the two geometry float4 of the lane's record; have: the lane has an
+    // entry; rec_off: byte offset of the lane's record from `recs` (the LDS staging; every record of the sub-chunk is there, or
+    // is parked there before the fence below by the lane that holds it); dummy: the list entry of the dummy record; s_list: the
+    // wave's four lists, mylist = s_list[this lane's row]; (bx0, by0): the quadrant's origin; jbase: 1-based stream index of the
+    // sub-chunk's entry 0.  A list entry = sub-chunk slot << 16 | rec_off of the slot's record (no multiply in the walk).
+    __device__ __forceinline__ void step(const float4 g0, const float4 g1, bool have, uint32_t rec_off, uint32_t dummy,
+                                         uint32_t (&s_list)[4][kRowListLen], const uint32_t* mylist, const float4* recs,
+                                         float bx0, float by0, uint32_t jbase, int lane) {
+        bool reach[4];
+        {
+            const float gxp = g0.x, gyp = g0.y;
+            const float A = -2.f * g0.z, B = -g1.x, Cc = -2.f * g0.w, thr = -2.f * g1.y;
+            const float nbA = -B / A, nbC = -B / Cc;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const float ox = bx0 + 4.f * (float)(b & 1), oy = by0 + 4.f * (float)(b >> 1);
+                const float m = max_power_in_box(A, B, Cc, nbA, nbC, gxp - ox - 3.f, gxp - ox, gyp - oy - 3.f, gyp - oy);
+                reach[b] = have && m >= thr;
+            }
+        }
+        // four compacted lists (row b's list: sub-chunk slots that can reach block b), padded with the dummy
+#pragma unroll
+        for (int b = 0; b < 4; ++b) s_list[b][lane] = dummy;
+        if (lane < kRowListLen - kWave) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) s_list[b][kWave + lane] = dummy;
+        }
+        int maxlen = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const uint64_t mask = __ballot(reach[b]);
+            const int pos = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            if (reach[b]) s_list[b][pos] = ((uint32_t)lane << 16) | rec_off;
+            maxlen = max(maxlen, (int)__popcll(mask));
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // the four rows walk their lists; records in two register sets, indices two steps ahead
+        RowRec<C> ra, rb;
+        auto rec_of = [&](uint32_t e) {
+            return reinterpret_cast<const float4*>(reinterpret_cast<const char*>(recs) + (e & 0xFFFFu));
+        };
+        uint32_t e0 = mylist[0], e1 = mylist[1];
+        ra.load_lds(rec_of(e0));
+        for (int t = 0; t < maxlen && alive != 0ull; t += 2) {
+            const uint32_t e2 = mylist[t + 2], e3 = mylist[t + 3];
+            rb.load_lds(rec_of(e1));
+            consume(ra, e0);
+            ra.load_lds(rec_of(e2));
+            if (t + 1 < maxlen) consume(rb, e1);
+            e0 = e2; e1 = e3;
+        }
+        // settle: list entry -> 1-based index into the quadrant stream (entry's slot in the sub-chunk + what came before)
+        if (last_e != kNoEntry) last = jbase + (last_e >> 16);
+        last_e = kNoEntry;
+        __builtin_amdgcn_wave_barrier();       // the lists and the staging may be rewritten
+    }
+
+    __device__ __forceinline__ float sum(int c) const { return (c & 1) ? accp[c / 2].y : accp[c / 2].x; }      // c <= C: depth
+    __device__ __forceinline__ float colour(int c, const float* __restrict__ bg) const { return sum(c) + T * bg[c]; }
+
+    // image epilogue of a pixel inside the image
+    __device__ __forceinline__ void write_pixel(int img, int W, int H, int px, int py, const float* __restrict__ bg,
+                                                float* __restrict__ out_color, float* __restrict__ out_depth,
+                                                float* __restrict__ out_alpha, uint32_t* __restrict__ n_contrib,
+                                                float* __restrict__ final_T) const {
+        const size_t plane = (size_t)W * H;
+        const size_t pix = (size_t)img * plane + (size_t)py * W + px;
+        float* oc = out_color + (size_t)img * (C - 1) * plane;
+#pragma unroll
+        for (int c = 0; c < C; ++c) oc[c * plane + pix] = colour(c, bg);
+        out_depth[pix] = sum(C);
+        out_alpha[pix] = wacc;
+        n_contrib[pix] = last;
+        final_T[pix] = T;
+    }
 };
 
-// one tile; n = this wave's quadrant count, n_kept = records kept by the tile (qcount[tile * 5 + wave / 4])
+// ---- stand-alone blend of streams that are already packed ---------------------------------------------------------------
+// Per sub-chunk, lane e gathers record e through the quadrant's index stream with vector loads (L2 hits: the prefetch at kernel
+// entry pulled the tile's records in) and parks it in the wave's LDS region for QuadWalk::step.
 // RF >= 0 (re-blend of a kept pass, ogs_raster_forward_reblend): channels [RF, C) of every record come from the caller's CURRENT
 // per-Gaussian features `feats` [P, C - RF] instead of the record -- the lane that gathers a record fetches its Gaussian's row
 // (slot 7 of the record is the id) on the way into LDS; the kept records are never written.
+template <int C>
+struct RowsLds {
+    float4 s_rec[kBlock / kWave][(kWave + 1) * stream_vec4(C)];      // per wave: 64 sub-chunk records + the dummy
+    uint32_t s_list[kBlock / kWave][4][kRowListLen];
+};
+
 template <int C, int RF = -1>
-__device__ __forceinline__ void blend_rows_tile(
-    const uint2 range, int n, int n_kept, const float* __restrict__ stream,
-    const uint32_t* __restrict__ quad_list, int W, int H, int gx, int img, int timg, const float* __restrict__ bg, float* __restrict__ out_color,
+__global__ __launch_bounds__(kBlock) void blend_forward_rows_kernel(
+    const uint2* __restrict__ ranges, const uint32_t* __restrict__ qcount, const float* __restrict__ stream,
+    const uint32_t* __restrict__ quad_list, int W, int H, int gx, int tiles, const float* __restrict__ bg, float* __restrict__ out_color,
     float* __restrict__ out_depth, float* __restrict__ out_alpha, uint32_t* __restrict__ n_contrib,
-    float* __restrict__ final_T, int pf_lines, RowsLds<C>& lds, const float* __restrict__ feats = nullptr) {
+    float* __restrict__ final_T, int pf_lines, const uint32_t* __restrict__ tile_order, const float* __restrict__ feats) {
     constexpr int NV4 = stream_vec4(C);
     constexpr int RS = NV4 * 4;                  // floats per stream record
-    constexpr int kListLen = kRowListLen;
-    auto& s_rec = lds.s_rec;
-    auto& s_list = lds.s_list;
+    __shared__ RowsLds<C> lds;
+    const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;
+    const int img = tile / tiles, timg = tile - img * tiles;
     const int tx = timg % gx, ty = timg / gx;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int row = lane >> 4, l16 = lane & 15;
@@ -99,8 +259,10 @@ __device__ __forceinline__ void blend_rows_tile(
     const int px = qx0 + 4 * (row & 1) + (l16 & 3);
     const int py = qy0 + 4 * (row >> 1) + (l16 >> 2);
     const bool inside = px < W && py < H;
-    const float fy = (float)py;
 
+    // n = this wave's quadrant count, n_kept = records kept by the tile
+    const uint2 range = ranges[tile];
+    const int n = (int)qcount[tile * 5 + wave], n_kept = (int)qcount[tile * 5 + 4];
     const int n_tile = (int)(range.y - range.x);
     const float* __restrict__ tb = stream + (size_t)range.x * RS;
     const uint32_t* __restrict__ qi = quad_list + ((size_t)range.x * 5 + (size_t)wave * n_tile);
@@ -108,61 +270,16 @@ __device__ __forceinline__ void blend_rows_tile(
     RecordPrefetch pf;
     pf.issue(tb, n_kept, RS, tid, pf_lines);
 
-    float4* __restrict__ recs = s_rec[wave];
-    uint32_t* __restrict__ mylist = s_list[wave][row];
-    if (lane == 0) {
-        // dummy record: h < 0 makes |power + h| <= h false for every pixel
-#pragma unroll
-        for (int k = 0; k < NV4; ++k) recs[64 * NV4 + k] = float4{0.f, 0.f, 0.f, 0.f};
-        recs[64 * NV4 + 1] = float4{0.f, -1.f, 0.f, 0.f};                    // fields 4..7: c2, h = -1, opacity, id
-    }
-    float fxe = inside ? (float)px : kFar;
-    float T = 1.0f;
-    constexpr int NPF = (C + 2) / 2;
-    v2f accp[NPF];
-#pragma unroll
-    for (int k = 0; k < NPF; ++k) accp[k] = (v2f){0.f, 0.f};
-    float wacc = 0.f;
-    uint32_t last = 0;
-    bool all_done = false;
+    float4* __restrict__ recs = lds.s_rec[wave];
+    uint32_t* __restrict__ mylist = lds.s_list[wave][row];
+    if (lane == 0) write_dummy_record<C>(recs + kWave * NV4);
+    QuadWalk<C> walk;
+    walk.init(px, py, inside);
 
-    constexpr uint32_t kNoEntry = 0xFFFFFFFFu;
-    uint32_t last_e = kNoEntry;          // list entry (slot << 16 | LDS offset) of the pixel's last contributor in the current chunk
-    auto consume = [&](const RowRec<C>& rec, uint32_t entry) {
-        // blend_power() with packed subtractions / first products (see pack_blend_chunked_kernel): same bits
-        const v2f d = (v2f){rec.at(0), rec.at(1)} - (v2f){fxe, fy};
-        const v2f m = (v2f){rec.at(2), rec.at(3)} * d;
-        const float u = fmaf(rec.at(4), d.y, m.x);
-        const float power = fmaf(m.y, d.y, u * d.x);
-        const float h = rec.at(5);
-        const bool cand = fabsf(power + h) <= h;
-        if (__ballot(cand) != 0ull) {
-            // straight-line for all 64 lanes (no exec-mask region: a lane that is no candidate gets alpha = 0, which leaves
-            // every one of its accumulators, its T and its `last` untouched -- w = 0, test_T = T >= 1e-4 -- so the values of
-            // the contributing lanes are the same operations on the same operands as before)
-            const float araw = fminf(0.99f, rec.at(6) * __expf(power));
-            const bool act = cand && araw >= kAlphaMin;
-            const float alpha = act ? araw : 0.f;
-            const float test_T = T * (1.0f - alpha);
-            const bool stop = test_T < 0.0001f;
-            const float w = stop ? 0.f : alpha * T;
-            const v2f w2 = {w, w};
-#pragma unroll
-            for (int k = 0; k < NPF; ++k)
-                accp[k] = __builtin_elementwise_fma((v2f){rec.feat(2 * k), rec.feat(2 * k + 1)}, w2, accp[k]);
-            wacc += w;
-            T = stop ? T : test_T;
-            last_e = (act && !stop) ? entry : last_e;      // w > 0 <=> act && !stop; see pack_blend_chunked_kernel
-            fxe = stop ? kFar : fxe;
-            if (__ballot(stop) != 0ull) all_done = __ballot(fxe < kFarTest) == 0ull;
-        }
-    };
-
-    const float bx0 = (float)(qx0 + 4 * 0), by0 = (float)qy0;
-    for (int c0 = 0; c0 < n && !all_done; c0 += kWave) {
-        const int cnt = min(kWave, n - c0);
-        // ---- 1. gather, test, park ----
-        const bool have = lane < cnt;
+    constexpr uint32_t kDummy = ((uint32_t)kWave << 16) | ((uint32_t)kWave * NV4 * 16u);
+    const float bx0 = (float)qx0, by0 = (float)qy0;
+    for (int c0 = 0; c0 < n && walk.alive != 0ull; c0 += kWave) {
+        const bool have = lane < min(kWave, n - c0);
         const uint32_t ridx = have ? min(qi[c0 + lane], lim) : 0u;
         const float4* __restrict__ rp = reinterpret_cast<const float4*>(tb + (size_t)ridx * RS);
         float4 r[NV4];
@@ -180,83 +297,12 @@ __device__ __forceinline__ void blend_rows_tile(
         }
 #pragma unroll
         for (int k = 0; k < NV4; ++k) recs[lane * NV4 + k] = r[k];
-        bool reach[4];
-        {
-            const float gxp = r[0].x, gyp = r[0].y;
-            const float A = -2.f * r[0].z, B = -r[1].x, Cc = -2.f * r[0].w, thr = -2.f * r[1].y;
-            const float nbA = -B / A, nbC = -B / Cc;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const float ox = bx0 + 4.f * (float)(b & 1), oy = by0 + 4.f * (float)(b >> 1);
-                const float m = max_power_in_box(A, B, Cc, nbA, nbC, gxp - ox - 3.f, gxp - ox, gyp - oy - 3.f, gyp - oy);
-                reach[b] = have && m >= thr;
-            }
-        }
-        // ---- 2. four compacted lists (row b's list: chunk slots that can reach block b), padded with the dummy ----
-        // list entry = chunk slot << 16 | byte offset of the slot's record in the wave's LDS region (no multiply in the walk)
-        constexpr uint32_t kDummy = (64u << 16) | (64u * NV4 * 16u);
-#pragma unroll
-        for (int b = 0; b < 4; ++b) s_list[wave][b][lane] = kDummy;
-        if (lane < kListLen - kWave) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b) s_list[wave][b][kWave + lane] = kDummy;
-        }
-        int maxlen = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const uint64_t mask = __ballot(reach[b]);
-            const int pos = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-            if (reach[b]) s_list[wave][b][pos] = ((uint32_t)lane << 16) | ((uint32_t)lane * NV4 * 16u);
-            maxlen = max(maxlen, (int)__popcll(mask));
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        // ---- 3. the four rows walk their lists; records two register sets, indices two steps ahead ----
-        RowRec<C> ra, rb;
-        auto rec_of = [&](uint32_t e) {
-            return reinterpret_cast<const float4*>(reinterpret_cast<const char*>(recs) + (e & 0xFFFFu));
-        };
-        uint32_t e0 = mylist[0], e1 = mylist[1];
-        ra.load_lds(rec_of(e0));
-        for (int t = 0; t < maxlen && !all_done; t += 2) {
-            const uint32_t e2 = mylist[t + 2], e3 = mylist[t + 3];
-            rb.load_lds(rec_of(e1));
-            consume(ra, e0);
-            ra.load_lds(rec_of(e2));
-            if (t + 1 < maxlen) consume(rb, e1);
-            e0 = e2; e1 = e3;
-        }
-        if (last_e != kNoEntry) last = (uint32_t)c0 + (last_e >> 16) + 1u;      // list entry -> 1-based stream index
-        last_e = kNoEntry;
-        __builtin_amdgcn_wave_barrier();
+        walk.step(r[0], r[1], have, (uint32_t)lane * NV4 * 16u, kDummy, lds.s_list[wave], mylist, recs, bx0, by0,
+                  (uint32_t)c0 + 1u, lane);
     }
 
-    if (inside) {
-        const size_t plane = (size_t)W * H;
-        const size_t pix = (size_t)img * plane + (size_t)py * W + px;
-        float* oc = out_color + (size_t)img * (C - 1) * plane;
-#pragma unroll
-        for (int c = 0; c < C; ++c) oc[c * plane + pix] = ((c & 1) ? accp[c / 2].y : accp[c / 2].x) + T * bg[c];
-        out_depth[pix] = (C & 1) ? accp[C / 2].y : accp[C / 2].x;
-        out_alpha[pix] = wacc;
-        n_contrib[pix] = last;
-        final_T[pix] = T;
-    }
+    if (inside) walk.write_pixel(img, W, H, px, py, bg, out_color, out_depth, out_alpha, n_contrib, final_T);
     pf.retire(n_contrib, W);
-}
-
-template <int C, int RF = -1>
-__global__ __launch_bounds__(kBlock) void blend_forward_rows_kernel(
-    const uint2* __restrict__ ranges, const uint32_t* __restrict__ qcount, const float* __restrict__ stream,
-    const uint32_t* __restrict__ quad_list, int W, int H, int gx, int tiles, const float* __restrict__ bg, float* __restrict__ out_color,
-    float* __restrict__ out_depth, float* __restrict__ out_alpha, uint32_t* __restrict__ n_contrib,
-    float* __restrict__ final_T, int pf_lines, const uint32_t* __restrict__ tile_order, const float* __restrict__ feats) {
-    __shared__ RowsLds<C> lds;
-    const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;
-    const int img = tile / tiles, timg = tile - img * tiles;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    blend_rows_tile<C, RF>(ranges[tile], (int)qcount[tile * 5 + wave], (int)qcount[tile * 5 + 4], stream, quad_list, W, H, gx, img, timg,
-                           bg, out_color, out_depth, out_alpha, n_contrib, final_T, pf_lines, lds, feats);
 }
 
 // ---- the step's accumulation as a matrix instruction (NOT used by the kernels: DESIGN.md section 3e) ---------------------------
@@ -299,13 +345,10 @@ __global__ __launch_bounds__(256) void fma_rank1_test_kernel(const float* __rest
 // (scripts/list_depth_stats.py -> profiles/r04_list_depth.json; 77 % at the headline workload), so packing the whole list
 // before the first pixel is blended does mostly wasted work.  Here the tile's list is taken in chunks of 256 entries:
 //     pack the chunk (quadrant box tests, block scan, kept records staged in LDS, index streams and records written out for
-//     the backward) -> barrier -> every wave blends the entries the chunk ADDED to its quadrant's stream, reading the
-//     records from the LDS staging itself -> the four waves vote; the workgroup leaves the list when every pixel of the
-//     tile is done.
-// The blend takes the records from the chunk's staging buffer, which all four waves share read-only between two barriers,
-// instead of re-reading the records it has just written.  Per (pixel, entry) the arithmetic is blend_rows_tile's, in the
-// same order: images, n_contrib (1-based position in the quadrant stream) and final_T are bit for bit what
-// blend_forward_rows_kernel gives on the packed streams.  qcount holds the counts AT THE EXIT: the backward (which starts
+//     the backward) -> barrier -> every wave blends the entries the chunk ADDED to its quadrant's stream (QuadWalk::step,
+//     64 at a time) -> the four waves vote; the workgroup leaves the list when every pixel of the tile is done.
+// The walk takes the records from the chunk's staging buffer, which all four waves share read-only between two barriers,
+// instead of re-reading the records it has just written.  qcount holds the counts AT THE EXIT: the backward (which starts
 // from n_contrib) and the n_contrib export never look past them; entries behind the exit are neither packed nor written.
 template <int C>
 struct ChunkLds {
@@ -436,7 +479,6 @@ void pack_blend_chunked_kernel(
     // workgroup entry, in front of the first gather, the same stores cost the S1M step 0.005 ms more: DESIGN.md section 3d)
     constexpr int NV = rec_vec4(C);
     constexpr int SV = stream_vec4(C);
-    constexpr int kListLen = kRowListLen;
     __shared__ ChunkLds<C> lds;
     const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;
     const int img = tile / tiles, timg = tile - img * tiles;
@@ -445,77 +487,18 @@ void pack_blend_chunked_kernel(
     const int tx = timg % gx, ty = timg / gx;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float X0 = (float)(tx * kTile), Y0 = (float)(ty * kTile);
-    // blend side: wave = quadrant, DPP row = 4x4 block (blend_rows_tile's mapping)
+    // blend side: wave = quadrant, DPP row = 4x4 block
     const int row = lane >> 4, l16 = lane & 15;
     const int qx0 = tx * kTile + (wave & 1) * 8, qy0 = ty * kTile + (wave >> 1) * 8;
     const int px = qx0 + 4 * (row & 1) + (l16 & 3);
     const int py = qy0 + 4 * (row >> 1) + (l16 >> 2);
     const bool inside = px < W && py < H;
-    const float fy = (float)py;
-    float fxe = inside ? (float)px : kFar;
-    float T = 1.0f;
-    constexpr int NPF = (C + 2) / 2;
-    v2f accp[NPF];
-#pragma unroll
-    for (int k = 0; k < NPF; ++k) accp[k] = (v2f){0.f, 0.f};
-    float wacc = 0.f;
-    uint32_t last = 0;
-    // pixels still blending, as a wave-uniform 64-bit mask (an SGPR pair: a `bool all_done` went through a VGPR and back on every
-    // walk step); a quadrant outside the image starts with none
-    uint64_t alive = __ballot(inside);
+    QuadWalk<C> walk;
+    walk.init(px, py, inside);
 
     const float4* __restrict__ recs = lds.s_rec;
     uint32_t* __restrict__ mylist = lds.s_list[wave][row];
-    if (tid == 0) {
-        // dummy record: h < 0 makes |power + h| <= h false for every pixel
-#pragma unroll
-        for (int k = 0; k < SV; ++k) lds.s_rec[kBlock * SV + k] = float4{0.f, 0.f, 0.f, 0.f};
-        lds.s_rec[kBlock * SV + 1] = float4{0.f, -1.f, 0.f, 0.f};
-    }
-
-    constexpr uint32_t kNoEntry = 0xFFFFFFFFu;
-    uint32_t last_e = kNoEntry;          // list entry of the pixel's last contributor in the current sub-chunk
-    auto consume = [&](const RowRec<C>& r, uint32_t entry) {
-        // blend_power(a2, b2, c2, dx, dy) with its subtractions and its first two products as PACKED operations on the record's
-        // register pairs (x, y) and (a2, c2) -- v_pk_add_f32 / v_pk_mul_f32: one issue slot for two results, and this walk is
-        // bound by vector issue.  Same operations, same roundings, same bits as blend_power() (ogs_common.h)
-        const v2f d = (v2f){r.at(0), r.at(1)} - (v2f){fxe, fy};
-        const v2f m = (v2f){r.at(2), r.at(3)} * d;                  // a2 * dx, c2 * dy
-        const float u = fmaf(r.at(4), d.y, m.x);                    // a2*dx + b2*dy
-        const float power = fmaf(m.y, d.y, u * d.x);
-        const float h = r.at(5);
-        const bool cand = fabsf(power + h) <= h;
-        if (__ballot(cand) != 0ull) {
-            const float araw = fminf(0.99f, r.at(6) * __expf(power));
-            const bool act = cand && araw >= kAlphaMin;
-            const float alpha = act ? araw : 0.f;
-            const float test_T = T * (1.0f - alpha);
-            const bool stop = test_T < 0.0001f;
-            float w = alpha * T;
-            // the pixel's last contributor: this entry iff it contributes, w > 0 <=> act && !stop (alpha >= 1/255, T >= 1e-4).
-            // The condition is a lane mask the step already has (SGPR pair), and what is recorded is the step's LIST ENTRY as it
-            // sits in a VGPR (slot << 16 | LDS offset) -- one select per step; it becomes the stream index once per sub-chunk
-            // (`settle`), instead of an index add, a compare and a select per step
-            bool contributes = act;
-            // a pixel saturates once: the three selects of the stop (weight, T, parking) only run in a step in which some lane
-            // stops; every other step takes the values straight (same bits: the selects would have picked them)
-            if (__ballot(stop) != 0ull) {
-                w = stop ? 0.f : w;
-                T = stop ? T : test_T;
-                fxe = stop ? kFar : fxe;
-                alive = __ballot(fxe < kFarTest);
-                contributes = act && !stop;
-            } else {
-                T = test_T;
-            }
-            const v2f w2 = {w, w};
-#pragma unroll
-            for (int k = 0; k < NPF; ++k)
-                accp[k] = __builtin_elementwise_fma((v2f){r.feat(2 * k), r.feat(2 * k + 1)}, w2, accp[k]);
-            wacc += w;
-            last_e = contributes ? entry : last_e;
-        }
-    };
+    if (tid == 0) write_dummy_record<C>(lds.s_rec + kBlock * SV);
 
     uint32_t running[5];
 #pragma unroll
@@ -610,64 +593,17 @@ void pack_blend_chunked_kernel(
         // ================= blend what the chunk added to this wave's quadrant stream =================
         const int cnt_q = (int)((uint32_t)(total >> (12 * wave)) & 0xFFFu);
         const uint32_t j0 = wave == 0 ? running[0] : wave == 1 ? running[1] : wave == 2 ? running[2] : running[3];
-        for (int c0 = 0; c0 < cnt_q && alive != 0ull; c0 += kWave) {
-            const int cnt = min(kWave, cnt_q - c0);
-            const bool have = lane < cnt;
+        // list entry = sub-chunk slot << 16 | byte offset of the record in the staging buffer
+        constexpr uint32_t kDummy = ((uint32_t)kWave << 16) | ((uint32_t)kBlock * SV * 16u);
+        for (int c0 = 0; c0 < cnt_q && walk.alive != 0ull; c0 += kWave) {
+            const bool have = lane < min(kWave, cnt_q - c0);
             const uint32_t cl = have ? (uint32_t)lds.s_qnew[wave][c0 + lane] : (uint32_t)kBlock;
-            const float4 r0 = recs[cl * SV], r1 = recs[cl * SV + 1];
-            bool reach[4];
-            {
-                const float gxp = r0.x, gyp = r0.y;
-                const float A = -2.f * r0.z, B = -r1.x, Cc = -2.f * r0.w, thr = -2.f * r1.y;
-                const float nbA = -B / A, nbC = -B / Cc;
-#pragma unroll
-                for (int bb = 0; bb < 4; ++bb) {
-                    const float ox = bx0 + 4.f * (float)(bb & 1), oy = by0 + 4.f * (float)(bb >> 1);
-                    const float m = max_power_in_box(A, B, Cc, nbA, nbC, gxp - ox - 3.f, gxp - ox, gyp - oy - 3.f, gyp - oy);
-                    reach[bb] = have && m >= thr;
-                }
-            }
-            // list entry = sub-chunk slot << 16 | byte offset of the record in the staging buffer
-            constexpr uint32_t kDummy = (64u << 16) | ((uint32_t)kBlock * SV * 16u);
-#pragma unroll
-            for (int bb = 0; bb < 4; ++bb) lds.s_list[wave][bb][lane] = kDummy;
-            if (lane < kListLen - kWave) {
-#pragma unroll
-                for (int bb = 0; bb < 4; ++bb) lds.s_list[wave][bb][kWave + lane] = kDummy;
-            }
-            int maxlen = 0;
-#pragma unroll
-            for (int bb = 0; bb < 4; ++bb) {
-                const uint64_t m64 = __ballot(reach[bb]);
-                const int p = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m64 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m64, 0u));
-                if (reach[bb]) lds.s_list[wave][bb][p] = ((uint32_t)lane << 16) | (cl * SV * 16u);
-                maxlen = max(maxlen, (int)__popcll(m64));
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            RowRec<C> ra, rb;
-            auto rec_of = [&](uint32_t e) {
-                return reinterpret_cast<const float4*>(reinterpret_cast<const char*>(recs) + (e & 0xFFFFu));
-            };
-            uint32_t e0 = mylist[0], e1 = mylist[1];
-            ra.load_lds(rec_of(e0));
-            const uint32_t jbase = j0 + (uint32_t)c0 + 1u;
-            for (int t = 0; t < maxlen && alive != 0ull; t += 2) {
-                const uint32_t e2 = mylist[t + 2], e3 = mylist[t + 3];
-                rb.load_lds(rec_of(e1));
-                consume(ra, e0);
-                ra.load_lds(rec_of(e2));
-                if (t + 1 < maxlen) consume(rb, e1);
-                e0 = e2; e1 = e3;
-            }
-            // settle: list entry -> 1-based index into the quadrant stream (entry's slot in the sub-chunk + what came before)
-            if (last_e != kNoEntry) last = jbase + (last_e >> 16);
-            last_e = kNoEntry;
-            __builtin_amdgcn_wave_barrier();
+            walk.step(recs[cl * SV], recs[cl * SV + 1], have, cl * SV * 16u, kDummy, lds.s_list[wave], mylist, recs, bx0, by0,
+                      j0 + (uint32_t)c0 + 1u, lane);
         }
 #pragma unroll
         for (int q = 0; q < 5; ++q) running[q] += (uint32_t)(total >> (12 * q)) & 0xFFFu;
-        if (lane == 0) lds.done[wave] = alive == 0ull ? 1u : 0u;
+        if (lane == 0) lds.done[wave] = walk.alive == 0ull ? 1u : 0u;
         lds_barrier();                    // (3) the staging buffer is free again; the four votes are in
         if ((lds.done[0] & lds.done[1] & lds.done[2] & lds.done[3]) != 0u) break;       // block-uniform
     }
@@ -675,24 +611,14 @@ void pack_blend_chunked_kernel(
         // every wave is past barrier (3) of the last chunk (or never entered the loop): the staging buffer is free
         float colour[C];
 #pragma unroll
-        for (int c = 0; c < C; ++c) colour[c] = ((c & 1) ? accp[c / 2].y : accp[c / 2].x) + T * bg[c];
-        group_stats_epilogue<C>(st, reinterpret_cast<float*>(lds.s_rec), img, W, inside ? py * W + px : -1, wacc, colour);
+        for (int c = 0; c < C; ++c) colour[c] = walk.colour(c, bg);
+        group_stats_epilogue<C>(st, reinterpret_cast<float*>(lds.s_rec), img, W, inside ? py * W + px : -1, walk.wacc, colour);
     } else {
         if (tid == 0) {
 #pragma unroll
             for (int q = 0; q < 5; ++q) qcount[tile * 5 + q] = running[q];
         }
-        if (inside) {
-            const size_t plane = (size_t)W * H;
-            const size_t pix = (size_t)img * plane + (size_t)py * W + px;
-            float* oc = out_color + (size_t)img * (C - 1) * plane;
-#pragma unroll
-            for (int c = 0; c < C; ++c) oc[c * plane + pix] = ((c & 1) ? accp[c / 2].y : accp[c / 2].x) + T * bg[c];
-            out_depth[pix] = (C & 1) ? accp[C / 2].y : accp[C / 2].x;
-            out_alpha[pix] = wacc;
-            n_contrib[pix] = last;
-            final_T[pix] = T;
-        }
+        if (inside) walk.write_pixel(img, W, H, px, py, bg, out_color, out_depth, out_alpha, n_contrib, final_T);
         if (clear != nullptr) {           // kernel-uniform
             const unsigned long long per = (clear_units + gridDim.x - 1) / gridDim.x;
             const unsigned long long u0 = min(clear_units, (unsigned long long)blockIdx.x * per), u1 = min(clear_units, u0 + per);
@@ -804,7 +730,7 @@ __global__ __launch_bounds__(kBlock) void tiny_blend_kernel(int P, const uint32_
     }
     __syncthreads();
 
-    // ---- blend (A.3), one pixel per thread, same arithmetic as blend_rows_tile's consume ----------------------
+    // ---- blend (A.3), one pixel per thread, same arithmetic as QuadWalk::consume ----------------------------
     const int px = tx * kTile + (wave & 1) * 8 + (lane & 7);
     const int py = ty * kTile + (wave >> 1) * 8 + (lane >> 3);
     const bool inside = px < W && py < H;
@@ -1027,7 +953,7 @@ int stats_c(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& sa, const GeomSt
 // packs exactly what the first one did, only the feature channels of the records differ.  A caller that kept image_buffer,
 // sorted_rec and quad_list of such a pass (rasterizer.py: KeptPasses) re-renders with ONE launch: the stand-alone forward blend
 // walks the kept quadrant streams and takes channels [F0, C) of every record from the current per-Gaussian features
-// (blend_rows_tile<C, RF>).  (First version: a kernel that rewrote the channels inside the kept records, then the plain blend --
+// (blend_forward_rows_kernel<C, RF>).  (First version: a kernel that rewrote the channels inside the kept records, then the plain blend --
 // 0.13 ms at the bench scene for the read-modify-write of 24 bytes in every 80-byte record, against 0.32 ms for the blend.)
 template <int C>
 int reblend_c(const OgsRasterFwdArgs& a, const ImageState& is, hipStream_t s) {
@@ -1106,6 +1032,8 @@ int export_c(const OgsRasterFwdArgs& a, const ImageState& is, uint32_t* out, hip
     return OGS_OK;
 }
 
+constexpr const char* kBadC = "unsupported channel count C=%d";
+
 }  // namespace
 
 static bool tile_order_enabled() {
@@ -1140,65 +1068,31 @@ int launch_mfma_rank1_test(const float* w, const float* f, const float* acc0, in
 
 int launch_blend_forward(const OgsRasterFwdArgs& a, const GeomState& gs, const ImageState& is, int64_t D,
                          hipStream_t s, bool order_ready) {
-    switch (a.C) {
-        case 3: return launch_c<3>(a, gs, is, D, s, order_ready);
-        case 6: return launch_c<6>(a, gs, is, D, s, order_ready);
-        case 9: return launch_c<9>(a, gs, is, D, s, order_ready);
-        case 12: return launch_c<12>(a, gs, is, D, s, order_ready);
-        default: set_error("unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return launch_c<c()>(a, gs, is, D, s, order_ready); });
 }
 
 int launch_group_stats(const OgsRasterFwdArgs& a, const OgsGroupStatsArgs& st, const GeomState& gs, const ImageState& is,
                        hipStream_t s, bool order_ready) {
-    switch (a.C) {
-        case 3: return stats_c<3>(a, st, gs, is, s, order_ready);
-        case 6: return stats_c<6>(a, st, gs, is, s, order_ready);
-        case 9: return stats_c<9>(a, st, gs, is, s, order_ready);
-        case 12: return stats_c<12>(a, st, gs, is, s, order_ready);
-        default: set_error("unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return stats_c<c()>(a, st, gs, is, s, order_ready); });
 }
 
 int launch_compact_kept(int W, int H, int C, const ImageState& is_old, const ImageState& is_new, const void* old_rec,
                         const void* old_quad, void* new_rec, void* new_quad, hipStream_t s) {
-    switch (C) {
-        case 3: return compact_c<3>(W, H, is_old, is_new, old_rec, old_quad, new_rec, new_quad, s);
-        case 6: return compact_c<6>(W, H, is_old, is_new, old_rec, old_quad, new_rec, new_quad, s);
-        case 9: return compact_c<9>(W, H, is_old, is_new, old_rec, old_quad, new_rec, new_quad, s);
-        case 12: return compact_c<12>(W, H, is_old, is_new, old_rec, old_quad, new_rec, new_quad, s);
-        default: set_error("unsupported channel count C=%d", C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<12>(C, kBadC, [&](auto c) {
+        return compact_c<c()>(W, H, is_old, is_new, old_rec, old_quad, new_rec, new_quad, s);
+    });
 }
 
 int launch_reblend(const OgsRasterFwdArgs& a, const ImageState& is, hipStream_t s) {
-    switch (a.C) {
-        case 3: return reblend_c<3>(a, is, s);
-        case 6: return reblend_c<6>(a, is, s);
-        case 9: return reblend_c<9>(a, is, s);
-        case 12: return reblend_c<12>(a, is, s);
-        default: set_error("unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return reblend_c<c()>(a, is, s); });
 }
 
 int launch_tiny_blend(const OgsRasterFwdArgs& a, const GeomState& gs, const uint32_t* order, hipStream_t s) {
-    switch (a.C) {
-        case 3: return tiny_c<3>(a, gs, order, s);
-        case 6: return tiny_c<6>(a, gs, order, s);
-        case 9: return tiny_c<9>(a, gs, order, s);
-        case 12: return tiny_c<12>(a, gs, order, s);
-        default: set_error("unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return tiny_c<c()>(a, gs, order, s); });
 }
 
 int launch_export_n_contrib(const OgsRasterFwdArgs& a, const ImageState& is, uint32_t* out, hipStream_t s) {
-    switch (a.C) {
-        case 3: return export_c<3>(a, is, out, s);
-        case 6: return export_c<6>(a, is, out, s);
-        case 9: return export_c<9>(a, is, out, s);
-        case 12: return export_c<12>(a, is, out, s);
-        default: set_error("unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return export_c<c()>(a, is, out, s); });
 }
 
 }  // namespace ogs

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "../../include/ogs_raster.h"
 
@@ -74,6 +75,22 @@ constexpr const char* chan_name(const char* const (&names)[4]) {
     return C == 3 ? names[0] : C == 6 ? names[1] : C == 9 ? names[2] : names[3];
 }
 
+// Runtime channel count -> compile-time constant: f(std::integral_constant<int, C>) for C in {3, 6, 9, 12} up to MaxC (the
+// backward kernels stop at 9); anything else sets `unsupported_fmt` (one %d: the count) and returns OGS_ERR_UNSUPPORTED.
+template <int MaxC, class F>
+int dispatch_channels(int C, const char* unsupported_fmt, F&& f) {
+    static_assert(MaxC == 9 || MaxC == 12, "supported sets: {3, 6, 9} and {3, 6, 9, 12}");
+    switch (C) {
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 9: return f(std::integral_constant<int, 9>{});
+        case 12:
+            if constexpr (MaxC >= 12) return f(std::integral_constant<int, 12>{});
+            [[fallthrough]];
+        default: set_error(unsupported_fmt, C); return OGS_ERR_UNSUPPORTED;
+    }
+}
+
 // ---- scratch carving ------------------------------------------------------------------------
 constexpr size_t kAlign = 256;
 inline size_t align_up(size_t v, size_t a = kAlign) { return (v + a - 1) / a * a; }
@@ -98,8 +115,8 @@ struct Carver {
 //   f4[2..] = C blended feature channels, zero padded to a multiple of 4
 __host__ __device__ constexpr int rec_vec4(int C) { return 2 + (C + 3) / 4; }   // float4 per record
 
-// Per sorted-list-entry record read by the blend kernels through the scalar path (blend_fwd.hip):
-// 8 geometry floats (the last is the Gaussian id) + C features + depth, padded to float4.
+// Packed per-list-entry record ("stream record") written by the forward pack and read by every blend kernel:
+// 8 geometry floats (the last is the Gaussian id) + C features + depth, padded to float4 (layout: blend_fwd.hip).
 __host__ __device__ constexpr int stream_vec4(int C) { return (8 + C + 1 + 3) / 4; }
 
 // Blend-side layout (blend_fwd.hip): `sorted_rec` holds ONE packed record per entry of the sorted (Gaussian, tile)
@@ -120,8 +137,9 @@ constexpr float kFar = 3.0e18f;
 constexpr float kFarTest = 1.0e18f;
 
 typedef float f8 __attribute__((ext_vector_type(8)));
-// One stream record as the blend loops hold it: loaded from a WAVE-UNIFORM address, so hipcc emits
-// s_load_dwordx8 / s_load_dwordx4 and the fields live in SGPRs (operands of the per-pixel VALU math).
+// One stream record as the backward blend loops (blend_bwd.hip) hold it: loaded from a WAVE-UNIFORM address, so hipcc emits
+// s_load_dwordx8 / s_load_dwordx4 and the fields live in SGPRs (operands of the per-pixel VALU math).  The forward walk
+// (blend_fwd.hip) keeps its records in VGPRs instead.
 template <int C>
 struct StreamRec {
     static constexpr int NF4 = stream_vec4(C) - 2;
@@ -342,7 +360,8 @@ int launch_block_offsets(const OgsRasterFwdArgs& a, const GeomTmp& gt, hipStream
 int launch_tiny_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, uint32_t* order, hipStream_t s);
 int launch_small_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s);
 int launch_tiny_blend(const OgsRasterFwdArgs& a, const GeomState& gs, const uint32_t* order, hipStream_t s);
-// re-blend of a kept pass with new feature channels (blend_fwd.hip::refresh_features_kernel + the stand-alone forward blend)
+// re-blend of a kept pass with new feature channels: ONE launch of the stand-alone forward blend, which takes the replaced
+// channels from the caller's per-Gaussian features while it gathers the kept records (blend_forward_rows_kernel<C, RF>)
 int launch_reblend(const OgsRasterFwdArgs& a, const ImageState& is, hipStream_t s);
 // a finished pass' records and quadrant streams re-laid out by the ranges of what each tile packed (blend_fwd.hip)
 int launch_compact_kept(int W, int H, int C, const ImageState& is_old, const ImageState& is_new, const void* old_rec,
@@ -414,11 +433,12 @@ __device__ __forceinline__ float blend_power(float a2, float b2, float c2, float
 }
 
 // ---- record prefetch of the blend kernels --------------------------------------------------------------------------
-// The blend loops read the tile's record stream through the SCALAR path (blend_fwd.hip), two batches in flight per
-// wave: with the stream coming from HBM (written by pack just before, far larger than L2) the loops are bound by
-// the latency of those scalar loads, not by VALU issue.  At kernel entry the four waves of a tile therefore touch
-// every 128-byte line of the tile's record range with plain vector loads -- all issued at once, never waited for
-// until the kernel's last instruction -- which pulls the range towards the XCD's L2 ahead of the scalar loads.
+// The backward blend loops (blend_bwd.hip) read the tile's record stream through the SCALAR path, two batches in flight per
+// wave: with the stream coming from HBM (far larger than L2) the loops are bound by the latency of those scalar loads, not
+// by VALU issue.  At kernel entry the four waves of a tile therefore touch every 128-byte line of the tile's record range
+// with plain vector loads -- all issued at once, never waited for until the kernel's last instruction -- which pulls the
+// range towards the XCD's L2 ahead of the loads that need it.  The stand-alone forward blend (blend_forward_rows_kernel)
+// does the same ahead of its per-lane vector gathers.
 // `lines` = 128-byte lines per thread (0: off; tuning knob OGS_BLEND_PREFETCH), `sink` is opaque to the compiler.
 constexpr int kPrefetchMax = 4;
 struct RecordPrefetch {

@@ -451,12 +451,8 @@ int launch_sh_grad_from_views(int P, int V, int sh_degree, int sh_coeffs, const 
 
 int launch_preprocess_backward(const OgsRasterBwdArgs& a, const GeomState& gs, const void* grad_rec, hipStream_t s) {
     if (a.P <= 0) return OGS_OK;
-    switch (a.C) {
-        case 3: return launch_c<3>(a, gs, grad_rec, s);
-        case 6: return launch_c<6>(a, gs, grad_rec, s);
-        case 9: return launch_c<9>(a, gs, grad_rec, s);
-        default: set_error("backward: unsupported channel count C=%d", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<9>(a.C, "backward: unsupported channel count C=%d",
+                                [&](auto c) { return launch_c<c()>(a, gs, grad_rec, s); });
 }
 
 }  // namespace ogs

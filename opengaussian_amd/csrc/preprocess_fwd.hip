@@ -637,36 +637,20 @@ int launch_small_geometry_c(const OgsRasterFwdArgs& a, const GeomState& gs, cons
     return OGS_OK;
 }
 
+constexpr const char* kBadC = "unsupported channel count C=%d (3, 6, 9 or 12)";
+
 }  // namespace
 
 int launch_small_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s) {
-    switch (a.C) {
-        case 3: return launch_small_geometry_c<3>(a, gs, gt, s);
-        case 6: return launch_small_geometry_c<6>(a, gs, gt, s);
-        case 9: return launch_small_geometry_c<9>(a, gs, gt, s);
-        case 12: return launch_small_geometry_c<12>(a, gs, gt, s);
-        default: set_error("unsupported channel count C=%d (3, 6, 9 or 12)", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return launch_small_geometry_c<c()>(a, gs, gt, s); });
 }
 
 int launch_tiny_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, uint32_t* order, hipStream_t s) {
-    switch (a.C) {
-        case 3: return launch_tiny_geometry_c<3>(a, gs, order, s);
-        case 6: return launch_tiny_geometry_c<6>(a, gs, order, s);
-        case 9: return launch_tiny_geometry_c<9>(a, gs, order, s);
-        case 12: return launch_tiny_geometry_c<12>(a, gs, order, s);
-        default: set_error("unsupported channel count C=%d (3, 6, 9 or 12)", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return launch_tiny_geometry_c<c()>(a, gs, order, s); });
 }
 
 int launch_preprocess(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s) {
-    switch (a.C) {
-        case 3: return launch_preprocess_c<3>(a, gs, gt, s);
-        case 6: return launch_preprocess_c<6>(a, gs, gt, s);
-        case 9: return launch_preprocess_c<9>(a, gs, gt, s);
-        case 12: return launch_preprocess_c<12>(a, gs, gt, s);
-        default: set_error("unsupported channel count C=%d (3, 6, 9 or 12)", a.C); return OGS_ERR_UNSUPPORTED;
-    }
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return launch_preprocess_c<c()>(a, gs, gt, s); });
 }
 
 int launch_block_offsets(const OgsRasterFwdArgs& a, const GeomTmp& gt, hipStream_t s) {

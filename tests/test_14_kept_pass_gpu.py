@@ -86,6 +86,58 @@ def test_reblend_is_bit_identical_to_a_full_pass(kept, gpu_device):
     assert e.sorted_rec.numel() == int(R._lib.lib().ogs_raster_sorted_bytes(e.D, 9)) and e.nbytes == R.KEPT_PASSES.nbytes
 
 
+# The shared walk at its edges: 37 x 21 is 3 x 2 tiles whose right column and bottom row hold quadrants that lie wholly outside the
+# image (no pixel alive at entry: the feeders skip the stream) and quadrants that are partly covered.  P, f and the seed were chosen
+# on the CPU with oracle/raster_oracle.py alone (tiny_scene(6000, 37, 21, 60.0, seed=2), fp32 oracle): num_rendered = 11038; the
+# entries that contribute to some pixel before it stops number 874 / 716 / 390 / 415 / 426 / 191 per tile (every tile but the last
+# packs a second 256-entry chunk) and at least 191 per non-empty quadrant (a second 64-entry sub-chunk in the stand-alone blend);
+# all 777 pixels stop at T < 1e-4 (every tile leaves its list early), the smallest alpha is 0.99869, three pixels have alpha > 0.9999.
+# A stopped pixel keeps T >= 1e-4, so alpha = 1 - T passes 0.9999 by rounding of the fp32 sums only: the seed is one where it does.
+EDGE_P, EDGE_W, EDGE_H, EDGE_F, EDGE_SEED = 6000, 37, 21, 60.0, 2
+
+
+@pytest.mark.parametrize("sh_path", [True, False], ids=["sh_RF3", "precomputed_RF0"])
+def test_reblend_is_bit_identical_at_image_edges_over_second_chunks_and_stops(kept, gpu_device, sh_path):
+    """Re-blend (blend_forward_rows_kernel<9, RF>) against a full pass (pack_blend_chunked_kernel<9>), bit for bit, where the
+    sub-chunk step they share can go wrong: quadrants outside the image, a second chunk, a second sub-chunk, pixels that stop and
+    tiles that leave their list.  sh_path: SH colours in channels 0..2 + 6 caller channels (RF = 3); else 9 caller channels (RF = 0)."""
+    R, dev = kept, gpu_device
+    sc, cam = helpers.tiny_scene(EDGE_P, EDGE_W, EDGE_H, EDGE_F, seed=EDGE_SEED)
+    cam = cam.to(dev)
+    g = torch.Generator().manual_seed(3)
+    E = 6 if sh_path else 9
+    f0, f1 = (torch.rand(EDGE_P, E, generator=g).to(dev) for _ in range(2))
+    shs = sc.shs.to(dev) if sh_path else None
+    m3, m2 = sc.means3D.to(dev), torch.zeros(EDGE_P, 3, device=dev)
+    opac, scales, rots = sc.opacities.to(dev), sc.scales.to(dev), sc.rotations.to(dev)
+
+    def fused(feats, frozen_key, bg):
+        return R.rasterize_fused(m3, m2, opac, shs, feats, helpers.settings_for(cam, bg, 3, dev), scales=scales, rotations=rots,
+                                 detach_extra_from_geometry=False, frozen_key=frozen_key)
+
+    key = ("edge", ("v", 0), None)
+    before = R.PASS_STATS["reblend"]
+    miss = fused(f0.clone().requires_grad_(True), key, (0.1, 0.2, 0.3))           # requires_grad: the pass' grad_fn carries num_rendered
+    assert R.KEPT_PASSES.stats["admitted"] == 1 and R.PASS_STATS["reblend"] == before
+    e = next(iter(R.KEPT_PASSES.slots.values()))
+    tiles = ((EDGE_W + 15) // 16) * ((EDGE_H + 15) // 16)
+    num_rendered, alpha = int(miss[0].grad_fn.num_rendered), miss[3].detach()
+    print(f"num_rendered={num_rendered} kept={e.D} alpha: max={float(alpha.max()):.9f} min={float(alpha.min()):.9f} "
+          f"pixels>0.9999={int((alpha > 0.9999).sum())}")
+    # preconditions.  More than 256 records per tile on average: some tile kept more than one chunk, and of its four quadrant
+    # streams, which together hold every kept record at least once, one is longer than 64.
+    assert tiles == 6 and num_rendered >= e.D > 256 * tiles, (num_rendered, e.D)
+    assert bool((alpha > 0.9999).any()), float(alpha.max())                      # a pixel whose T sits at the stop's floor of 1e-4
+    assert float(alpha.min()) > 0.99                                             # no tile has a pixel that cannot have stopped
+    full = fused(f1, None, (0.7, 0.0, 0.4))
+    again = fused(f1, key, (0.7, 0.0, 0.4))
+    assert R.PASS_STATS["reblend"] == before + 1 and R.KEPT_PASSES.stats["hits"] == 1
+    assert full[0].shape == (9, EDGE_H, EDGE_W)
+    for a, b, what in zip(full, again, ("color", "radii", "depth", "alpha")):
+        assert torch.equal(a, b), what
+    assert not torch.equal(full[0], miss[0].detach())
+
+
 def test_reblend_feature_gradient_equals_the_full_pass(kept, gpu_device):
     R, dev = kept, gpu_device
     sc, cam, W, H = _scene(dev, seed=8)
