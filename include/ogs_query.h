@@ -1,0 +1,104 @@
+/*
+ * ogs_query.h -- C ABI of the open-vocabulary query step that follows `cluster_lang.npz`: text features to leaves
+ * (render_lerf_by_text.py:62,101-115), leaves to point classes and the confusion table behind mIoU / mAcc
+ * (scripts/eval_scannet.py:143-144,158-163 and calculate_metrics, :55-93), and the stable multi-split that turns
+ * OVERLAPPING leaf selections into group-contiguous row lists, so that all queries of a view go through one grouped
+ * rasterizer pass and one ogs_knn_group_ksum launch (the reference: one render() and one kNN filter per (text, frame),
+ * render_lerf_by_text.py:96-184).
+ *
+ * ---- similarity and selection (ogs_query_select) --------------------------------------------------------------------
+ * One workgroup per query row q of `text` [Q, D].  For every leaf k < K
+ *     sim[q, k] = leaf_valid[k] ? dot(text_q, leaf_k) / (max(|text_q|, 1e-12) * max(|leaf_k|, 1e-12)) : 0       fp32
+ * (F.normalize on both sides, then the dot product; a zero row gives 0; one product and one quotient, so that D = 1
+ * gives exactly +-1 as the normalised factors do).  leaf_valid == NULL: every leaf is valid.  The
+ * summation order is fixed, so two calls give the same bits; it is not torch's, so sim differs from a matmul by rounding
+ * (at most 2 * D * 2^-24 from the exact value).  The K similarities of a query stay in LDS for the ranking:
+ * K <= ogs_query_max_leaves(), above that the call returns OGS_ERR_UNSUPPORTED.  D is arbitrary (16-byte loads over the
+ * aligned part of every row, scalar loads for the rest).
+ * With top > 0 (top <= ogs_query_max_top()) the R = min(top, K) highest similarities are ranked descending, ties to the
+ * LOWER index, NaN never ranked.  selected[q, 0] = best = rank 0 (the argmax, lowest index on ties); every later rank c is
+ * appended, in rank order, when
+ *     (float)(c - best) < leaf_num      signed: every lower id qualifies (the reference's rule, kept as it is)   and
+ *     || centers[best] - centers[c] ||_2 < max_dist        fp32 over center_dim values, rows of `centers` [>= K, center_dim]
+ * selected [Q, top] int32 is padded with -1, count[q] = entries written.  top == 0: similarities only (selected, count,
+ * centers may be NULL).
+ *
+ * ---- point classes (ogs_query_classify) -----------------------------------------------------------------------------
+ * class_of_leaf[k] = argmax_t sim[t, k] over the T rows of sim [T, K], lowest t on ties (a zeroed leaf has an all-zero
+ * column: class 0), then pred[p] = class_of_leaf[min(max(leaf_ind[p], 0), K - 1)] + 1.  The reference clamps at K - 1
+ * only (:144); a negative id, which it would wrap, is clamped to 0 here and never addresses anything out of range.
+ *
+ * ---- confusion table (ogs_query_confusion) --------------------------------------------------------------------------
+ * conf [C, C] int64 (cleared by the call): conf[g, r] = points with label g and prediction r, after
+ *     g = ignore[p] ? 0 : gt[p]          (:131-132)          r = g == 0 ? 0 : pred[p]      (:58)
+ * Each workgroup counts ogs_query_confusion_block() consecutive points in an LDS table of C * C counters and adds its
+ * non-zero cells to `conf` with integer atomics: exact and deterministic.  C <= ogs_query_max_classes(), above that
+ * OGS_ERR_UNSUPPORTED.  A point whose g or r lies outside [0, C) is NOT counted (never an out-of-range LDS index); the
+ * Python wrapper checks the ranges before it calls.
+ *
+ * ---- stable multi-split (ogs_query_split_count / _scan / _scatter) ----------------------------------------------------
+ * member(p, q) = bit q of leaf_groups[leaf_ind[p]]  &&  row_ok[p] (NULL: all)  &&  group_keep[q] (NULL: all), for
+ * q < Q <= 64; a leaf id outside [0, K) (the k-means dummy id k1*k2, -1) is in no group.  The result is
+ *     begin [Q + 1] int32, rows [begin[Q]] int64:  rows[begin[q] .. begin[q + 1]) = the p with member(p, q), ASCENDING
+ * which is torch.nonzero(member[:, q]) group after group.  A point selected by several queries appears once per query.
+ * Three launches, none of which waits for another workgroup (no spin, no look-back):
+ *   count    workgroup b counts, per group, the members among its ogs_query_split_block() consecutive rows (row_ok
+ *            applied, group_keep not) into tmp
+ *   scan     ONE workgroup: exclusive prefix over (group, workgroup) of the counts of the kept groups -> tmp, begin;
+ *            counts [Q] = the group totals BEFORE group_keep (what a caller decides group_keep by); may be run again with
+ *            another group_keep over the same counts
+ *   scatter  workgroup b re-derives its members and writes each at its group's offset + the rank a wave ballot gives
+ * Every loop bound comes from the arguments, a leaf id is range-checked before it addresses leaf_groups (one outside
+ * [0, K) is dropped, not clamped: it is in no group; only ogs_query_classify clamps), and the scatter writes no row
+ * at or beyond `capacity`: a position past it (count and scatter called with different inputs) is dropped and reported
+ * through the library's sticky status word, i.e. ogs_check_async_status() returns OGS_ERR_DEVICE.
+ * Limits: Q <= 64 (OGS_ERR_UNSUPPORTED above), n * Q <= INT32_MAX (offsets are 32 bits; OGS_ERR_INVALID_ARG above).
+ * tmp: ogs_query_split_tmp_bytes(n, Q) bytes, carried from count to scatter.
+ *
+ * No entry point reads anything back from the device.  All pointers are device pointers, `stream` is a hipStream_t as
+ * void*.  Returns 0 or a negative OGS_ERR_* code.
+ */
+#ifndef OGS_QUERY_H
+#define OGS_QUERY_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+size_t ogs_query_max_leaves(void);        /* K limit of ogs_query_select: one query's similarities in LDS */
+size_t ogs_query_max_top(void);           /* top limit of ogs_query_select */
+size_t ogs_query_max_classes(void);       /* C limit of ogs_query_confusion */
+size_t ogs_query_confusion_block(void);   /* points per workgroup of ogs_query_confusion */
+size_t ogs_query_split_block(void);       /* rows per workgroup of the split */
+size_t ogs_query_split_tmp_bytes(int64_t n, int32_t Q);
+
+/* text [Q, D], leaf [K, D], leaf_valid [K] bytes or NULL, centers [>= K, center_dim]; sim [Q, K], selected [Q, top],
+ * count [Q] */
+int ogs_query_select(int32_t Q, int32_t K, int32_t D, const float* text, const float* leaf, const uint8_t* leaf_valid,
+                     const float* centers, int32_t center_dim, float leaf_num, float max_dist, int32_t top, float* sim,
+                     int32_t* selected, int32_t* count, void* stream);
+
+/* sim [T, K], leaf_ind [n]; class_of_leaf [K] int32, pred [n] int64 (n == 0: class_of_leaf only) */
+int ogs_query_classify(int64_t n, const int64_t* leaf_ind, int32_t K, int32_t T, const float* sim, int32_t* class_of_leaf,
+                       int64_t* pred, void* stream);
+
+/* gt [n], pred [n], ignore [n] bytes or NULL; conf [C, C] */
+int ogs_query_confusion(int64_t n, const int64_t* gt, const int64_t* pred, const uint8_t* ignore, int32_t C, int64_t* conf,
+                        void* stream);
+
+/* leaf_ind [n], leaf_groups [K], row_ok [n] bytes or NULL, group_keep [Q] bytes or NULL */
+int ogs_query_split_count(int64_t n, const int64_t* leaf_ind, int32_t K, const uint64_t* leaf_groups, const uint8_t* row_ok,
+                          int32_t Q, void* tmp, void* stream);
+int ogs_query_split_scan(int64_t n, int32_t Q, const uint8_t* group_keep, void* tmp, int32_t* begin, int32_t* counts,
+                         void* stream);
+int ogs_query_split_scatter(int64_t n, const int64_t* leaf_ind, int32_t K, const uint64_t* leaf_groups,
+                            const uint8_t* row_ok, int32_t Q, const uint8_t* group_keep, const void* tmp, int64_t* rows,
+                            int64_t capacity, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* OGS_QUERY_H */

@@ -154,6 +154,19 @@ SIGNATURES = {
                                            _vp]),
     "ogs_knn_tile_points": (C.c_size_t, []),
     "ogs_knn_group_ksum": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ogs_query_max_leaves": (C.c_size_t, []),
+    "ogs_query_max_top": (C.c_size_t, []),
+    "ogs_query_max_classes": (C.c_size_t, []),
+    "ogs_query_confusion_block": (C.c_size_t, []),
+    "ogs_query_split_block": (C.c_size_t, []),
+    "ogs_query_split_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "ogs_query_select": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_float, C.c_float,
+                                   C.c_int32, _vp, _vp, _vp, _vp]),
+    "ogs_query_classify": (C.c_int, [C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "ogs_query_confusion": (C.c_int, [C.c_int64, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
+    "ogs_query_split_count": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
+    "ogs_query_split_scan": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "ogs_query_split_scatter": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64, _vp]),
 }
 
 _lib = None

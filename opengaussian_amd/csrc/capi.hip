@@ -81,9 +81,10 @@ int take_async_status() {
 int check_async_status(const char* where) {
     const int st = take_async_status();
     if (st == 0) return OGS_OK;
-    set_error("%s: a kernel of an earlier launch reported status 0x%x%s -- the results of the passes since the last check "
+    set_error("%s: a kernel of an earlier launch reported status 0x%x%s%s -- the results of the passes since the last check "
               "are not valid", where, st,
-              (st & (int)kAsyncRadixSpin) ? " (one-launch radix pass: a look-back wait exceeded its bound)" : "");
+              (st & (int)kAsyncRadixSpin) ? " (one-launch radix pass: a look-back wait exceeded its bound)" : "",
+              (st & (int)kAsyncSplitOverflow) ? " (query split: the scatter met more rows than its capacity)" : "");
     return OGS_ERR_DEVICE;
 }
 
@@ -149,7 +150,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 405; }
+int ogs_version(void) { return 406; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 

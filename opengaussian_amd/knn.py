@@ -68,13 +68,20 @@ def _ksum_sorted(points, group, num_groups, k, want_kth=True):
     kk = kk.to(torch.int32).contiguous()
     if kk.shape != (G,):
         raise ValueError(f"k must be a number or [{G}] values")
-    begin32 = begin.to(torch.int32)
+    kth, sum1, sum2 = ksum_contiguous(pts, begin.to(torch.int32), kk, want_kth)
+    return order, gid, begin, kk, kth, sum1, sum2
+
+
+def ksum_contiguous(pts, begin32, kk, want_kth=False):
+    """The launch itself over rows that already lie group by group: pts [n, 3] fp32 contiguous, begin32 [G + 1] int32,
+    kk [G] int32.  Returns (kth or None, sum1, sum2); rows outside every group keep zeros."""
+    n, dev, G = pts.shape[0], pts.device, kk.numel()
     kth = torch.zeros(n, dtype=torch.float32, device=dev) if want_kth else None
     sum1 = torch.zeros(n, dtype=torch.float64, device=dev)
     sum2 = torch.zeros(n, dtype=torch.float64, device=dev)
     check(_lib.lib().ogs_knn_group_ksum(n, ptr(pts), G, ptr(begin32), ptr(kk), ptr(kth), ptr(sum1), ptr(sum2), _stream()),
           "ogs_knn_group_ksum")
-    return order, gid, begin, kk, kth, sum1, sum2
+    return kth, sum1, sum2
 
 
 def _unsort(t, order):
@@ -111,7 +118,16 @@ def outlier_mask(points: torch.Tensor, group=None, num_groups: int = 1, k_scale:
     only."""
     order, gid, begin, kk, _, sum1, sum2 = _ksum_sorted(points, group, num_groups,
                                                         lambda sizes: isqrt(sizes) * int(k_scale), want_kth=False)
-    G, dev = int(num_groups), points.device
+    return _unsort(keep_from_sums(gid, begin, kk, sum1, sum2, std_weight), order)
+
+
+def keep_from_sums(gid, begin, kk, sum1, sum2, std_weight: float = 1.0):
+    """The keep rule of ``outlier_mask`` over GROUP-SORTED rows, from what one ``ogs_knn_group_ksum`` launch left: gid [n]
+    group of every row (-1: none; None: all rows in group 0), begin [G + 1] row offsets, kk [G] the K handed to the kernel,
+    sum1 / sum2 [n] fp64 (sum1 is overwritten).  Shared with ``query.render_queries``, whose rows come out of the split
+    group by group and need no sort."""
+    G, dev = begin.numel() - 1, sum1.device
+    begin = begin.to(torch.int64)
     sizes = begin[1:] - begin[:-1]
     kd = torch.minimum(kk.to(torch.int64), sizes).to(torch.float64)                # the K the kernel used
     N = sizes.to(torch.float64) * kd
@@ -129,8 +145,7 @@ def outlier_mask(points: torch.Tensor, group=None, num_groups: int = 1, k_scale:
         return sum1 / kd < limit
     nan = torch.full((1,), float("nan"), dtype=torch.float64, device=dev)          # slot 0: nothing is below nan
     row_mean = sum1.div_(torch.cat((nan, kd)).index_select(0, slot))
-    keep = row_mean < torch.cat((nan, limit)).index_select(0, slot)
-    return _unsort(keep, order)
+    return row_mean < torch.cat((nan, limit)).index_select(0, slot)
 
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:

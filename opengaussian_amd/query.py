@@ -1,0 +1,407 @@
+"""Open-vocabulary queries on the GPU (include/ogs_query.h): what the reference does after ``cluster_lang.npz`` is written.
+
+``select_leaves_by_text``   every query text to its leaves in one launch (render_lerf_by_text.py:62,101-115)
+``classify_points``         leaf -> class -> point prediction (scripts/eval_scannet.py:143-144,158-163)
+``segmentation_metrics``    ``calculate_metrics`` (:55-93) from one confusion table instead of 4 x classes full-length
+                            reductions on the CPU; ``confusion_table`` / ``metrics_from_confusion`` are its two halves
+``multi_split``             rows of OVERLAPPING leaf selections, group by group, each group ascending
+``render_queries``          the object image and silhouette of every query of a view from one grouped rasterizer pass and
+                            one kNN launch, instead of one ``render(selected_leaf_id=...)`` call per query
+
+CPU tensors raise: there is no CPU path.
+"""
+from __future__ import annotations
+
+import math
+from collections import namedtuple
+
+import torch
+
+from . import _lib
+from . import knn as _knn
+from . import rasterizer as _rasterizer
+from . import renderer as _renderer
+from ._lib import check, ptr
+
+SPLIT_GROUPS = 64          # groups of one split: a bit each in a leaf's 64-bit word
+
+QueryRender = namedtuple("QueryRender", "images silhouettes kept counts")
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _need_gpu(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must live on the GPU (got {t.device}); the query kernels have no CPU path")
+
+
+def _f32(t):
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _i64(t):
+    return t.detach().to(torch.int64).contiguous()
+
+
+def _bytes(t):
+    return None if t is None else t.detach().to(torch.bool).contiguous().view(torch.uint8)
+
+
+# ---- text -> leaves -------------------------------------------------------------------------------------------------------
+def _similarity(text_feats, leaf_lang_feat, occu_count, min_occu, centers, leaf_num, max_dist, top):
+    _need_gpu(text_feats, "text_feats")
+    _need_gpu(leaf_lang_feat, "leaf_lang_feat")
+    if text_feats.dim() != 2 or leaf_lang_feat.dim() != 2 or text_feats.shape[1] != leaf_lang_feat.shape[1]:
+        raise ValueError(f"text_feats must be [Q, D] and leaf_lang_feat [K, D], got {tuple(text_feats.shape)} and "
+                         f"{tuple(leaf_lang_feat.shape)}")
+    (Q, D), K, dev = text_feats.shape, leaf_lang_feat.shape[0], text_feats.device
+    if K < 1 or D < 1:
+        raise ValueError(f"need at least one leaf and one feature, got K={K} D={D}")
+    lib = _lib.lib()
+    if K > lib.ogs_query_max_leaves():
+        raise ValueError(f"K={K} leaves: a query's similarities are ranked in LDS, at most {lib.ogs_query_max_leaves()}")
+    if top > lib.ogs_query_max_top():
+        raise ValueError(f"top={top}: at most {lib.ogs_query_max_top()}")
+    valid = None
+    if occu_count is not None:
+        if occu_count.shape != (K,):
+            raise ValueError(f"occu_count must be [{K}], got {tuple(occu_count.shape)}")
+        valid = _bytes(~(occu_count.to(dev) < min_occu))           # `feat[occu_count < min_occu] *= 0`
+    cd = 0
+    if top > 0:
+        if centers.dim() != 2 or centers.shape[0] < K:
+            raise ValueError(f"leaf_centers must be [>= {K}, C], got {tuple(centers.shape)}")
+        _need_gpu(centers, "leaf_centers")
+        centers, cd = _f32(centers), centers.shape[1]
+    sim = torch.empty(Q, K, dtype=torch.float32, device=dev)
+    selected = torch.empty(Q, top, dtype=torch.int32, device=dev) if top > 0 else None
+    count = torch.empty(Q, dtype=torch.int32, device=dev) if top > 0 else None
+    text, leaf = _f32(text_feats), _f32(leaf_lang_feat)
+    check(lib.ogs_query_select(Q, K, D, ptr(text), ptr(leaf), ptr(valid), ptr(centers if top > 0 else None), cd,
+                               float(leaf_num), float(max_dist), top, ptr(sim), ptr(selected), ptr(count), _stream()),
+          "ogs_query_select")
+    return sim, selected, count
+
+
+def select_leaves_by_text(text_feats, leaf_lang_feat, occu_count, leaf_centers, leaf_num, min_occu=5, top=10, max_dist=0.9):
+    """(sim [Q, K] fp32, selected [Q, top] int32, count [Q] int32) for all query texts at once.
+
+    Leaves with ``occu_count < min_occu`` are zeroed, both sides are normalised as ``F.normalize`` does, ``sim`` is the fp32
+    dot product.  ``selected[q, 0]`` is the argmax (lowest index on ties); the other ``min(top, K) - 1`` highest, ranked
+    descending with ties to the lowest index, are appended in rank order when ``candidate - best < leaf_num`` (signed, so
+    every lower id qualifies: the reference's rule, reproduced) and the fp32 distance of the two rows of ``leaf_centers``
+    (``leaf_code_book["ins_feat"]``, [K + 1, 6]) is below ``max_dist``; the rest of the row is -1.  ``leaf_num`` is the
+    reference's ``K / root_num``.  No read-back; K is limited to ``ogs_query_max_leaves()`` (8192), above that ValueError."""
+    if int(top) < 1:
+        raise ValueError("top must be at least 1")
+    return _similarity(text_feats, leaf_lang_feat, occu_count, min_occu, leaf_centers, leaf_num, max_dist, int(top))
+
+
+# ---- ScanNet point classes and metrics -----------------------------------------------------------------------------------------
+def classify_points(text_feats, leaf_lang_feat, occu_count, leaf_ind, min_occu=2):
+    """pred [N] int64 = ``argmax_t sim[t, leaf] + 1`` of every point's leaf, ``leaf_ind`` clamped at K - 1 (:144); leaves with
+    ``occu_count < min_occu`` are zeroed and therefore map to class 0 + 1.  Negative leaf ids clamp to 0."""
+    _need_gpu(leaf_ind, "leaf_ind")
+    if leaf_ind.dim() != 1:
+        raise ValueError(f"leaf_ind must be [N], got {tuple(leaf_ind.shape)}")
+    sim, _, _ = _similarity(text_feats, leaf_lang_feat, occu_count, min_occu, None, 0.0, 0.0, 0)
+    T, K = sim.shape
+    if T < 1:
+        raise ValueError("need at least one class text")
+    n, dev = leaf_ind.shape[0], sim.device
+    ind = _i64(leaf_ind)
+    cls = torch.empty(K, dtype=torch.int32, device=dev)
+    pred = torch.empty(n, dtype=torch.int64, device=dev)
+    check(_lib.lib().ogs_query_classify(n, ptr(ind), K, T, ptr(sim), ptr(cls), ptr(pred), _stream()), "ogs_query_classify")
+    return pred
+
+
+def confusion_table(gt, pred, total_classes, ignore=None):
+    """conf [C, C] int64 on the device: conf[g, r] = points with label g predicted r, after ``gt[ignore] = 0`` (:131-132) and
+    ``pred[gt == 0] = 0`` (:58).  Values outside [0, total_classes) AFTER those two rules raise ValueError (one min / max
+    read-back): a label under ``ignore`` and a prediction at an unlabelled point may hold anything."""
+    _need_gpu(gt, "gt")
+    _need_gpu(pred, "pred")
+    C = int(total_classes)
+    if gt.dim() != 1 or pred.shape != gt.shape or (ignore is not None and ignore.shape != gt.shape):
+        raise ValueError(f"gt, pred and ignore must be [N] alike, got {tuple(gt.shape)}, {tuple(pred.shape)}"
+                         + ("" if ignore is None else f", {tuple(ignore.shape)}"))
+    lib = _lib.lib()
+    if C < 1 or C > lib.ogs_query_max_classes():
+        raise ValueError(f"total_classes={C}: the table of a workgroup lives in LDS, 1 to {lib.ogs_query_max_classes()} classes")
+    n, dev = gt.shape[0], gt.device
+    g, r = _i64(gt), _i64(pred)
+    if n > 0:
+        # checked as they are counted: an ignored label is 0, a prediction at an unlabelled point is 0 (a sentinel such as -1
+        # there is overwritten by the reference too)
+        g_seen = g if ignore is None else g.masked_fill(ignore.to(dev).to(torch.bool), 0)
+        r_seen = r.masked_fill(g_seen == 0, 0)
+        lo_g, hi_g, lo_r, hi_r = torch.stack((g_seen.min(), g_seen.max(), r_seen.min(), r_seen.max())).tolist()
+        if lo_g < 0 or hi_g >= C or lo_r < 0 or hi_r >= C:
+            raise ValueError(f"gt in [{lo_g}, {hi_g}] / pred in [{lo_r}, {hi_r}] outside [0, {C})")
+    conf = torch.empty(C, C, dtype=torch.int64, device=dev)
+    ign = _bytes(None if ignore is None else ignore.to(dev))
+    check(lib.ogs_query_confusion(n, ptr(g), ptr(r), ptr(ign), C, ptr(conf), _stream()), "ogs_query_confusion")
+    return conf
+
+
+def metrics_from_confusion(conf):
+    """``(ious, mean_iou, accuracy, mean_class_accuracy)`` of ``calculate_metrics`` from its confusion table, with the
+    reference's arithmetic: per-class counts held in fp32 tensors, IoU and class accuracy fp32 quotients, the means over the
+    classes >= 1 that occur in ``gt`` (nan when there are none), ``accuracy`` a Python quotient of integers."""
+    conf = conf.detach().cpu().to(torch.int64)
+    C = conf.shape[0]
+    diag, row, col = conf.diagonal(), conf.sum(1), conf.sum(0)
+    intersection, union, total = torch.zeros(C), torch.zeros(C), torch.zeros(C)
+    intersection[1:] = diag[1:].to(torch.float32)
+    union[1:] = (row + col - diag)[1:].to(torch.float32)
+    total[1:] = row[1:].to(torch.float32)
+    ious = torch.zeros(C)
+    valid_union = union != 0
+    ious[valid_union] = intersection[valid_union] / union[valid_union]
+    present = torch.nonzero(row[1:] > 0).flatten() + 1
+    mean_iou = ious[present].mean().item()
+    correct, valid_points = int(diag[1:].sum()), int(row[1:].sum())
+    accuracy = correct / valid_points if valid_points > 0 else float("nan")
+    class_accuracy = intersection / total
+    return ious, mean_iou, accuracy, class_accuracy[present].mean().item()
+
+
+def segmentation_metrics(gt, pred, total_classes, ignore=None):
+    """``calculate_metrics(gt, pred, total_classes)`` of scripts/eval_scannet.py, ``ignore`` being its ``ignored_pts``: one
+    pass over the points on the GPU, one read-back of the [C, C] table, the same four results (``ious`` a CPU fp32 tensor)."""
+    return metrics_from_confusion(confusion_table(gt, pred, total_classes, ignore))
+
+
+# ---- the split ------------------------------------------------------------------------------------------------------------
+def _pad_selections(selections, dev):
+    """[Q, L] int64 ids padded with -1 from either form: a list of id tensors, or the (selected, count) pair"""
+    if isinstance(selections, (tuple, list)) and len(selections) == 2 and torch.is_tensor(selections[0]) \
+            and selections[0].dim() == 2:
+        selected, count = selections
+        if count.shape != (selected.shape[0],):
+            raise ValueError(f"count must be [{selected.shape[0]}], got {tuple(count.shape)}")
+        sel = selected.to(dev).to(torch.int64)
+        live = torch.arange(sel.shape[1], device=dev)[None, :] < count.to(dev)[:, None]
+        return torch.where(live, sel, torch.full_like(sel, -1))
+    rows = [torch.as_tensor(s).to(dev).to(torch.int64).flatten() for s in selections]
+    if any(torch.as_tensor(s).dim() > 1 for s in selections):
+        raise ValueError("every selection must be a 1-D tensor of leaf ids")
+    if not rows:
+        return torch.empty(0, 0, dtype=torch.int64, device=dev)
+    return torch.nn.utils.rnn.pad_sequence(rows, batch_first=True, padding_value=-1)
+
+
+def leaf_group_table(selections, num_leaves, device):
+    """[K, ceil(Q / 64)] int64 words, bit q % 64 of word q // 64 of row k set when query q lists leaf k; ids outside
+    [0, K) select nothing.  Built on the device, no read-back."""
+    sel = _pad_selections(selections, device)
+    Q, K = sel.shape[0], int(num_leaves)
+    W = max(1, (Q + SPLIT_GROUPS - 1) // SPLIT_GROUPS)
+    member = torch.zeros(K + 1, W * SPLIT_GROUPS, dtype=torch.bool, device=device)       # row K: the ids that select nothing
+    if sel.numel():
+        ids = torch.where((sel >= 0) & (sel < K), sel, torch.full_like(sel, K))
+        member[ids, torch.arange(Q, device=device)[:, None].expand_as(ids)] = True
+    bit = torch.ones(SPLIT_GROUPS, dtype=torch.int64, device=device) << torch.arange(SPLIT_GROUPS, device=device)
+    return (member[:K].view(K, W, SPLIT_GROUPS).to(torch.int64) * bit).sum(-1).contiguous(), Q
+
+
+class _Split:
+    """One split of up to 64 groups: count + scan at construction; ``scatter(group_keep)`` gives (begin, rows)."""
+
+    def __init__(self, leaf_ind, words, Q, row_ok):
+        self.lib, self.n, self.K, self.Q, self.dev = _lib.lib(), leaf_ind.shape[0], words.shape[0], int(Q), leaf_ind.device
+        self.leaf_ind, self.words, self.row_ok = leaf_ind, words, row_ok
+        self.tmp = torch.empty(self.lib.ogs_query_split_tmp_bytes(self.n, self.Q), dtype=torch.uint8, device=self.dev)
+        check(self.lib.ogs_query_split_count(self.n, ptr(leaf_ind), self.K, ptr(words), ptr(row_ok), self.Q, ptr(self.tmp),
+                                             _stream()), "ogs_query_split_count")
+        self.begin = torch.empty(self.Q + 1, dtype=torch.int32, device=self.dev)
+        self.counts = torch.empty(self.Q, dtype=torch.int32, device=self.dev)
+        self._scan(None)
+
+    def _scan(self, keep):
+        check(self.lib.ogs_query_split_scan(self.n, self.Q, ptr(keep), ptr(self.tmp), ptr(self.begin), ptr(self.counts),
+                                            _stream()), "ogs_query_split_scan")
+
+    def scatter(self, group_keep, total):
+        """rows [total] int64 and begin [Q + 1] int32 for the kept groups; `total` = the sum of their counts, which the
+        caller has read (the scatter writes nothing at or past it)."""
+        keep = _bytes(group_keep)
+        if keep is not None:
+            self._scan(keep)
+        rows = torch.empty(int(total), dtype=torch.int64, device=self.dev)
+        check(self.lib.ogs_query_split_scatter(self.n, ptr(self.leaf_ind), self.K, ptr(self.words), ptr(self.row_ok), self.Q,
+                                               ptr(keep), ptr(self.tmp), ptr(rows), int(total), _stream()),
+              "ogs_query_split_scatter")
+        return self.begin, rows
+
+
+def multi_split(leaf_ind, leaf_groups, num_groups, row_ok=None, group_keep=None):
+    """(begin [Q + 1] int64, rows int64, counts [Q] int64): ``rows[begin[q]:begin[q + 1]]`` is
+    ``torch.nonzero(member[:, q]).flatten()``, ascending, with ``member[p, q] = bit q of leaf_groups[leaf_ind[p]] & row_ok[p]
+    & group_keep[q]``; ``counts`` are the group sizes BEFORE ``group_keep``.  ``leaf_groups`` is [K] or [K, ceil(Q / 64)]
+    int64 words (``leaf_group_table``); leaf ids outside [0, K) are in no group.  More than 64 groups run as one split per
+    64.  One read-back of the counts per split (the size of ``rows``)."""
+    _need_gpu(leaf_ind, "leaf_ind")
+    _need_gpu(leaf_groups, "leaf_groups")
+    Q = int(num_groups)
+    words = leaf_groups.reshape(leaf_groups.shape[0], -1)
+    if leaf_ind.dim() != 1 or words.dtype != torch.int64 or words.shape[1] * SPLIT_GROUPS < Q:
+        raise ValueError(f"leaf_ind must be [N] and leaf_groups [K, >= {(Q + 63) // 64}] int64, got {tuple(leaf_ind.shape)} and "
+                         f"{tuple(leaf_groups.shape)} {leaf_groups.dtype}")
+    if row_ok is not None and row_ok.shape != leaf_ind.shape:
+        raise ValueError(f"row_ok must be [{leaf_ind.shape[0]}], got {tuple(row_ok.shape)}")
+    if group_keep is not None and group_keep.shape != (Q,):
+        raise ValueError(f"group_keep must be [{Q}], got {tuple(group_keep.shape)}")
+    dev = leaf_ind.device
+    ind, ok = _i64(leaf_ind), _bytes(row_ok)
+    begins, rows, counts, base = [torch.zeros(1, dtype=torch.int64, device=dev)], [], [], 0
+    for c0 in range(0, Q, SPLIT_GROUPS):
+        qc = min(SPLIT_GROUPS, Q - c0)
+        sp = _Split(ind, words[:, c0 // SPLIT_GROUPS].contiguous(), qc, ok)
+        keep = None if group_keep is None else group_keep[c0:c0 + qc].to(dev).to(torch.bool)
+        cnt = sp.counts.to(torch.int64)
+        total = int((cnt if keep is None else cnt * keep).sum())                       # the read-back
+        b, r = sp.scatter(keep, total)
+        begins.append(b[1:].to(torch.int64) + base)
+        rows.append(r)
+        counts.append(cnt)
+        base += total
+    check(_lib.lib().ogs_check_async_status(), "ogs_check_async_status")
+    if not rows:
+        return begins[0], torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
+    return torch.cat(begins), torch.cat(rows), torch.cat(counts)
+
+
+# ---- all queries of a view ------------------------------------------------------------------------------------------------------
+def _visible(means3D, opacity, settings, scales, rotations, cov3D):
+    """radii > 0 of the view's pass; a radius does not depend on colour, the means stand in for the [P, 3] colour input"""
+    return _rasterizer.visible_radii(means3D, opacity, settings, means3D, scales=scales, rotations=rotations,
+                                     cov3D_precomp=cov3D) > 0
+
+
+def _render_groups(local, num, settings, means3D, opacity, scales, rotations, cov3D, shs, colors):
+    """Images of the subsets {r : local[r] == g}, g < num, of the given rows: the plain pass on the indexed subset for one
+    subset (what render() does for a selection), one grouped pass otherwise.  -> (colour list, alpha list)
+
+    The one-subset / grouped branch restates renderer._render_subsets (on gathered rows and without its mask bookkeeping);
+    the images are bit-equal to render()'s only while the two make the same rasterizer calls, so change them together."""
+    pick = lambda t, m: None if t is None else t[m]
+    means2D = torch.zeros_like(means3D)
+    if num == 1:
+        m = local == 0
+        color, _, _, alpha = _rasterizer.GaussianRasterizer(settings)(
+            means3D=means3D[m], means2D=means2D[m], shs=pick(shs, m), colors_precomp=pick(colors, m), opacities=opacity[m],
+            scales=pick(scales, m), rotations=pick(rotations, m), cov3D_precomp=pick(cov3D, m))
+        return [color], [alpha]
+    color, _, _, alpha = _rasterizer.rasterize_groups(means3D, means2D, opacity, local, num, settings, shs=shs,
+                                                      colors_precomp=colors, scales=scales, rotations=rotations,
+                                                      cov3D_precomp=cov3D)
+    return list(color.unbind(0)), list(alpha.unbind(0))
+
+
+@torch.no_grad()
+def render_queries(view, pc, pipe, bg, iteration, leaf_cluster_idx, selections, pre_mask=None, better_vis=True, seg_rgb=True,
+                   post_process=True, root_num=64, leaf_num=10, num_leaves=None):
+    """Object image and silhouette of every query of one view: for each q what
+
+        render(view, pc, pipe, bg, iteration, rescale=False, leaf_cluster_idx=leaf_cluster_idx,
+               selected_leaf_id=selections[q], render_feat_map=False, render_cluster=False, better_vis=..., seg_rgb=...,
+               post_process=..., pre_mask=..., root_num=..., leaf_num=...)
+
+    returns as ``leaf_clusters_imgs[0]`` (its first three channels when ``seg_rgb``) and ``leaf_cluster_silhouettes[0]``, or
+    None where that call returns empty lists -- bit for bit, from one preprocess, one split, one kNN launch and one grouped
+    rasterizer pass per 64 queries instead of one of each per query.  Forward only (no autograd graph).
+
+    ``selections``: a list of 1-D leaf-id tensors, or the ``(selected, count)`` pair of ``select_leaves_by_text``.  An empty
+    selection renders nothing (None).  ``num_leaves``: size of the leaf table, default ``root_num * leaf_num + 1`` (the k-means
+    dummy id included); ids beyond it select nothing.
+
+    Returns ``QueryRender(images, silhouettes, kept, counts)``: lists of Q entries; ``counts[q]`` is the number of Gaussians
+    of query q left after the row filters (0 when the `< 100` rule dropped it), ``kept[q]`` whether it was rendered
+    (``counts[q] >= 10``).  Host read-backs per 64 queries: the group counts after the split, the group counts after the kNN
+    filter (only with ``post_process``), and the rasterizer's own list-length read per pass -- none grows with Q."""
+    xyz = pc.get_xyz
+    _need_gpu(xyz, "the model")
+    _need_gpu(leaf_cluster_idx, "leaf_cluster_idx")
+    dev, P = xyz.device, xyz.shape[0]
+    if leaf_cluster_idx.shape != (P,):
+        raise ValueError(f"leaf_cluster_idx must be [{P}], got {tuple(leaf_cluster_idx.shape)}")
+    if pre_mask is not None and pre_mask.shape != (P,):
+        raise ValueError(f"pre_mask must be [{P}], got {tuple(pre_mask.shape)}")
+    settings = _rasterizer.GaussianRasterizationSettings(
+        image_height=int(view.image_height), image_width=int(view.image_width), tanfovx=math.tan(view.FoVx * 0.5),
+        tanfovy=math.tan(view.FoVy * 0.5), bg=bg, scale_modifier=1.0, viewmatrix=view.world_view_transform,
+        projmatrix=view.full_proj_transform, sh_degree=pc.active_sh_degree, campos=view.camera_center, prefiltered=False,
+        debug=pipe.debug)
+    means3D, opacity = xyz.detach(), pc.get_opacity.detach()
+    scales = rotations = cov3D = None
+    if pipe.compute_cov3D_python:
+        cov3D = pc.get_covariance(1.0).detach()
+    else:
+        scales, rotations = pc.get_scaling.detach(), pc.get_rotation.detach()
+    if better_vis and scales is None:
+        raise ValueError("better_vis filters by the scales: not available with pipe.compute_cov3D_python")
+    shs = colors = None
+    if seg_rgb:
+        if pipe.convert_SHs_python:
+            raise ValueError("seg_rgb renders from the SH coefficients: not available with pipe.convert_SHs_python")
+        shs = pc.get_features.detach()
+    else:
+        colors = ((pc.get_ins_feat(origin=False) + 1) / 2).detach()
+
+    K = int(num_leaves) if num_leaves is not None else int(round(float(root_num) * float(leaf_num))) + 1
+    table, Q = leaf_group_table(selections, K, dev)
+    images, sils, kept_all, counts_all = [None] * Q, [None] * Q, [False] * Q, [0] * Q
+    if Q == 0 or P == 0:
+        return QueryRender(images, sils, kept_all, counts_all)
+
+    row_ok = _visible(means3D, opacity, settings, scales, rotations, cov3D)
+    occ = getattr(view, "bClusterOccur", None)
+    if occ is not None and occ[None] == False:                                   # noqa: E712  render() :284-285, as it stands
+        row_ok = torch.zeros_like(row_ok)
+    if pre_mask is not None:
+        row_ok = row_ok & pre_mask.to(dev)
+    if better_vis:                                                               # small Gaussians only (:293-296)
+        row_ok = row_ok & (scales < 0.1).all(dim=1)
+    ind, ok = _i64(leaf_cluster_idx), _bytes(row_ok)
+    per_pass = int(_renderer.GROUPS_PER_PASS)
+
+    for c0 in range(0, Q, SPLIT_GROUPS):
+        qc = min(SPLIT_GROUPS, Q - c0)
+        sp = _Split(ind, table[:, c0 // SPLIT_GROUPS].contiguous(), qc, ok)
+        cnt = sp.counts.tolist()                                                 # read-back 1: the Q counts
+        keep = [(c >= 100 if better_vis else c > 0) for c in cnt]                # at least 100 per query (:295)
+        sizes = [c if k else 0 for c, k in zip(cnt, keep)]
+        total = sum(sizes)
+        if total == 0:
+            continue
+        begin32, rows = sp.scatter(None if all(keep) else torch.tensor(keep, device=dev), total)
+        sizes_t = torch.tensor(sizes, dtype=torch.int64, device=dev)
+        gid = torch.repeat_interleave(torch.arange(qc, device=dev), sizes_t, output_size=total)
+        g_means = means3D[rows]
+        if post_process:                                                         # the kNN filter of every query, one launch
+            kk = _knn.isqrt(sizes_t).to(torch.int32)                            # K = int(n ** 0.5) per query (:298)
+            _, s1, s2 = _knn.ksum_contiguous(_f32(g_means), begin32, kk)
+            ok_rows = _knn.keep_from_sums(gid, begin32, kk, s1, s2)
+            gid = torch.where(ok_rows, gid, torch.full_like(gid, -1))
+            left = torch.zeros(qc + 1, dtype=torch.int64, device=dev).index_add_(0, gid + 1, torch.ones_like(gid))
+            sizes = left[1:].tolist()                                            # read-back 2
+        check(_lib.lib().ogs_check_async_status(), "ogs_check_async_status")
+        drawn = [q for q in range(qc) if sizes[q] >= 10]                         # at least 10 per query (:313)
+        for q in range(qc):
+            counts_all[c0 + q], kept_all[c0 + q] = int(sizes[q]), sizes[q] >= 10
+        pick = lambda t: None if t is None else t[rows]
+        g = dict(means3D=g_means, opacity=opacity[rows], scales=pick(scales), rotations=pick(rotations), cov3D=pick(cov3D),
+                 shs=pick(shs), colors=pick(colors))
+        for p0 in range(0, len(drawn), per_pass):
+            chunk = drawn[p0:p0 + per_pass]
+            remap = torch.full((qc + 1,), -1, dtype=torch.int32, device=dev)
+            remap[torch.tensor(chunk, device=dev)] = torch.arange(len(chunk), dtype=torch.int32, device=dev)
+            local = remap[torch.where(gid >= 0, gid, torch.full_like(gid, qc))]
+            imgs, alphas = _render_groups(local, len(chunk), settings, **g)
+            for q, img, alpha in zip(chunk, imgs, alphas):
+                images[c0 + q], sils[c0 + q] = img, alpha
+    return QueryRender(images, sils, kept_all, counts_all)
