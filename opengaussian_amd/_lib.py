@@ -69,6 +69,15 @@ class OgsGroupStatsArgs(C.Structure):
                 ("count", _vp), ("feat_sum", _vp), ("stats_tmp", _vp)]
 
 
+class OgsRawModel(C.Structure):
+    """include/ogs_model.h: the reference model's raw parameters."""
+    _fields_ = [("features_dc", _vp), ("features_rest", _vp), ("scaling", _vp), ("rotation", _vp), ("opacity", _vp)]
+
+
+class OgsRawModelGrads(C.Structure):
+    _fields_ = [("features_dc", _vp), ("features_rest", _vp), ("scaling", _vp), ("rotation", _vp), ("opacity", _vp)]
+
+
 # name -> (restype, argtypes); also the list the symbol-export test checks against the headers
 SIGNATURES = {
     "ogs_version": (C.c_int, []),
@@ -102,6 +111,11 @@ SIGNATURES = {
     "ogs_selftest_tile_order": (C.c_int, [_vp, C.c_int64, _vp, _vp]),
     "ogs_selftest_radix_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "ogs_selftest_radix_sort": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "ogs_raster_forward_geometry_raw": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsRawModel), _vp,
+                                                  C.POINTER(C.c_int64)]),
+    "ogs_raster_forward_tiny_raw": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsRawModel), _vp]),
+    "ogs_raster_backward_raw": (C.c_int, [C.POINTER(OgsRasterBwdArgs), C.POINTER(OgsRawModel), C.POINTER(OgsRawModelGrads), _vp]),
+    "ogs_model_activate": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(OgsRawModel), _vp, _vp, _vp, _vp, _vp]),
     "ogs_check_async_status": (C.c_int, []),
     "ogs_prof_enable": (C.c_int, [C.c_int]),
     "ogs_prof_filter": (C.c_int, [C.c_char_p]),

@@ -144,6 +144,41 @@ static int validate_fwd(const OgsRasterFwdArgs* a, bool images = true) {
     return OGS_OK;
 }
 
+// ---- raw-model entries (include/ogs_model.h) ------------------------------------------------------------------------------
+// The per-Gaussian kernels take the raw model through the pointer slots the args structs already have -- shs = features_dc
+// (non-NULL, so every `shs != NULL` test in the library keeps meaning "channels 0..2 come from SH"), cov3D_precomp = features_rest
+// (a raw pass has no precomputed covariance), opacities / scales / rotations = the raw arrays -- and a template switch that makes
+// them read those slots through ogs_model_act.h.  The copies below are what the launchers get; the callers' structs are
+// checked to have all five slots NULL.
+static int validate_raw(const OgsRawModel* raw, int P, int M) {
+    if (!raw) { set_error("raw == NULL"); return OGS_ERR_INVALID_ARG; }
+    if (M < 1) { set_error("raw model: sh_coeffs=%d < 1", M); return OGS_ERR_INVALID_ARG; }
+    if (P > 0 && (!raw->features_dc || !raw->scaling || !raw->rotation || !raw->opacity)) {
+        set_error("raw model: NULL features_dc / scaling / rotation / opacity"); return OGS_ERR_INVALID_ARG;
+    }
+    if (P > 0 && M > 1 && !raw->features_rest) { set_error("raw model: features_rest == NULL with %d SH coefficients", M); return OGS_ERR_INVALID_ARG; }
+    return OGS_OK;
+}
+
+static int raw_fwd_args(const OgsRasterFwdArgs* a, const OgsRawModel* raw, OgsRasterFwdArgs* out) {
+    if (!a) { set_error("args == NULL"); return OGS_ERR_INVALID_ARG; }
+    if (a->shs || a->opacities || a->scales || a->rotations || a->cov3D_precomp) {
+        set_error("raw pass: args.shs / opacities / scales / rotations / cov3D_precomp must be NULL (the raw model takes their place)");
+        return OGS_ERR_INVALID_ARG;
+    }
+    int rc = validate_raw(raw, a->P, a->sh_coeffs);
+    if (rc != OGS_OK) return rc;
+    *out = *a;
+    out->shs = raw->features_dc;
+    out->opacities = raw->opacity;
+    out->scales = raw->scaling;
+    out->rotations = raw->rotation;
+    if (a->P == 0) {                     // nothing is read per Gaussian; the argument check wants a colour source and a covariance form
+        out->shs = out->scales = out->rotations = a->bg;
+    }
+    return OGS_OK;
+}
+
 }  // namespace ogs
 
 using namespace ogs;
@@ -216,9 +251,15 @@ size_t ogs_raster_quad_list_bytes(int64_t D) {
 }
 size_t ogs_raster_backward_tmp_bytes(int32_t P) { return align_up((size_t)(P > 0 ? P : 1) * 16 * sizeof(double)); }
 
-int ogs_raster_forward_geometry(const OgsRasterFwdArgs* a, void* stream_, int64_t* num_rendered_host) {
-    int rc = validate_fwd(a, /*images=*/false);        // the images are written by the render phase only
+// raw_rest: NULL for the existing entry; otherwise `a` is raw_fwd_args' copy and this is the raw model's features_rest (which may
+// itself be NULL when M == 1: `raw` says which form runs)
+static int forward_geometry_impl(const OgsRasterFwdArgs* a_in, void* stream_, int64_t* num_rendered_host, bool raw,
+                                 const float* raw_rest) {
+    int rc = validate_fwd(a_in, /*images=*/false);        // the images are written by the render phase only
     if (rc != OGS_OK) return rc;
+    OgsRasterFwdArgs a_raw;
+    const OgsRasterFwdArgs* a = a_in;
+    if (raw) { a_raw = *a_in; a_raw.cov3D_precomp = raw_rest; a = &a_raw; }      // after the check: the slot is not a covariance
     hipStream_t s = static_cast<hipStream_t>(stream_);
     if (num_rendered_host) *num_rendered_host = 0;
     if (a->P == 0) return OGS_OK;
@@ -228,14 +269,14 @@ int ogs_raster_forward_geometry(const OgsRasterFwdArgs* a, void* stream_, int64_
     const GeomTmp gt = GeomTmp::carve(a->geom_tmp, a->P);
     if (a->P <= kSmallMaxP) {
         // small pass: preprocess + depth order + scan in ONE single-workgroup launch instead of 15 (preprocess_fwd.hip)
-        rc = launch_small_geometry(*a, gs, gt, s);
+        rc = launch_small_geometry(*a, gs, gt, s, raw);
         if (rc != OGS_OK) return rc;
     } else if (per_tile_depth_order(*a)) {
         // no depth sort: duplicate walks the Gaussians in index order and every tile's list is sorted by depth in the render
         // phase (tile_depth_sort_kernel, which gathers keys[0] as preprocess leaves it).  A culled Gaussian has tiles_touched 0,
         // so the scan and duplicate pass over it.  offsets[i] = exclusive scan of tiles_touched; total = num_rendered
         // (full-list passes; a default pass leaves offsets[] unwritten, see below)
-        rc = launch_preprocess(*a, gs, gt, s);
+        rc = launch_preprocess(*a, gs, gt, s, raw);
         if (rc != OGS_OK) return rc;
         // default mode: preprocess left one sum per workgroup, one small launch makes them offsets and the total, and duplicate
         // scans its own 256 counts (block_sum_offsets); the full-list export keeps the scan
@@ -243,7 +284,7 @@ int ogs_raster_forward_geometry(const OgsRasterFwdArgs* a, void* stream_, int64_
                                    : exclusive_scan_u32(gt.tiles_touched, nullptr, gt.offsets, a->P, gt.num_rendered, gt.sort_tmp, s, a->debug);
         if (rc != OGS_OK) return rc;
     } else {
-        rc = launch_preprocess(*a, gs, gt, s);
+        rc = launch_preprocess(*a, gs, gt, s, raw);
         if (rc != OGS_OK) return rc;
         // grouped pass (up to 2^31 virtual tiles of a few entries each: the lists are not sorted one by one, the Gaussians are
         // sorted once): depth sort of the Gaussians that are drawn, 4 x 8-bit stable passes, ends in keys[0]/order[0].  A Gaussian that is
@@ -279,6 +320,29 @@ int ogs_raster_forward_geometry(const OgsRasterFwdArgs* a, void* stream_, int64_
         if (rc != OGS_OK) return rc;
     }
     return OGS_OK;
+}
+
+int ogs_raster_forward_geometry(const OgsRasterFwdArgs* a, void* stream_, int64_t* num_rendered_host) {
+    return forward_geometry_impl(a, stream_, num_rendered_host, false, nullptr);
+}
+
+int ogs_raster_forward_geometry_raw(const OgsRasterFwdArgs* a, const OgsRawModel* raw, void* stream_, int64_t* num_rendered_host) {
+    OgsRasterFwdArgs b;
+    const int rc = raw_fwd_args(a, raw, &b);
+    if (rc != OGS_OK) return rc;
+    return forward_geometry_impl(&b, stream_, num_rendered_host, true, raw->features_rest);
+}
+
+int ogs_model_activate(int32_t P, int32_t M, const OgsRawModel* raw, float* scales, float* rotations, float* opacities, float* shs,
+                       void* stream_) {
+    if (P < 0) { set_error("model_activate: P=%d", P); return OGS_ERR_INVALID_ARG; }
+    if (P == 0) return OGS_OK;
+    if (!raw) { set_error("model_activate: raw == NULL"); return OGS_ERR_INVALID_ARG; }
+    if ((scales && !raw->scaling) || (rotations && !raw->rotation) || (opacities && !raw->opacity) ||
+        (shs && (M < 1 || !raw->features_dc || (M > 1 && !raw->features_rest)))) {
+        set_error("model_activate: an output is requested whose raw input is NULL (M=%d)", M); return OGS_ERR_INVALID_ARG;
+    }
+    return launch_model_activate(P, M, *raw, scales, rotations, opacities, shs, static_cast<hipStream_t>(stream_));
 }
 
 // A one-thread kernel storing the word into the mapped pinned buffer instead of this 4-byte copy was tried (round 3: the copy costs
@@ -443,20 +507,32 @@ size_t ogs_raster_tile_sort_capacity(int32_t level) {
     return level == 0 ? (size_t)kWaveSortCap : level == 1 ? (size_t)kTileSortCap : 0;
 }
 
-int ogs_raster_forward_tiny(const OgsRasterFwdArgs* a, void* stream_) {
-    int rc = validate_fwd(a);
+static int forward_tiny_impl(const OgsRasterFwdArgs* a_in, void* stream_, bool raw, const float* raw_rest) {
+    int rc = validate_fwd(a_in);
     if (rc != OGS_OK) return rc;
+    OgsRasterFwdArgs a_raw;
+    const OgsRasterFwdArgs* a = a_in;
+    if (raw) { a_raw = *a_in; a_raw.cov3D_precomp = raw_rest; a = &a_raw; }
     if (a->P <= 0 || a->P > kTinyMaxP) { set_error("forward_tiny: P=%d outside [1, %d]", a->P, kTinyMaxP); return OGS_ERR_INVALID_ARG; }
     if (a->num_groups > 1) { set_error("forward_tiny: grouped passes use the streaming path"); return OGS_ERR_UNSUPPORTED; }
     hipStream_t s = static_cast<hipStream_t>(stream_);
     const GeomState gs = GeomState::carve(a->geom_buffer, a->P, a->C);
     uint32_t* order = static_cast<uint32_t*>(a->geom_tmp);        // [P] depth order; geom_tmp >= ogs_raster_geom_tmp_bytes(P)
-    rc = launch_tiny_geometry(*a, gs, order, s);
+    rc = launch_tiny_geometry(*a, gs, order, s, raw);
     if (rc != OGS_OK) return rc;
     return launch_tiny_blend(*a, gs, order, s);
 }
 
-int ogs_raster_backward(const OgsRasterBwdArgs* a, void* stream_) {
+int ogs_raster_forward_tiny(const OgsRasterFwdArgs* a, void* stream_) { return forward_tiny_impl(a, stream_, false, nullptr); }
+
+int ogs_raster_forward_tiny_raw(const OgsRasterFwdArgs* a, const OgsRawModel* raw, void* stream_) {
+    OgsRasterFwdArgs b;
+    const int rc = raw_fwd_args(a, raw, &b);
+    if (rc != OGS_OK) return rc;
+    return forward_tiny_impl(&b, stream_, true, raw->features_rest);
+}
+
+static int backward_impl(const OgsRasterBwdArgs* a, void* stream_, const OgsRawModelGrads* raw_grads) {
     if (!a) { set_error("args == NULL"); return OGS_ERR_INVALID_ARG; }
     if (a->C != 3 && a->C != 6 && a->C != 9) { set_error("backward: C=%d unsupported (3, 6, 9)", a->C); return OGS_ERR_UNSUPPORTED; }
     if (a->P == 0) return OGS_OK;
@@ -493,7 +569,37 @@ int ogs_raster_backward(const OgsRasterBwdArgs* a, void* stream_) {
     if (a->num_rendered > 0 && (!a->sorted_rec || !a->quad_list)) { set_error("backward: sorted_rec / quad_list == NULL"); return OGS_ERR_INVALID_ARG; }
     int rc = launch_blend_backward(*a, is, grad_rec, s);
     if (rc != OGS_OK) return rc;
-    return launch_preprocess_backward(*a, gs, grad_rec, s);
+    return launch_preprocess_backward(*a, gs, grad_rec, s, raw_grads);
+}
+
+int ogs_raster_backward(const OgsRasterBwdArgs* a, void* stream_) { return backward_impl(a, stream_, nullptr); }
+
+int ogs_raster_backward_raw(const OgsRasterBwdArgs* a, const OgsRawModel* raw, const OgsRawModelGrads* grads, void* stream_) {
+    if (!a) { set_error("args == NULL"); return OGS_ERR_INVALID_ARG; }
+    if (a->shs || a->opacities || a->scales || a->rotations || a->cov3D_precomp || a->dL_dsh || a->dL_dopacity || a->dL_dscales ||
+        a->dL_drotations || a->dL_dcov3D) {
+        set_error("raw backward: args.shs / opacities / scales / rotations / cov3D_precomp and their dL_d* outputs must be NULL "
+                  "(the raw model and its gradient struct take their place)");
+        return OGS_ERR_INVALID_ARG;
+    }
+    const int rc = validate_raw(raw, a->P, a->sh_coeffs);
+    if (rc != OGS_OK) return rc;
+    static const OgsRawModelGrads kNoGrads = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const OgsRawModelGrads* g = grads ? grads : &kNoGrads;
+    if (g->features_rest && !raw->features_rest) { set_error("raw backward: a features_rest gradient without features_rest"); return OGS_ERR_INVALID_ARG; }
+    // the copy the kernels get (see raw_fwd_args).  dL_dsh stands for "the dense SH gradient is wanted" in the host-side choices
+    // (backward_is_features_only); launch_preprocess_backward puts the two halves into the kernel's slots
+    OgsRasterBwdArgs b = *a;
+    b.shs = raw->features_dc;
+    b.opacities = raw->opacity;
+    b.scales = raw->scaling;
+    b.rotations = raw->rotation;
+    b.cov3D_precomp = raw->features_rest;
+    b.dL_dsh = g->features_dc ? g->features_dc : g->features_rest;
+    b.dL_dopacity = g->opacity;
+    b.dL_dscales = g->scaling;
+    b.dL_drotations = g->rotation;
+    return backward_impl(&b, stream_, g);
 }
 
 int ogs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float*, uint8_t* present,

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "../../include/ogs_raster.h"
+#include "../../include/ogs_model.h"
 
 namespace ogs {
 
@@ -355,12 +356,16 @@ struct BinTmp {         // transient, render phase
 };
 
 // kernels launched by capi.hip ------------------------------------------------------------------
-int launch_preprocess(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s);
+// raw (here and in the two single-workgroup launchers below): the raw-model form of the kernel (include/ogs_model.h); the
+// pointer slots of `a` then hold the raw arrays (capi.hip::raw_fwd_args)
+int launch_preprocess(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s, bool raw = false);
 // block-sum scheme: gt.block_sum (one sum of tiles_touched per preprocess workgroup) -> exclusive prefix in place, total ->
 // gt.num_rendered[0]; one workgroup
 int launch_block_offsets(const OgsRasterFwdArgs& a, const GeomTmp& gt, hipStream_t s);
-int launch_tiny_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, uint32_t* order, hipStream_t s);
-int launch_small_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s);
+int launch_tiny_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, uint32_t* order, hipStream_t s, bool raw = false);
+int launch_small_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s, bool raw = false);
+int launch_model_activate(int P, int M, const OgsRawModel& raw, float* scales, float* rotations, float* opacities, float* shs,
+                          hipStream_t s);
 int launch_tiny_blend(const OgsRasterFwdArgs& a, const GeomState& gs, const uint32_t* order, hipStream_t s);
 // re-blend of a kept pass with new feature channels: ONE launch of the stand-alone forward blend, which takes the replaced
 // channels from the caller's per-Gaussian features while it gathers the kept records (blend_forward_rows_kernel<C, RF>)
@@ -407,7 +412,10 @@ int launch_blend_forward(const OgsRasterFwdArgs& a, const GeomState& gs, const I
 // order-insensitive to ~1e-16 and is rounded to fp32 ONCE, in preprocess_backward_kernel.  (Round 4: the fp32 record of
 // OGS_GRAD_ACCUM=f32 is gone -- the moment slots are sums about the image origin now and NEED the fp64 headroom.)
 int launch_blend_backward(const OgsRasterBwdArgs& a, const ImageState& is, void* grad_rec, hipStream_t s);
-int launch_preprocess_backward(const OgsRasterBwdArgs& a, const GeomState& gs, const void* grad_rec, hipStream_t s);
+// raw_grads != NULL: the raw-model form (include/ogs_model.h) -- `a` holds the raw arrays in its pointer slots and the dense SH
+// gradient goes to raw_grads->features_dc / features_rest (capi.hip::ogs_raster_backward_raw)
+int launch_preprocess_backward(const OgsRasterBwdArgs& a, const GeomState& gs, const void* grad_rec, hipStream_t s,
+                               const OgsRawModelGrads* raw_grads = nullptr);
 // Only dL/dcolors_precomp is requested (every other output pointer NULL): the stage >= 1 training graph
 // (train.py:431-436) -> features-only kernels.
 inline bool backward_is_features_only(const OgsRasterBwdArgs& a) {

@@ -6,6 +6,7 @@
 // requested gradient exactly once -- culled Gaussians get zeros, so no output needs a prior memset.
 // HBM-bound: <= 300 B read, <= 300 B written per Gaussian (SH path dominates with 192 B of dL/dsh).
 #include "ogs_common.h"
+#include "ogs_model_act.h"
 
 #include <type_traits>
 
@@ -21,7 +22,12 @@ __device__ constexpr float kC3[7] = {-0.5900435899266435f, 2.890611442640554f, -
                                      0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f,
                                      -0.5900435899266435f};
 
-template <int C>
+// RAW (include/ogs_model.h::ogs_raster_backward_raw): the pointer slots carry the raw model -- shs = features_dc, cov3D_precomp =
+// features_rest, scales / rotations = log-scales / unnormalised quaternions; dL_dsh = d features_dc, dL_dcov3D = d features_rest
+// (either may be NULL on its own: `dense_sh` is "one of them"), dL_dscales / dL_drotations / dL_dopacity are with respect to the
+// raw parameters.  The activations are recomputed (ogs_model_act.h; the opacity is the record's) and their chain rule applied
+// where the gradients are stored.
+template <int C, bool RAW>
 __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
     int P, int W, int H, int sh_degree, int sh_coeffs, float tanfovx, float tanfovy, float focal_x, float focal_y,
     float scale_modifier, const float* __restrict__ means3D, const float* __restrict__ shs,
@@ -44,7 +50,8 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
     const bool valid = idx_raw < P;                 // no early return: the workgroup meets again for the dL/dsh rows
     const int idx = valid ? idx_raw : P - 1;
     const bool vis = valid && radii[idx] > 0;
-    const bool dense_sh = dL_dsh != nullptr && shs != nullptr;
+    const bool want_dsh = dL_dsh != nullptr || (RAW && dL_dcov3D != nullptr);     // the dense SH gradient, or (RAW) a half of it
+    const bool dense_sh = want_dsh && shs != nullptr;
     if (dense_sh) {
 #pragma unroll
         for (int k = 0; k < 16; ++k) s_basis[tid][k] = 0.f;
@@ -103,6 +110,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
         dconB = -0.5f * Sxy;
         dconC = -0.5f * Syy;
         dopac = co.w > 0.f ? S0 / co.w : 0.f;
+        if constexpr (RAW) dopac = act_opacity_bwd(dopac, co.w);      // co.w = sigmoid(logit), the bits the forward computed
     }
 
     if (dL_dmeans2D && valid) {
@@ -123,6 +131,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
     float dscale[3] = {0.f, 0.f, 0.f};
     float drot[4] = {0.f, 0.f, 0.f, 0.f};
 
+    // (RAW: dL_dcov3D is the features_rest gradient -- still "the geometry block is needed")
     const bool need_geom = dL_dmeans3D || dL_dcov3D || dL_dscales || dL_drotations || dL_dsh || dL_dsh_rgb;
     float drgb_out[3] = {0.f, 0.f, 0.f};
     if (vis && touched && need_geom) {
@@ -134,14 +143,25 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
         // ---- forward intermediates --------------------------------------------------------------
         float cov[6];
         float Rm[9] = {0}, sx = 0.f, sy = 0.f, sz = 0.f, qr = 0.f, qx = 0.f, qy = 0.f, qz = 0.f;
-        if (cov3D_precomp) {
+        float act_s[3] = {0.f, 0.f, 0.f}, q_norm = 0.f;       // RAW: exp(log-scale) before the modifier, |q| before normalising
+        if (!RAW && cov3D_precomp) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) cov[i] = cov3D_precomp[6 * idx + i];
         } else {
-            sx = scale_modifier * scales[3 * idx]; sy = scale_modifier * scales[3 * idx + 1];
-            sz = scale_modifier * scales[3 * idx + 2];
-            const float4 q = reinterpret_cast<const float4*>(rotations)[idx];
-            qr = q.x; qx = q.y; qy = q.z; qz = q.w;
+            if constexpr (RAW) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) act_s[k] = opaque(act_scale(scales[3 * idx + k]));
+                sx = scale_modifier * act_s[0]; sy = scale_modifier * act_s[1]; sz = scale_modifier * act_s[2];
+                const float4 q_raw = reinterpret_cast<const float4*>(rotations)[idx];
+                q_norm = quat_norm(q_raw);
+                const float4 q = act_rotation(q_raw, q_norm);
+                qr = opaque(q.x); qx = opaque(q.y); qy = opaque(q.z); qz = opaque(q.w);
+            } else {
+                sx = scale_modifier * scales[3 * idx]; sy = scale_modifier * scales[3 * idx + 1];
+                sz = scale_modifier * scales[3 * idx + 2];
+                const float4 q = reinterpret_cast<const float4*>(rotations)[idx];
+                qr = q.x; qx = q.y; qy = q.z; qz = q.w;
+            }
             Rm[0] = 1.f - 2.f * (qy * qy + qz * qz); Rm[1] = 2.f * (qx * qy - qr * qz); Rm[2] = 2.f * (qx * qz + qr * qy);
             Rm[3] = 2.f * (qx * qy + qr * qz); Rm[4] = 1.f - 2.f * (qx * qx + qz * qz); Rm[5] = 2.f * (qy * qz - qr * qx);
             Rm[6] = 2.f * (qx * qz - qr * qy); Rm[7] = 2.f * (qy * qz + qr * qx); Rm[8] = 1.f - 2.f * (qx * qx + qy * qy);
@@ -229,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
         for (int i = 0; i < 3; ++i) dmean[i] += V[4 * i + 2] * d_depth;
 
         // ---- colour -> SH, view direction -> mean ---------------------------------------------------------
-        if (shs != nullptr && (dL_dsh != nullptr || dL_dsh_rgb != nullptr || dL_dmeans3D != nullptr)) {
+        if (shs != nullptr && (want_dsh || dL_dsh_rgb != nullptr || dL_dmeans3D != nullptr)) {
             // Two instantiations (dense dL/dsh written or not): a run-time `if (dsh)` around every store keeps
             // the compiler from merging the 48 loads / stores per Gaussian into dwordx4 accesses (2x slower).
             auto sh_block = [&](auto write_tag) {
@@ -237,7 +257,10 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
                 const uint32_t cl = clamped_in[idx];
                 const float dRGB[3] = {(cl & 1u) ? 0.f : gr[0], (cl & 2u) ? 0.f : gr[1], (cl & 4u) ? 0.f : gr[2]};
                 drgb_out[0] = dRGB[0]; drgb_out[1] = dRGB[1]; drgb_out[2] = dRGB[2];
-                const float* sh = shs + (size_t)idx * sh_coeffs * 3;
+                const auto sh = [&] {
+                    if constexpr (RAW) return raw_sh_row(shs, cov3D_precomp, idx, sh_coeffs);
+                    else return shs + (size_t)idx * sh_coeffs * 3;
+                }();
                 const float ox = x - campos[0], oy = y - campos[1], oz = z - campos[2];
                 const float il = rsqrtf(ox * ox + oy * oy + oz * oz);
                 const float dxn = ox * il, dyn = oy * il, dzn = oz * il;
@@ -285,12 +308,12 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
                 dmean[1] += (ddir[1] - dyn * nd) * il;
                 dmean[2] += (ddir[2] - dzn * nd) * il;
             };
-            if (dL_dsh != nullptr) sh_block(std::true_type{});
+            if (want_dsh) sh_block(std::true_type{});
             else sh_block(std::false_type{});
         }
 
         // ---- cov3D -> scale, rotation ------------------------------------------------------------------------
-        if (cov3D_precomp == nullptr && (dL_dscales || dL_drotations)) {
+        if ((RAW || cov3D_precomp == nullptr) && (dL_dscales || dL_drotations)) {
             // G = dL/dSigma as a full symmetric matrix (off-diagonals halved), dL/dM = 2 G M, M_ik = R_ik s_k
             const float G[9] = {dcov[0], 0.5f * dcov[1], 0.5f * dcov[2], 0.5f * dcov[1], dcov[3], 0.5f * dcov[4],
                                 0.5f * dcov[2], 0.5f * dcov[4], dcov[5]};
@@ -316,6 +339,13 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
                              2.f * qy * dR[8]);
             drot[3] = 2.f * (-2.f * qz * dR[0] - qr * dR[1] + qx * dR[2] + qr * dR[3] - 2.f * qz * dR[4] + qy * dR[5] +
                              qx * dR[6] + qy * dR[7]);
+            if constexpr (RAW) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dscale[k] = act_scale_bwd(opaque(dscale[k]), act_s[k]);
+                const float4 dq = act_rotation_bwd(make_float4(opaque(drot[0]), opaque(drot[1]), opaque(drot[2]), opaque(drot[3])),
+                                                   make_float4(qr, qx, qy, qz), q_norm);
+                drot[0] = dq.x; drot[1] = dq.y; drot[2] = dq.z; drot[3] = dq.w;
+            }
         }
     }
 
@@ -327,18 +357,43 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
         const int L = sh_coeffs * 3;
         const size_t row0 = (size_t)blockIdx.x * kBlock;
         const int rows = min(kBlock, P - (int)row0);
-        float* __restrict__ out = dL_dsh + row0 * L;
-        auto value = [&](int e) {
-            const int g = e / L, i = e - g * L, k = i / 3, ch = i - 3 * k;
-            return k < 16 ? s_basis[g][k] * s_drgb[g][ch] : 0.f;
-        };
-        if ((L & 3) == 0) {
-            const int n4 = rows * L / 4;
-            for (int e4 = tid; e4 < n4; e4 += kBlock)
-                reinterpret_cast<float4*>(out)[e4] = make_float4(value(4 * e4), value(4 * e4 + 1), value(4 * e4 + 2), value(4 * e4 + 3));
+        if constexpr (RAW) {
+            // the same products, as two contiguous ranges per workgroup: rows x 3 floats of features_dc (coefficient 0) and
+            // rows x 3 (M - 1) floats of features_rest (coefficients 1..M-1); the latter in float4 stores up to a scalar tail
+            // (256 x 3 (M - 1) floats per full workgroup: every workgroup's range starts 16-byte aligned)
+            if (dL_dsh != nullptr) {
+                float* __restrict__ out_dc = dL_dsh + row0 * 3;
+                for (int e = tid; e < rows * 3; e += kBlock) {
+                    const int g = e / 3, ch = e - 3 * g;
+                    out_dc[e] = s_basis[g][0] * s_drgb[g][ch];
+                }
+            }
+            const int Lr = L - 3;
+            if (dL_dcov3D != nullptr && Lr > 0) {
+                float* __restrict__ out_rest = dL_dcov3D + row0 * Lr;
+                auto rest_value = [&](int e) {
+                    const int g = e / Lr, i = e - g * Lr, k = 1 + i / 3, ch = i - 3 * (k - 1);
+                    return k < 16 ? s_basis[g][k] * s_drgb[g][ch] : 0.f;
+                };
+                const int n = rows * Lr, n4 = n / 4;
+                for (int e4 = tid; e4 < n4; e4 += kBlock)
+                    reinterpret_cast<float4*>(out_rest)[e4] = make_float4(rest_value(4 * e4), rest_value(4 * e4 + 1), rest_value(4 * e4 + 2), rest_value(4 * e4 + 3));
+                for (int e = 4 * n4 + tid; e < n; e += kBlock) out_rest[e] = rest_value(e);
+            }
         } else {
-            const int n = rows * L;
-            for (int e = tid; e < n; e += kBlock) out[e] = value(e);
+            float* __restrict__ out = dL_dsh + row0 * L;
+            auto value = [&](int e) {
+                const int g = e / L, i = e - g * L, k = i / 3, ch = i - 3 * k;
+                return k < 16 ? s_basis[g][k] * s_drgb[g][ch] : 0.f;
+            };
+            if ((L & 3) == 0) {
+                const int n4 = rows * L / 4;
+                for (int e4 = tid; e4 < n4; e4 += kBlock)
+                    reinterpret_cast<float4*>(out)[e4] = make_float4(value(4 * e4), value(4 * e4 + 1), value(4 * e4 + 2), value(4 * e4 + 3));
+            } else {
+                const int n = rows * L;
+                for (int e = tid; e < n; e += kBlock) out[e] = value(e);
+            }
         }
     }
 
@@ -349,7 +404,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
     if (dL_dmeans3D) {
         dL_dmeans3D[3 * idx] = dmean[0]; dL_dmeans3D[3 * idx + 1] = dmean[1]; dL_dmeans3D[3 * idx + 2] = dmean[2];
     }
-    if (dL_dcov3D) {
+    if (!RAW && dL_dcov3D) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) dL_dcov3D[6 * idx + i] = dcov[i];
     }
@@ -361,13 +416,14 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(
     }
 }
 
-template <int C>
+template <int C, bool RAW>
 int launch_c(const OgsRasterBwdArgs& a, const GeomState& gs, const void* grad_rec, hipStream_t s) {
     const float focal_x = (float)a.W / (2.0f * a.tanfovx);
     const float focal_y = (float)a.H / (2.0f * a.tanfovy);
     const int grid = (a.P + kBlock - 1) / kBlock;
     static constexpr const char* const kNames[4] = {"preprocess_backward_kernel<3>", "preprocess_backward_kernel<6>", "preprocess_backward_kernel<9>", "preprocess_backward_kernel<12>"};
-    OGS_LAUNCH_NAMED(chan_name<C>(kNames), (preprocess_backward_kernel<C>), dim3(grid), dim3(kBlock), 0, s, a.P, a.W, a.H, a.sh_degree,
+    static constexpr const char* const kRawNames[4] = {"preprocess_backward_kernel<3, raw>", "preprocess_backward_kernel<6, raw>", "preprocess_backward_kernel<9, raw>", "preprocess_backward_kernel<12, raw>"};
+    OGS_LAUNCH_NAMED(chan_name<C>(RAW ? kRawNames : kNames), (preprocess_backward_kernel<C, RAW>), dim3(grid), dim3(kBlock), 0, s, a.P, a.W, a.H, a.sh_degree,
                        a.sh_coeffs, a.tanfovx, a.tanfovy, focal_x, focal_y, a.scale_modifier, a.means3D, a.shs, a.scales,
                        a.rotations, a.cov3D_precomp, a.viewmatrix, a.projmatrix, a.campos, a.radii,
                        (const uint32_t*)gs.clamped, (const float4*)gs.rec, (const double*)grad_rec, a.dL_dmeans2D, a.dL_dcolors, a.dL_dopacity, a.dL_dmeans3D,
@@ -449,10 +505,19 @@ int launch_sh_grad_from_views(int P, int V, int sh_degree, int sh_coeffs, const 
     return OGS_OK;
 }
 
-int launch_preprocess_backward(const OgsRasterBwdArgs& a, const GeomState& gs, const void* grad_rec, hipStream_t s) {
+int launch_preprocess_backward(const OgsRasterBwdArgs& a, const GeomState& gs, const void* grad_rec, hipStream_t s,
+                               const OgsRawModelGrads* raw_grads) {
     if (a.P <= 0) return OGS_OK;
+    if (raw_grads != nullptr) {
+        // the kernel's slots for the two halves of the dense SH gradient (preprocess_backward_kernel, RAW)
+        OgsRasterBwdArgs b = a;
+        b.dL_dsh = raw_grads->features_dc;
+        b.dL_dcov3D = raw_grads->features_rest;
+        return dispatch_channels<9>(b.C, "backward: unsupported channel count C=%d",
+                                    [&](auto c) { return launch_c<c(), true>(b, gs, grad_rec, s); });
+    }
     return dispatch_channels<9>(a.C, "backward: unsupported channel count C=%d",
-                                [&](auto c) { return launch_c<c()>(a, gs, grad_rec, s); });
+                                [&](auto c) { return launch_c<c(), false>(a, gs, grad_rec, s); });
 }
 
 }  // namespace ogs

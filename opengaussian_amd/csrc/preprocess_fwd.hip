@@ -9,6 +9,7 @@
 // coefficients read as 12 x float4 per Gaussian; one 16-byte-aligned record per Gaussian written
 // with float4 stores.  The kernel is HBM-bound (236 B in / ~70 B out per Gaussian with SH).
 #include "ogs_common.h"
+#include "ogs_model_act.h"
 
 namespace ogs {
 
@@ -28,11 +29,18 @@ struct Cam {
     float campos[3];
 };
 
+// RAW: `scales` holds log-scales and `rots` unnormalised quaternions (ogs_model_act.h activates them)
+template <bool RAW>
 __device__ __forceinline__ void cov3d_from_scale_rot(const float* __restrict__ scales,
                                                      const float* __restrict__ rots, int idx, float mod,
                                                      float cov[6]) {
-    const float sx = mod * scales[3 * idx + 0], sy = mod * scales[3 * idx + 1], sz = mod * scales[3 * idx + 2];
-    const float4 q = reinterpret_cast<const float4*>(rots)[idx];
+    float s0 = scales[3 * idx + 0], s1 = scales[3 * idx + 1], s2 = scales[3 * idx + 2];
+    float4 q = reinterpret_cast<const float4*>(rots)[idx];
+    if constexpr (RAW) {
+        s0 = act_scale(s0); s1 = act_scale(s1); s2 = act_scale(s2);
+        q = act_rotation(q, quat_norm(q));
+    }
+    const float sx = mod * s0, sy = mod * s1, sz = mod * s2;
     const float r = q.x, x = q.y, y = q.z, z = q.w;
     const float R00 = 1.f - 2.f * (y * y + z * z), R01 = 2.f * (x * y - r * z), R02 = 2.f * (x * z + r * y);
     const float R10 = 2.f * (x * y + r * z), R11 = 1.f - 2.f * (x * x + z * z), R12 = 2.f * (y * z - r * x);
@@ -48,11 +56,12 @@ __device__ __forceinline__ void cov3d_from_scale_rot(const float* __restrict__ s
     cov[5] = M20 * M20 + M21 * M21 + M22 * M22;
 }
 
-// SH -> RGB (+0.5, clamp at 0).  shs: [P, M, 3] coefficient-major, channel-minor.
-__device__ __forceinline__ void sh_to_rgb(int idx, int deg, int M, const float* __restrict__ shs, float px,
+// SH -> RGB (+0.5, clamp at 0).  sh: the Gaussian's row of [P, M, 3] (coefficient-major, channel-minor), anything indexable by
+// 3 k + c: a pointer into shs, or the raw model's two arrays (RawShRow).
+template <class ShRow>
+__device__ __forceinline__ void sh_to_rgb(int deg, const ShRow sh, float px,
                                           float py, float pz, const float* campos, float rgb[3],
                                           uint32_t& clamped) {
-    const float* sh = shs + (size_t)idx * M * 3;
     float dx = px - campos[0], dy = py - campos[1], dz = pz - campos[2];
     const float ln = sqrtf(dx * dx + dy * dy + dz * dz);
     const float x = dx / ln, y = dy / ln, z = dz / ln;
@@ -92,7 +101,10 @@ __device__ __forceinline__ void sh_to_rgb(int idx, int deg, int M, const float* 
 
 // One Gaussian of A.1 (shared by the streaming kernel and the single-workgroup kernel of the tiny pass).
 // Returns the depth-sort key: positive float bits are order preserving; culled Gaussians sort last.
-template <int C>
+// RAW (the raw-model entries, include/ogs_model.h): the pointer slots carry the model's raw parameters -- shs = features_dc,
+// cov3D_precomp = features_rest (a raw pass has no precomputed covariance), opacities / scales / rotations = the logits, log-scales
+// and unnormalised quaternions -- and are read through ogs_model_act.h.  Nothing else differs.
+template <int C, bool RAW>
 __device__ __forceinline__ uint32_t preprocess_one(
     int idx, int W, int H, int sh_degree, int sh_coeffs, float tanfovx, float tanfovy, float focal_x, float focal_y,
     float scale_modifier, const float* __restrict__ means3D, const float* __restrict__ colors_precomp,
@@ -109,7 +121,7 @@ __device__ __forceinline__ uint32_t preprocess_one(
     for (int i = 0; i < 16; ++i) { V[i] = viewmatrix[i]; M[i] = projmatrix[i]; }
 
     const float x = means3D[3 * idx + 0], y = means3D[3 * idx + 1], z = means3D[3 * idx + 2];
-    const float opacity = opacities[idx];
+    const float opacity = RAW ? act_opacity(opacities[idx]) : opacities[idx];
 
     // blended features travel in the record even for culled Gaussians (kept simple: one writer)
     float feat[(C + 3) / 4 * 4];
@@ -137,11 +149,11 @@ __device__ __forceinline__ uint32_t preprocess_one(
         const float projx = hx * p_w, projy = hy * p_w;
         // 3. 3D covariance
         float cov[6];
-        if (cov3D_precomp != nullptr) {
+        if (!RAW && cov3D_precomp != nullptr) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) cov[i] = cov3D_precomp[6 * idx + i];
         } else {
-            cov3d_from_scale_rot(scales, rotations, idx, scale_modifier, cov);
+            cov3d_from_scale_rot<RAW>(scales, rotations, idx, scale_modifier, cov);
         }
         // 4. EWA splat
         const float limx = 1.3f * tanfovx, limy = 1.3f * tanfovy;
@@ -220,7 +232,8 @@ __device__ __forceinline__ uint32_t preprocess_one(
     if (shs != nullptr && ok) {
         float rgb[3];
         float cp[3] = {campos[0], campos[1], campos[2]};
-        sh_to_rgb(idx, sh_degree, sh_coeffs, shs, x, y, z, cp, rgb, clamped);
+        if constexpr (RAW) sh_to_rgb(sh_degree, raw_sh_row(shs, cov3D_precomp, idx, sh_coeffs), x, y, z, cp, rgb, clamped);
+        else sh_to_rgb(sh_degree, shs + (size_t)idx * sh_coeffs * 3, x, y, z, cp, rgb, clamped);
         feat[0] = rgb[0]; feat[1] = rgb[1]; feat[2] = rgb[2];
     }
 
@@ -239,7 +252,7 @@ __device__ __forceinline__ uint32_t preprocess_one(
     return ok ? __float_as_uint(depth) : 0xFFFFFFFFu;
 }
 
-template <int C>
+template <int C, bool RAW>
 __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     int P, int W, int H, int sh_degree, int sh_coeffs, float tanfovx, float tanfovy, float focal_x, float focal_y,
     float scale_modifier, const float* __restrict__ means3D, const float* __restrict__ colors_precomp,
@@ -258,7 +271,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     const int idx = blockIdx.x * kBlock + tid;
     uint32_t touched = 0;
     if (idx < P) {
-        depth_keys[idx] = preprocess_one<C>(idx, W, H, sh_degree, sh_coeffs, tanfovx, tanfovy, focal_x, focal_y, scale_modifier,
+        depth_keys[idx] = preprocess_one<C, RAW>(idx, W, H, sh_degree, sh_coeffs, tanfovx, tanfovy, focal_x, focal_y, scale_modifier,
                                             means3D, colors_precomp, shs, opacities, scales, rotations, cov3D_precomp, viewmatrix,
                                             projmatrix, campos, s_rec + tid * NV, clamped_out, radii, tiles_touched, group_ids,
                                             num_groups, &touched);
@@ -290,7 +303,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
 // and the small subset renders of stages 2.2 / 3): ONE workgroup preprocesses every Gaussian and depth-sorts them in
 // LDS (rank sort on (depth bits, index): the reference's tile-list order restricted to any tile), so the whole
 // geometry phase -- preprocess, 4 radix passes, scan, read-back in the streaming path: ~15 launches -- is one launch.
-template <int C>
+template <int C, bool RAW>
 __global__ __launch_bounds__(kTinyMaxP) void tiny_geometry_kernel(
     int P, int W, int H, int sh_degree, int sh_coeffs, float tanfovx, float tanfovy, float focal_x, float focal_y,
     float scale_modifier, const float* __restrict__ means3D, const float* __restrict__ colors_precomp,
@@ -302,7 +315,7 @@ __global__ __launch_bounds__(kTinyMaxP) void tiny_geometry_kernel(
     const int idx = threadIdx.x;
     uint32_t key = 0xFFFFFFFFu;
     if (idx < P)
-        key = preprocess_one<C>(idx, W, H, sh_degree, sh_coeffs, tanfovx, tanfovy, focal_x, focal_y, scale_modifier, means3D,
+        key = preprocess_one<C, RAW>(idx, W, H, sh_degree, sh_coeffs, tanfovx, tanfovy, focal_x, focal_y, scale_modifier, means3D,
                                 colors_precomp, shs, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
                                 campos, rec + (size_t)idx * rec_vec4(C), clamped_out, radii, nullptr, nullptr, 0);
     s_key[idx] = key;
@@ -323,7 +336,7 @@ __global__ __launch_bounds__(kTinyMaxP) void tiny_geometry_kernel(
 // kernel), the depth order comes from a rank sort on (depth bits, index) in LDS (= what the stable radix passes
 // produce) and the exclusive scan of tiles_touched in that order from a block scan.  Leaves order[0], offsets and
 // num_rendered exactly as the streaming kernels do; the render phase follows unchanged.
-template <int C>
+template <int C, bool RAW>
 __global__ __launch_bounds__(kSmallMaxP) void small_geometry_kernel(
     int P, int W, int H, int sh_degree, int sh_coeffs, float tanfovx, float tanfovy, float focal_x, float focal_y,
     float scale_modifier, const float* __restrict__ means3D, const float* __restrict__ colors_precomp,
@@ -341,7 +354,7 @@ __global__ __launch_bounds__(kSmallMaxP) void small_geometry_kernel(
     uint32_t key = 0xFFFFFFFFu;
     s_touched[idx] = 0u;
     if (idx < P)
-        key = preprocess_one<C>(idx, W, H, sh_degree, sh_coeffs, tanfovx, tanfovy, focal_x, focal_y, scale_modifier, means3D,
+        key = preprocess_one<C, RAW>(idx, W, H, sh_degree, sh_coeffs, tanfovx, tanfovy, focal_x, focal_y, scale_modifier, means3D,
                                 colors_precomp, shs, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
                                 campos, rec + (size_t)idx * rec_vec4(C), clamped_out, radii, s_touched, group_ids, num_groups);
     s_key[idx] = key;
@@ -598,13 +611,48 @@ __global__ __launch_bounds__(kBlock) void mark_visible_kernel(int P, const float
     present[idx] = pvz > 0.2f ? 1 : 0;
 }
 
-template <int C>
+// The four getters of the reference model as one kernel (include/ogs_model.h::ogs_model_activate), through the device functions
+// the raw passes use.  One thread per Gaussian for scale / rotation / opacity; the [P, M, 3] interleave of features_dc and
+// features_rest is written by the whole workgroup as one contiguous range.  HBM: 12 M + 32 B in, the same out per Gaussian.
+__global__ __launch_bounds__(kBlock) void model_activate_kernel(int P, int M, const float* __restrict__ features_dc,
+                                                                const float* __restrict__ features_rest,
+                                                                const float* __restrict__ scaling,
+                                                                const float* __restrict__ rotation,
+                                                                const float* __restrict__ opacity, float* __restrict__ scales,
+                                                                float* __restrict__ rotations, float* __restrict__ opacities,
+                                                                float* __restrict__ shs) {
+    const int tid = threadIdx.x;
+    const int idx = blockIdx.x * kBlock + tid;
+    if (idx < P) {
+        if (scales != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) scales[3 * idx + k] = act_scale(scaling[3 * idx + k]);
+        }
+        if (rotations != nullptr) {
+            const float4 q = reinterpret_cast<const float4*>(rotation)[idx];
+            reinterpret_cast<float4*>(rotations)[idx] = act_rotation(q, quat_norm(q));
+        }
+        if (opacities != nullptr) opacities[idx] = act_opacity(opacity[idx]);
+    }
+    if (shs != nullptr) {
+        const int L = 3 * M, Lr = L - 3;
+        const size_t row0 = (size_t)blockIdx.x * kBlock;
+        const int n = min(kBlock, P - (int)row0) * L;
+        for (int e = tid; e < n; e += kBlock) {
+            const int g = e / L, i = e - g * L;
+            shs[row0 * L + e] = i < 3 ? features_dc[(row0 + g) * 3 + i] : features_rest[(row0 + g) * Lr + (i - 3)];
+        }
+    }
+}
+
+template <int C, bool RAW>
 int launch_preprocess_c(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s) {
     const float focal_x = (float)a.W / (2.0f * a.tanfovx);
     const float focal_y = (float)a.H / (2.0f * a.tanfovy);
     const int grid = (a.P + kBlock - 1) / kBlock;
     static constexpr const char* const kNames[4] = {"preprocess_kernel<3>", "preprocess_kernel<6>", "preprocess_kernel<9>", "preprocess_kernel<12>"};
-    OGS_LAUNCH_NAMED(chan_name<C>(kNames), preprocess_kernel<C>, dim3(grid), dim3(kBlock), 0, s, a.P, a.W, a.H, a.sh_degree, a.sh_coeffs,
+    static constexpr const char* const kRawNames[4] = {"preprocess_kernel<3, raw>", "preprocess_kernel<6, raw>", "preprocess_kernel<9, raw>", "preprocess_kernel<12, raw>"};
+    OGS_LAUNCH_NAMED(chan_name<C>(RAW ? kRawNames : kNames), (preprocess_kernel<C, RAW>), dim3(grid), dim3(kBlock), 0, s, a.P, a.W, a.H, a.sh_degree, a.sh_coeffs,
                        a.tanfovx, a.tanfovy, focal_x, focal_y, a.scale_modifier, a.means3D, a.colors_precomp, a.shs,
                        a.opacities, a.scales, a.rotations, a.cov3D_precomp, a.viewmatrix, a.projmatrix, a.campos,
                        gs.rec, gs.clamped, a.radii, gt.tiles_touched, gt.keys[0],
@@ -614,22 +662,22 @@ int launch_preprocess_c(const OgsRasterFwdArgs& a, const GeomState& gs, const Ge
     return OGS_OK;
 }
 
-template <int C>
+template <int C, bool RAW>
 int launch_tiny_geometry_c(const OgsRasterFwdArgs& a, const GeomState& gs, uint32_t* order, hipStream_t s) {
     const float focal_x = (float)a.W / (2.0f * a.tanfovx);
     const float focal_y = (float)a.H / (2.0f * a.tanfovy);
-    OGS_LAUNCH(tiny_geometry_kernel<C>, dim3(1), dim3(kTinyMaxP), 0, s, a.P, a.W, a.H, a.sh_degree, a.sh_coeffs, a.tanfovx,
+    OGS_LAUNCH_NAMED(RAW ? "tiny_geometry_kernel<C, raw>" : "tiny_geometry_kernel<C>", (tiny_geometry_kernel<C, RAW>), dim3(1), dim3(kTinyMaxP), 0, s, a.P, a.W, a.H, a.sh_degree, a.sh_coeffs, a.tanfovx,
                a.tanfovy, focal_x, focal_y, a.scale_modifier, a.means3D, a.colors_precomp, a.shs, a.opacities, a.scales,
                a.rotations, a.cov3D_precomp, a.viewmatrix, a.projmatrix, a.campos, gs.rec, gs.clamped, a.radii, order);
     OGS_LAUNCH_CHECK(a.debug, s);
     return OGS_OK;
 }
 
-template <int C>
+template <int C, bool RAW>
 int launch_small_geometry_c(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s) {
     const float focal_x = (float)a.W / (2.0f * a.tanfovx);
     const float focal_y = (float)a.H / (2.0f * a.tanfovy);
-    OGS_LAUNCH(small_geometry_kernel<C>, dim3(1), dim3(kSmallMaxP), 0, s, a.P, a.W, a.H, a.sh_degree, a.sh_coeffs, a.tanfovx,
+    OGS_LAUNCH_NAMED(RAW ? "small_geometry_kernel<C, raw>" : "small_geometry_kernel<C>", (small_geometry_kernel<C, RAW>), dim3(1), dim3(kSmallMaxP), 0, s, a.P, a.W, a.H, a.sh_degree, a.sh_coeffs, a.tanfovx,
                a.tanfovy, focal_x, focal_y, a.scale_modifier, a.means3D, a.colors_precomp, a.shs, a.opacities, a.scales,
                a.rotations, a.cov3D_precomp, a.viewmatrix, a.projmatrix, a.campos, gs.rec, gs.clamped, a.radii, gt.order[0],
                gt.offsets, gt.num_rendered, a.num_groups > 1 ? a.group_ids : (const int32_t*)nullptr, a.num_groups);
@@ -641,16 +689,31 @@ constexpr const char* kBadC = "unsupported channel count C=%d (3, 6, 9 or 12)";
 
 }  // namespace
 
-int launch_small_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s) {
-    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return launch_small_geometry_c<c()>(a, gs, gt, s); });
+// raw: `a` carries the raw model in its pointer slots (preprocess_one; capi.hip::raw_fwd_args fills them)
+int launch_small_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s, bool raw) {
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) {
+        return raw ? launch_small_geometry_c<c(), true>(a, gs, gt, s) : launch_small_geometry_c<c(), false>(a, gs, gt, s);
+    });
 }
 
-int launch_tiny_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, uint32_t* order, hipStream_t s) {
-    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return launch_tiny_geometry_c<c()>(a, gs, order, s); });
+int launch_tiny_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, uint32_t* order, hipStream_t s, bool raw) {
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) {
+        return raw ? launch_tiny_geometry_c<c(), true>(a, gs, order, s) : launch_tiny_geometry_c<c(), false>(a, gs, order, s);
+    });
 }
 
-int launch_preprocess(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s) {
-    return dispatch_channels<12>(a.C, kBadC, [&](auto c) { return launch_preprocess_c<c()>(a, gs, gt, s); });
+int launch_preprocess(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s, bool raw) {
+    return dispatch_channels<12>(a.C, kBadC, [&](auto c) {
+        return raw ? launch_preprocess_c<c(), true>(a, gs, gt, s) : launch_preprocess_c<c(), false>(a, gs, gt, s);
+    });
+}
+
+int launch_model_activate(int P, int M, const OgsRawModel& raw, float* scales, float* rotations, float* opacities, float* shs,
+                          hipStream_t s) {
+    OGS_LAUNCH(model_activate_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, P, M, raw.features_dc,
+               raw.features_rest, raw.scaling, raw.rotation, raw.opacity, scales, rotations, opacities, shs);
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
 }
 
 int launch_block_offsets(const OgsRasterFwdArgs& a, const GeomTmp& gt, hipStream_t s) {

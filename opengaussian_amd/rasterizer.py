@@ -23,7 +23,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._lib import OgsRasterBwdArgs, OgsRasterFwdArgs, check, ptr
+from ._lib import OgsRasterBwdArgs, OgsRasterFwdArgs, OgsRawModel, OgsRawModelGrads, check, ptr
 
 SUPPORTED_CHANNELS = (3, 6, 9, 12)
 BACKWARD_CHANNELS = (3, 6, 9)          # the gradient record holds C + 7 <= 16 slots
@@ -42,7 +42,9 @@ _HINT_WINDOW = 32
 # how the render phase of every forward was sized: "blocking" (first pass at a size, grouped / debug passes: the
 # reference's 4-byte read-back), "deferred" (sync-free, capacity from the hint), "overflow" (deferred result
 # discarded, render phase redone with exact buffers)
-PASS_STATS = {"blocking": 0, "deferred": 0, "overflow": 0, "tiny": 0, "tiny_rerendered_for_backward": 0, "reblend": 0}
+# "raw_model": passes taken from the model's raw parameters (rasterize_model), counted besides the sizing mode they used
+PASS_STATS = {"blocking": 0, "deferred": 0, "overflow": 0, "tiny": 0, "tiny_rerendered_for_backward": 0, "reblend": 0,
+              "raw_model": 0}
 
 
 def _hint_capacity(key):
@@ -218,9 +220,11 @@ def _render_sizes(count, W, H, Cn):
             int(lib.ogs_raster_quad_list_bytes(count)))
 
 
-def _streaming_render(a: OgsRasterFwdArgs, dev, lib, debug: bool):
+def _streaming_render(a: OgsRasterFwdArgs, dev, lib, debug: bool, raw: Optional[OgsRawModel] = None):
     """The two-phase forward (geometry -> num_rendered -> render) on the buffers `a` already points to for inputs
-    and outputs; allocates and returns (geom, image, point_list, sorted_rec, quad_list, num_rendered)."""
+    and outputs; allocates and returns (geom, image, point_list, sorted_rec, quad_list, num_rendered).
+    raw: the geometry phase reads the model's raw parameters (include/ogs_model.h; `a` then has no shs / opacities / scales /
+    rotations); the render phase is the same call either way."""
     P, W, H, Cn, G = int(a.P), int(a.W), int(a.H), int(a.C), max(int(a.num_groups), 1)
     u8 = lambda n: torch.empty(int(n), dtype=torch.uint8, device=dev)
     gb, gtb, ib = _geom_sizes(P, W, H, Cn, G)
@@ -235,6 +239,14 @@ def _streaming_render(a: OgsRasterFwdArgs, dev, lib, debug: bool):
         a.point_list, a.binning_tmp, a.sorted_rec, a.quad_list = ptr(pl), ptr(bt), ptr(sr), ptr(ql)
         return pl, bt, sr, ql
 
+    def geometry(n_ref):
+        if raw is None:
+            check(lib.ogs_raster_forward_geometry(C.byref(a), stream, n_ref), "ogs_raster_forward_geometry")
+            return
+        check(lib.ogs_raster_forward_geometry_raw(C.byref(a), C.byref(raw), stream, n_ref), "ogs_raster_forward_geometry_raw")
+        # what the render phase's argument check wants to see (include/ogs_model.h): it reads none of them
+        a.shs, a.opacities, a.scales, a.rotations = raw.features_dc, raw.opacity, raw.scaling, raw.rotation
+
     key = (P, W, H, G)
     # grouped passes: num_rendered follows the group ids of the call (cluster chunk, leaf range), which change
     # from call to call -> sized by the blocking read-back, like subset passes (their P is new every time)
@@ -243,7 +255,7 @@ def _streaming_render(a: OgsRasterFwdArgs, dev, lib, debug: bool):
         PASS_STATS["blocking"] += 1
         # first pass at this size: blocking 4-byte read-back of num_rendered (what the reference does every time)
         n = C.c_int64(0)
-        check(lib.ogs_raster_forward_geometry(C.byref(a), stream, C.byref(n)), "ogs_raster_forward_geometry")
+        geometry(C.byref(n))
         D = int(n.value)
         point_list, bin_tmp, sorted_rec, quad_list = alloc_render(D)
         check(lib.ogs_raster_forward_render(C.byref(a), D, stream), "ogs_raster_forward_render")
@@ -251,7 +263,7 @@ def _streaming_render(a: OgsRasterFwdArgs, dev, lib, debug: bool):
         # steady state: no GPU idle gap.  The render phase is enqueued for a capacity derived from the recent
         # passes at this size; the true count arrives through an async pinned copy and is only WAITED for after
         # everything is queued.  Overflow (scene changed a lot) -> redo the render phase with exact buffers.
-        check(lib.ogs_raster_forward_geometry(C.byref(a), stream, None), "ogs_raster_forward_geometry")
+        geometry(None)
         pinned, ev = _readback_slot(dev)
         check(lib.ogs_raster_read_num_rendered_async(C.byref(a), stream, pinned.data_ptr()),
               "ogs_raster_read_num_rendered_async")
@@ -770,6 +782,204 @@ def rasterize_fused(means3D, means2D, opacities, shs, extra_feats, raster_settin
     if sink:
         KEPT_PASSES.admit(slot, key, holds, sink[0], generation)
     return out
+
+
+def _raw_model_struct(dc, rest, opac, scl, rot) -> OgsRawModel:
+    raw = OgsRawModel()
+    raw.features_dc, raw.features_rest, raw.scaling, raw.rotation, raw.opacity = ptr(dc), ptr(rest), ptr(scl), ptr(rot), ptr(opac)
+    return raw
+
+
+class _RasterizeModel(torch.autograd.Function):
+    """The fused SH pass of _RasterizeGaussians taken from the model's raw parameters (include/ogs_model.h): the activations
+    of the reference's getters (scene/gaussian_model.py:122-159) run inside the per-Gaussian kernels, forward and backward."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, extra_feats,
+                raster_settings: GaussianRasterizationSettings, geom_channels: int = 0):
+        rs = raster_settings
+        ctx.geom_channels = int(geom_channels)
+        ctx.set_materialize_grads(False)
+        for t, name in ((means3D, "means3D"), (features_dc, "features_dc"), (opacity_raw, "opacity_raw"),
+                        (scaling_raw, "scaling_raw"), (rotation_raw, "rotation_raw")):
+            _require_gpu(t, name)
+        dev = means3D.device
+        lib = _lib.lib()
+        P = int(means3D.shape[0])
+        H, W = int(rs.image_height), int(rs.image_width)
+        if means3D.dim() != 2 or means3D.shape[1] != 3:
+            raise RuntimeError("means3D must have dimensions (num_points, 3)")
+        if tuple(features_dc.shape) != (P, 1, 3) or tuple(scaling_raw.shape) != (P, 3) or tuple(rotation_raw.shape) != (P, 4) \
+                or opacity_raw.numel() != P:
+            raise RuntimeError("raw model: features_dc [P,1,3], scaling [P,3], rotation [P,4], opacity [P,1] expected")
+        M = 1
+        if features_rest is not None and features_rest.numel() > 0:
+            if features_rest.dim() != 3 or features_rest.shape[0] != P or features_rest.shape[2] != 3:
+                raise RuntimeError("raw model: features_rest must be [P, M-1, 3]")
+            _require_gpu(features_rest, "features_rest")
+            M += int(features_rest.shape[1])
+        m3, dc, rest = _f32c(means3D), _f32c(features_dc), _f32c(features_rest)
+        opac, scl, rot = _f32c(opacity_raw), _f32c(scaling_raw), _f32c(rotation_raw)
+        cols = _f32c(extra_feats)
+        if cols is not None:
+            _require_gpu(cols, "extra_feats")
+        Cn = 3 + (0 if cols is None else int(cols.shape[1]))
+        if Cn not in SUPPORTED_CHANNELS:
+            raise RuntimeError(f"the blended channel count must be 3, 6, 9 or 12, got {Cn}")
+        if Cn not in BACKWARD_CHANNELS and any(ctx.needs_input_grad[:8]):
+            raise RuntimeError(f"a {Cn}-channel pass is forward-only (backward supports {BACKWARD_CHANNELS} channels): "
+                               "detach the inputs or split the pass")
+        bg = _f32c(rs.bg.to(dev))
+        if bg is None or bg.numel() != Cn:
+            if bg is not None and bg.numel() == 3 and Cn > 3:
+                bg = _tiled_bg(bg, Cn)
+            else:
+                raise RuntimeError(f"bg must have {Cn} entries")
+        view, proj, campos = _f32c(rs.viewmatrix.to(dev)), _f32c(rs.projmatrix.to(dev)), _f32c(rs.campos.to(dev))
+        alloc = torch.zeros if P == 0 else torch.empty
+        color = alloc(Cn, H, W, dtype=torch.float32, device=dev)
+        depth = alloc(1, H, W, dtype=torch.float32, device=dev)
+        alpha = alloc(1, H, W, dtype=torch.float32, device=dev)
+        radii = alloc(P, dtype=torch.int32, device=dev)
+        ctx.raster_settings = rs
+        ctx.P, ctx.Cn, ctx.M, ctx.num_rendered, ctx.tiny = P, Cn, M, 0, False
+        ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
+        ctx.full_binning, ctx.num_groups = bool(FULL_BINNING), 1
+        if P == 0:
+            ctx.save_for_backward()
+            ctx.mark_non_differentiable(radii)
+            return color, radii, depth, alpha
+        PASS_STATS["raw_model"] += 1
+        a = _fwd_args(rs, P, Cn, m3, None, cols, None, None, None, None, bg, view, proj, campos, color, depth, alpha, radii, None, 1)
+        a.sh_coeffs = M
+        raw = _raw_model_struct(dc, rest, opac, scl, rot)
+        if not rs.debug and P <= _tiny_limit():
+            stream = _stream()
+            geom, geom_tmp = _tiny_scratch(dev, stream, lib)
+            a.geom_buffer, a.geom_tmp = geom.data_ptr(), geom_tmp.data_ptr()
+            check(lib.ogs_raster_forward_tiny_raw(C.byref(a), C.byref(raw), stream), "ogs_raster_forward_tiny_raw")
+            PASS_STATS["tiny"] += 1
+            ctx.tiny, ctx.num_rendered = True, -1
+            ctx.save_for_backward(m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha)
+            ctx.mark_non_differentiable(radii)
+            return color, radii, depth, alpha
+        need = ctx.needs_input_grad
+        if HOST_BWD_CLEAR and not rs.debug and any(need[:8]):
+            bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
+            a.bwd_clear, a.bwd_clear_bytes = ptr(bwd_tmp), _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot)
+        geom, image, point_list, sorted_rec, quad_list, D = _streaming_render(a, dev, lib, rs.debug, raw)
+        ctx.num_rendered = D
+        if a.bwd_clear:
+            ctx.bwd_tmp, ctx.bwd_clear_bytes = bwd_tmp, int(a.bwd_clear_bytes)
+        ctx.save_for_backward(m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha, geom, image, point_list,
+                              sorted_rec, quad_list)
+        ctx.mark_non_differentiable(radii)
+        return color, radii, depth, alpha
+
+    @staticmethod
+    def _record_bytes(need, P, Cn, dc, cols, scl, rot) -> int:
+        # in _RasterizeGaussians' order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D
+        return _grad_record_bytes((need[0], need[1], need[2] or need[3], need[7], need[4], need[5], need[6], False), P, Cn, dc,
+                                  cols, scl, rot, None)
+
+    @staticmethod
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
+        rs = ctx.raster_settings
+        P, Cn, M = ctx.P, ctx.Cn, ctx.M
+        if P == 0:
+            return (None,) * 10
+        lib = _lib.lib()
+        H, W = int(rs.image_height), int(rs.image_width)
+        scratch = None
+        if ctx.tiny:
+            # as _RasterizeGaussians: a tiny pass keeps nothing, the backward re-renders through the streaming path
+            (m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha) = ctx.saved_tensors
+            dev = m3.device
+            e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
+            scratch = (e(Cn, H, W), e(1, H, W), e(1, H, W), torch.empty(P, dtype=torch.int32, device=dev))
+            a = _fwd_args(rs, P, Cn, m3, None, cols, None, None, None, None, bg, view, proj, campos, *scratch, None, 1)
+            a.sh_coeffs = M
+            geom, image, point_list, sorted_rec, quad_list, D = _streaming_render(
+                a, dev, lib, False, _raw_model_struct(dc, rest, opac, scl, rot))
+            ctx.num_rendered = D
+            PASS_STATS["tiny_rerendered_for_backward"] += 1
+        else:
+            (m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha, geom, image, point_list, sorted_rec,
+             quad_list) = ctx.saved_tensors
+        dev = m3.device
+        need = ctx.needs_input_grad   # means3D, means2D, features_dc, features_rest, opacity, scaling, rotation, extra_feats
+        z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        g_m3 = z(P, 3) if need[0] else None
+        g_m2 = z(P, 3) if need[1] else None
+        g_dc = z(P, 1, 3) if need[2] else None
+        g_rest = z(P, M - 1, 3) if (need[3] and rest is not None) else None
+        g_op = z(P, 1) if need[4] else None
+        g_scl = z(P, 3) if need[5] else None
+        g_rot = z(P, 4) if need[6] else None
+        g_col = z(*cols.shape) if (need[7] and cols is not None) else None
+        gc = _f32c(grad_color)
+        if gc is None:
+            gc = torch.zeros(Cn, H, W, dtype=torch.float32, device=dev)
+        gd, ga = _f32c(grad_depth), _f32c(grad_alpha)
+        bwd_tmp, is_clear = ctx.bwd_tmp, False
+        if bwd_tmp is not None:
+            is_clear = ctx.bwd_clear_bytes >= _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot)
+            ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
+        else:
+            bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
+        b = OgsRasterBwdArgs()
+        b.bwd_tmp_is_clear = int(is_clear)
+        b.P, b.W, b.H, b.C = P, W, H, Cn
+        b.sh_degree, b.sh_coeffs = int(rs.sh_degree), M
+        b.tanfovx, b.tanfovy, b.scale_modifier = float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier)
+        b.debug = int(bool(rs.debug))
+        b.num_rendered, b.geom_channels, b.num_groups = int(ctx.num_rendered), int(ctx.geom_channels), 1
+        b.sorted_rec, b.quad_list = ptr(sorted_rec), ptr(quad_list)
+        b.bg, b.means3D, b.colors_precomp = ptr(bg), ptr(m3), ptr(cols)
+        b.viewmatrix, b.projmatrix, b.campos = ptr(view), ptr(proj), ptr(campos)
+        b.radii, b.out_alpha = ptr(radii), ptr(alpha)
+        b.dL_dcolor, b.dL_ddepth, b.dL_dalpha = ptr(gc), ptr(gd), ptr(ga)
+        b.geom_buffer, b.image_buffer, b.point_list, b.bwd_tmp = ptr(geom), ptr(image), ptr(point_list), ptr(bwd_tmp)
+        b.dL_dmeans2D, b.dL_dcolors, b.dL_dmeans3D = ptr(g_m2), ptr(g_col), ptr(g_m3)
+        raw = _raw_model_struct(dc, rest, opac, scl, rot)
+        grads = OgsRawModelGrads()
+        grads.features_dc, grads.features_rest, grads.scaling, grads.rotation, grads.opacity = \
+            ptr(g_dc), ptr(g_rest), ptr(g_scl), ptr(g_rot), ptr(g_op)
+        check(lib.ogs_raster_backward_raw(C.byref(b), C.byref(raw), C.byref(grads), _stream()), "ogs_raster_backward_raw")
+        scratch = None
+        return g_m3, g_m2, g_dc, g_rest, g_op, g_scl, g_rot, g_col, None, None
+
+
+def rasterize_model(means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings,
+                    extra_feats=None, detach_extra_from_geometry=True):
+    """rasterize_fused (or, without `extra_feats`, the plain SH pass) from the reference model's RAW parameters -- `_features_dc`
+    [P,1,3], `_features_rest` [P,M-1,3] (None or empty: M = 1), `_opacity` [P,1] logits, `_scaling` [P,3] log-scales,
+    `_rotation` [P,4] unnormalised quaternions -- instead of the getters' outputs (scene/gaussian_model.py:122-159: exp,
+    F.normalize, sigmoid, cat).  The activations run inside the per-Gaussian kernels and the gradients come back with respect
+    to the raw parameters: no activated copies, no torch graph between the parameters and the rasterizer.  Same four outputs,
+    bit for bit those of the existing pass fed with activate_model's outputs.  CPU tensors raise: there is no fallback."""
+    return _RasterizeModel.apply(means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
+                                 extra_feats, raster_settings, 3 if (detach_extra_from_geometry and extra_feats is not None) else 0)
+
+
+def activate_model(features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw):
+    """(scales [P,3], rotations [P,4], opacities [P,1], shs [P,M,3]): the reference's four getters as ONE kernel
+    (ogs_model_activate), through the device functions the raw pass uses.  No autograd (the outputs are detached)."""
+    for t, name in ((features_dc, "features_dc"), (opacity_raw, "opacity_raw"), (scaling_raw, "scaling_raw"),
+                    (rotation_raw, "rotation_raw")):
+        _require_gpu(t, name)
+    dev = features_dc.device
+    P = int(features_dc.shape[0])
+    M = 1 + (int(features_rest.shape[1]) if features_rest is not None and features_rest.numel() > 0 else 0)
+    dc, rest = _f32c(features_dc), _f32c(features_rest)
+    opac, scl, rot = _f32c(opacity_raw), _f32c(scaling_raw), _f32c(rotation_raw)
+    e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
+    scales, rotations, opacities, shs = e(P, 3), e(P, 4), e(P, 1), e(P, M, 3)
+    if P:
+        raw = _raw_model_struct(dc, rest, opac, scl, rot)
+        check(_lib.lib().ogs_model_activate(P, M, C.byref(raw), ptr(scales), ptr(rotations), ptr(opacities), ptr(shs), _stream()),
+              "ogs_model_activate")
+    return scales, rotations, opacities, shs
 
 
 def rasterize_groups(means3D, means2D, opacities, group_ids, num_groups, raster_settings, shs=None,

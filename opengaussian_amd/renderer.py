@@ -23,7 +23,8 @@ import torch
 
 from . import knn as _knn
 from . import rasterizer as _rasterizer
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_fused, rasterize_groups
+from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, rasterize_fused, rasterize_groups,
+                         rasterize_model)
 
 # a grouped pass materialises [G, C+2, H, W] fp32: bound G per pass (the loop over passes keeps the order)
 GROUPS_PER_PASS = 64
@@ -139,6 +140,31 @@ def _frozen_geometry_key(viewpoint_camera, pc, pipe, xyz, scaling_modifier):
     return slot, key, (tuple(params), cam), key[0]          # generation = the parameters' identities: one state of the model
 
 
+def _raw_model_params(pc, pipe, xyz, override_color):
+    """The model's raw parameters (name -> tensor) when this call MAY take the raw-model pass (rasterizer.rasterize_model: the
+    getters' activations run inside the rasterizer's kernels), else None.
+
+    Opt-in: ``pipe.raw_model_pass`` -- the reference's PipelineParams has no such attribute, so a drop-in caller stays on the
+    getters.  And only where the pass is exact: SH colours (no override_color), none of the pipe's python / debug branches,
+    a model that looks like the reference's GaussianModel (the six `_MODEL_PARAMS` as CUDA fp32 tensors, `get_xyz` the `_xyz`
+    parameter itself) -- the getters of such a model are exp / F.normalize / sigmoid / cat (scene/gaussian_model.py:122-159),
+    which is what the kernels apply.  render() adds what it only knows later: no rescale draw, and a call the frozen-geometry
+    caches would not have served."""
+    if not getattr(pipe, "raw_model_pass", False) or override_color is not None:
+        return None
+    if getattr(pipe, "debug", False) or getattr(pipe, "compute_cov3D_python", False) or getattr(pipe, "convert_SHs_python", False):
+        return None
+    params = {}
+    for name in _MODEL_PARAMS:
+        t = getattr(pc, name, None)
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype is not torch.float32:
+            return None
+        params[name] = t
+    if not isinstance(xyz, torch.Tensor) or params["_xyz"].data_ptr() != xyz.data_ptr() or params["_xyz"].shape != xyz.shape:
+        return None
+    return params
+
+
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, iteration,
            scaling_modifier=1.0, override_color=None, visible_mask=None, mask_num=0,
            cluster_idx=None, leaf_cluster_idx=None, rescale=True, origin_feat=False,
@@ -171,28 +197,41 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, iteration,
 
     means3D = xyz
     means2D = screenspace_points
-    opacity = pc.get_opacity
+    # raw-model pass (opt-in, pipe.raw_model_pass): the getters are not evaluated until the call turns out to need them
+    raw = _raw_model_params(pc, pipe, xyz, override_color)
+    opacity = scales = rotations = cov3D_precomp = None
+    shs = colors_precomp = None
 
-    scales = rotations = cov3D_precomp = None
-    if pipe.compute_cov3D_python:
-        cov3D_precomp = pc.get_covariance(scaling_modifier)
+    def read_getters():
+        # opacity, then scale and rotation: the getters the rasterizer's activated inputs come from
+        sc_ = ro_ = None
+        op_ = pc.get_opacity
+        if not pipe.compute_cov3D_python:
+            sc_, ro_ = pc.get_scaling, pc.get_rotation
+        return op_, sc_, ro_
+
+    if raw is None:
+        opacity, scales, rotations = read_getters()
+        if pipe.compute_cov3D_python:
+            cov3D_precomp = pc.get_covariance(scaling_modifier)
+        grad_probe = (means3D, opacity, scales, rotations, cov3D_precomp)
     else:
-        scales = pc.get_scaling
-        rotations = pc.get_rotation
+        # a getter's output requires grad exactly when its parameter does and grad mode is on
+        grad_on = torch.is_grad_enabled()
+        grad_probe = (means3D,) + tuple(raw[n] if grad_on else raw[n].detach() for n in ("_opacity", "_scaling", "_rotation"))
 
     if viewspace_grad is None:
-        viewspace_grad = any(t is not None and t.requires_grad for t in (means3D, opacity, scales, rotations, cov3D_precomp))
+        viewspace_grad = any(t is not None and t.requires_grad for t in grad_probe)
     if not viewspace_grad:
         means2D = screenspace_points.detach()
 
-    shs = colors_precomp = None
     if override_color is None:
         if pipe.convert_SHs_python:
             shs_view = pc.get_features.transpose(1, 2).view(-1, 3, (pc.max_sh_degree + 1) ** 2)
             dir_pp = pc.get_xyz - viewpoint_camera.camera_center.repeat(pc.get_features.shape[0], 1)
             dir_pp_normalized = dir_pp / dir_pp.norm(dim=1, keepdim=True)
             colors_precomp = torch.clamp_min(eval_sh(pc.active_sh_degree, shs_view, dir_pp_normalized) + 0.5, 0.0)
-        else:
+        elif raw is None:       # (raw: SH colours from the raw features, or from get_features once the pass is decided)
             shs = pc.get_features
     else:
         colors_precomp = override_color
@@ -212,11 +251,29 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, iteration,
     # a 12-channel pass has no backward (gradient record: C + 7 <= 16 slots): only fuse / widen that far without grad
     differentiable = torch.is_grad_enabled() and any(
         t is not None and t.requires_grad for t in (means3D, means2D, opacity, scales, rotations, cov3D_precomp, shs,
-                                                    colors_precomp, ins_feat))
+                                                    colors_precomp, ins_feat) + (tuple(raw.values()) if raw is not None else ()))
     max_pass_channels = 9 if differentiable else 12
     can_fuse = (render_color and render_feat_map and not rescaled and ins_feat.shape[-1] in (3, 6, 9)
                 and ins_feat.shape[-1] + 3 <= max_pass_channels)
-    if can_fuse:
+    # the raw pass serves the un-rescaled RGB pass -- alone (the stage-0 call) or fused with the feature map -- of a call the
+    # frozen-geometry caches would not have served
+    take_raw = (raw is not None and render_color and not rescaled and (can_fuse or not render_feat_map)
+                and (viewspace_grad or _frozen_geometry_key(viewpoint_camera, pc, pipe, xyz, scaling_modifier) is None))
+    if raw is not None and not take_raw:
+        opacity, scales, rotations = read_getters()
+        shs = pc.get_features
+    if take_raw:
+        out, radii, rendered_depth, rendered_alpha = rasterize_model(
+            means3D, means2D, raw["_features_dc"], raw["_features_rest"], raw["_opacity"], raw["_scaling"], raw["_rotation"],
+            raster_settings, extra_feats=ins_feat if can_fuse else None, detach_extra_from_geometry=False)
+        rendered_image = out[:3]
+        if can_fuse:
+            rendered_ins_feat, silhouette = out[3:], rendered_alpha
+        if (render_cluster and cluster_idx is not None) or (leaf_cluster_idx is not None and leaf_cluster_idx.numel() > 0):
+            # the subset renders below read the activated arrays
+            opacity, scales, rotations = read_getters()
+            shs = pc.get_features
+    elif can_fuse:
         # RGB + features + silhouette on identical geometry: one bin / sort / blend for everything
         if shs is not None:
             # stage >= 1 (everything but ins_feat frozen, no rescale draw): the camera's first pass is kept, later ones re-blend it
