@@ -55,6 +55,21 @@
  * Limits: Q <= 64 (OGS_ERR_UNSUPPORTED above), n * Q <= INT32_MAX (offsets are 32 bits; OGS_ERR_INVALID_ARG above).
  * tmp: ogs_query_split_tmp_bytes(n, Q) bytes, carried from count to scatter.
  *
+ * ---- label map (ogs_raster_label_map) ----------------------------------------------------------------------------------
+ * Pixel -> label: for every pixel of a finished pass, which of the per-Gaussian labels it shows.  `pass` names a finished
+ * UNGROUPED streaming pass exactly as ogs_raster_forward_reblend takes it (P, W, H, C, debug, image_buffer, sorted_rec,
+ * quad_list; everything else is ignored), in the layout the pass left or in the one ogs_raster_compact_kept leaves; the kept
+ * buffers are only read.  For a pixel, the entries of its tile in depth order have the weights w_i = alpha_i * T_i the forward
+ * blend adds to out_alpha -- same arithmetic, same candidate window, 0.99 cap, 1/255 skip and stop at T * (1 - alpha) < 1e-4 --
+ * and W_l is the sum, in depth order, of the w_i whose Gaussian (slot 7 of the record) has labels[id] == l.  Then
+ *     out_label  = the l with the largest W_l > 0, the LOWEST l on an exact tie, -1 where no labelled entry contributed
+ *     out_weight = that W_l (0 where -1)          out_second = the largest W_l of any other label (0 if there is none)
+ *     out_alpha  = the sum of ALL w_i, labelled or not: the pass's own alpha image, bit for bit
+ * A label outside [0, num_labels) marks an unlabelled Gaussian: it occludes and never wins.  One launch whatever num_labels is,
+ * nothing larger than the four [H, W] outputs is written, no atomic touches an output: two calls give the same bytes.  A tile
+ * with more than ogs_label_map_tile_capacity() distinct labels walks its streams once per that many labels; the result is
+ * exact for any tile and any num_labels.  Forward only.  Asynchronous.
+ *
  * No entry point reads anything back from the device.  All pointers are device pointers, `stream` is a hipStream_t as
  * void*.  Returns 0 or a negative OGS_ERR_* code.
  */
@@ -63,6 +78,8 @@
 
 #include <stddef.h>
 #include <stdint.h>
+
+#include "ogs_raster.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -97,6 +114,17 @@ int ogs_query_split_scan(int64_t n, int32_t Q, const uint8_t* group_keep, void* 
 int ogs_query_split_scatter(int64_t n, const int64_t* leaf_ind, int32_t K, const uint64_t* leaf_groups,
                             const uint8_t* row_ok, int32_t Q, const uint8_t* group_keep, const void* tmp, int64_t* rows,
                             int64_t capacity, void* stream);
+
+typedef struct OgsLabelMapArgs {
+    const int32_t* labels;   /* [P]; a value outside [0, num_labels) = unlabelled: occludes, never wins */
+    int32_t num_labels;      /* L >= 0, no upper limit other than int32 */
+    int32_t* out_label;      /* [H,W]  winner, -1 where no labelled entry contributed */
+    float* out_weight;       /* [H,W]  the winner's weight W_l (0 where -1) */
+    float* out_second;       /* [H,W]  the runner-up label's weight (0 if there is none) */
+    float* out_alpha;        /* [H,W]  sum of ALL weights of the pixel, labelled or not */
+} OgsLabelMapArgs;
+int ogs_raster_label_map(const OgsRasterFwdArgs* pass, const OgsLabelMapArgs* lm, void* stream);
+size_t ogs_label_map_tile_capacity(void);   /* test hook: distinct labels of one tile handled per walk */
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,12 @@ class OgsGroupStatsArgs(C.Structure):
                 ("count", _vp), ("feat_sum", _vp), ("stats_tmp", _vp)]
 
 
+class OgsLabelMapArgs(C.Structure):
+    """include/ogs_query.h: labels in, the four [H, W] maps out."""
+    _fields_ = [("labels", _vp), ("num_labels", C.c_int32), ("out_label", _vp), ("out_weight", _vp), ("out_second", _vp),
+                ("out_alpha", _vp)]
+
+
 class OgsRawModel(C.Structure):
     """include/ogs_model.h: the reference model's raw parameters."""
     _fields_ = [("features_dc", _vp), ("features_rest", _vp), ("scaling", _vp), ("rotation", _vp), ("opacity", _vp)]
@@ -181,6 +187,8 @@ SIGNATURES = {
     "ogs_query_split_count": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
     "ogs_query_split_scan": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "ogs_query_split_scatter": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64, _vp]),
+    "ogs_raster_label_map": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsLabelMapArgs), _vp]),
+    "ogs_label_map_tile_capacity": (C.c_size_t, []),
 }
 
 _lib = None

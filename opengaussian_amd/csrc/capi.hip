@@ -185,7 +185,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 406; }
+int ogs_version(void) { return 407; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 

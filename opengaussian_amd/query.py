@@ -7,8 +7,12 @@
 ``multi_split``             rows of OVERLAPPING leaf selections, group by group, each group ascending
 ``render_queries``          the object image and silhouette of every query of a view from one grouped rasterizer pass and
                             one kNN launch, instead of one ``render(selected_leaf_id=...)`` call per query
+``render_label_map``        pixel -> label: per pixel the leaf / instance / class with the largest blend weight, one launch over
+                            the view's kept pass (``rasterizer.label_map``); ``labels_at_pixels`` reads clicks off it
+``click_features`` /        the reference's own click route (scripts/render_by_click.py:35-66,138-166), batched over clicks, in
+``select_leaves_by_click``  plain torch
 
-CPU tensors raise: there is no CPU path.
+CPU tensors raise: there is no CPU path (the three plain-torch click helpers run wherever their inputs live).
 """
 from __future__ import annotations
 
@@ -26,6 +30,7 @@ from ._lib import check, ptr
 SPLIT_GROUPS = 64          # groups of one split: a bit each in a leaf's 64-bit word
 
 QueryRender = namedtuple("QueryRender", "images silhouettes kept counts")
+LabelMap = namedtuple("LabelMap", "label weight second alpha")
 
 
 def _stream():
@@ -405,3 +410,156 @@ def render_queries(view, pc, pipe, bg, iteration, leaf_cluster_idx, selections, 
             for q, img, alpha in zip(chunk, imgs, alphas):
                 images[c0 + q], sils[c0 + q] = img, alpha
     return QueryRender(images, sils, kept_all, counts_all)
+
+
+# ---- pixel -> label ------------------------------------------------------------------------------------------------------------
+def render_label_map(view, pc, pipe, bg, iteration, point_labels, num_labels, pre_mask=None, scaling_modifier=1.0):
+    """``LabelMap(label [H,W] int32, weight, second, alpha [H,W] fp32)`` of one view: per pixel the label whose Gaussians carry the
+    largest summed blend weight (lowest label on an exact tie, -1 where no labelled Gaussian contributes), that weight, the
+    runner-up label's weight, and the alpha of the full-scene render.  ``point_labels`` [P] integers: leaf ids
+    (click -> leaf -> ``render_queries``), instance ids, or ``classify_points`` output (a 2D class map); values outside
+    [0, num_labels) are unlabelled.  ``pre_mask`` [P] bool sets the labels of masked-out points to -1: they still occlude, as in the
+    full-scene render.
+
+    The map is one launch over the UN-RESCALED pass of the view: the pass ``render()`` kept for this camera when the model is
+    frozen (``rasterizer.KEPT_PASSES``), else one pass run here and dropped afterwards (its colour is never read, so the means
+    stand in for it, as in ``render_queries``); nothing is admitted to the cache by this call.  Forward only: runs under
+    ``no_grad`` and raises when a model tensor requires grad while grad mode is on."""
+    xyz = pc.get_xyz
+    _need_gpu(xyz, "the model")
+    if not torch.is_tensor(point_labels):
+        raise ValueError("point_labels must be a tensor")
+    _need_gpu(point_labels, "point_labels")
+    P = xyz.shape[0]
+    if point_labels.shape != (P,):
+        raise ValueError(f"point_labels must be [{P}], got {tuple(point_labels.shape)}")
+    if pre_mask is not None and pre_mask.shape != (P,):
+        raise ValueError(f"pre_mask must be [{P}], got {tuple(pre_mask.shape)}")
+    if torch.is_grad_enabled():
+        probe = [xyz, pc.get_opacity] + ([] if pipe.compute_cov3D_python else [pc.get_scaling, pc.get_rotation])
+        if any(t.requires_grad for t in probe):
+            raise RuntimeError("render_label_map is forward only: call it under torch.no_grad() or detach the model")
+    with torch.no_grad():
+        dev = xyz.device
+        H, W = int(view.image_height), int(view.image_width)
+        labels = point_labels.to(dev)
+        if pre_mask is not None:
+            labels = torch.where(pre_mask.to(dev).to(torch.bool), labels, torch.full_like(labels, -1))
+        kept = None
+        frozen = _renderer._frozen_geometry_key(view, pc, pipe, xyz, scaling_modifier)
+        if frozen is not None:
+            # a look, not a lookup: the cache's slots and counters stay as they are
+            e = _rasterizer.KEPT_PASSES.slots.get(frozen[0])
+            if e is not None and e.key[0] == frozen[1] and e.full_binning == bool(_rasterizer.FULL_BINNING):
+                kept = e
+        if kept is None and P > 0:
+            settings = _rasterizer.GaussianRasterizationSettings(
+                image_height=H, image_width=W, tanfovx=math.tan(view.FoVx * 0.5), tanfovy=math.tan(view.FoVy * 0.5), bg=bg,
+                scale_modifier=float(scaling_modifier), viewmatrix=view.world_view_transform,
+                projmatrix=view.full_proj_transform, sh_degree=pc.active_sh_degree, campos=view.camera_center,
+                prefiltered=False, debug=pipe.debug)
+            means3D = xyz.detach()
+            scales = rotations = cov3D = None
+            if pipe.compute_cov3D_python:
+                cov3D = pc.get_covariance(scaling_modifier).detach()
+            else:
+                scales, rotations = pc.get_scaling.detach(), pc.get_rotation.detach()
+            sink: list = []
+            _rasterizer._RasterizeGaussians.apply(means3D, torch.zeros_like(means3D), None, means3D, pc.get_opacity.detach(),
+                                                  scales, rotations, cov3D, settings, 0, None, None, 1, sink, True)
+            kept = sink[0] if sink else None
+        if kept is None:
+            # nothing reaches a tile of this view: an empty map
+            z = lambda: torch.zeros(H, W, dtype=torch.float32, device=dev)
+            return LabelMap(torch.full((H, W), -1, dtype=torch.int32, device=dev), z(), z(), z())
+        return LabelMap(*_rasterizer.label_map(kept, labels, num_labels))
+
+
+def _window(pixels_xy, radius, W, H):
+    """(x [K, n], y [K, n], inside [K, n]) of the (2r+1)^2 window around every click, in the reference's order (x outer, y inner,
+    render_by_click.py:46-48); positions outside the image are flagged, their coordinates clamped into it"""
+    xy = torch.as_tensor(pixels_xy)
+    if xy.dim() != 2 or xy.shape[1] != 2 or xy.is_floating_point():
+        raise ValueError(f"pixels_xy must be [K, 2] integers (x, y), got {tuple(xy.shape)} {xy.dtype}")
+    r = int(radius)
+    if r < 0:
+        raise ValueError("radius must be >= 0")
+    xy = xy.to(torch.int64)
+    d = torch.arange(-r, r + 1, device=xy.device)
+    x = (xy[:, 0, None, None] + d[None, :, None]).expand(-1, -1, 2 * r + 1).reshape(xy.shape[0], -1)
+    y = (xy[:, 1, None, None] + d[None, None, :]).expand(-1, 2 * r + 1, -1).reshape(xy.shape[0], -1)
+    inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+    return x.clamp(0, W - 1), y.clamp(0, H - 1), inside
+
+
+def labels_at_pixels(label_map, pixels_xy, radius=0):
+    """[K] int64: per click (x, y) the label with the largest summed ``weight`` over the (2r+1)^2 window clamped to the image,
+    the lowest label on a tie, -1 when the window holds no label.  ``label_map``: a ``LabelMap`` (or any (label, weight, ...)
+    pair of [H, W] tensors).  Plain torch where the map lives, no read-back and no atomics (the same bits every run; K * n * n
+    compares for windows of n = (2r+1)^2 pixels); the result, one id per click, is what
+    ``render_queries(..., selections=[ids[k:k + 1] ...])`` takes."""
+    label, weight = label_map[0], label_map[1]
+    if label.dim() != 2 or weight.shape != label.shape:
+        raise ValueError(f"label and weight must be [H, W] alike, got {tuple(label.shape)} and {tuple(weight.shape)}")
+    H, W = label.shape
+    xy = torch.as_tensor(pixels_xy).to(label.device)
+    x, y, inside = _window(xy, radius, W, H)
+    lab = label[y, x].to(torch.int64)                                   # [K, n]
+    valid = inside & (lab >= 0)
+    w = torch.where(valid, weight[y, x].to(torch.float32), torch.zeros((), dtype=torch.float32, device=label.device))
+    # total[k, j] = summed weight of the label of window pixel j: every pixel of one label holds the same sum
+    same = (lab[:, :, None] == lab[:, None, :]) & valid[:, None, :]
+    total = (same.to(torch.float32) * w[:, None, :]).sum(-1)
+    total = torch.where(valid, total, torch.full_like(total, -1.0))
+    top = total.max(dim=1, keepdim=True).values
+    big = torch.iinfo(torch.int64).max
+    cand = torch.where(valid & (total == top), lab, torch.full_like(lab, big))
+    best = cand.min(dim=1).values
+    return torch.where(best == big, torch.full_like(best, -1), best)
+
+
+def click_features(ins_feat_map, pixels_xy, radius=5, quantize=True):
+    """[K, C] fp32 click values of the reference (render_by_click.py:35-53,61): the mean of the rendered feature map
+    ``ins_feat_map`` [C, H, W] (values in [0, 1]; C = 6: the two three-channel images of a checkpoint) over the (2r+1)^2 window
+    clamped to the image, then ``* 2 - 1``.  ``quantize``: the map first takes the 8-bit rounding ``save_image`` applies
+    (``mul(255).add(0.5).clamp(0, 255)`` to uint8) and the mean is divided by 255, as the reference reads it back from PNG
+    files.  Plain torch where the map lives."""
+    if ins_feat_map.dim() != 3:
+        raise ValueError(f"ins_feat_map must be [C, H, W], got {tuple(ins_feat_map.shape)}")
+    _, H, W = ins_feat_map.shape
+    xy = torch.as_tensor(pixels_xy).to(ins_feat_map.device)
+    x, y, inside = _window(xy, radius, W, H)
+    v = ins_feat_map.detach().to(torch.float32)
+    if quantize:
+        v = v.mul(255).add(0.5).clamp(0, 255).to(torch.uint8)
+    v = v[:, y, x].to(torch.float64)                                    # [C, K, n]
+    mean = (v * inside[None].to(torch.float64)).sum(-1) / inside.sum(-1)[None].to(torch.float64)
+    mean = mean.t().to(torch.float32)
+    return (mean / 255 if quantize else mean) * 2 - 1
+
+
+def select_leaves_by_click(root_feats, leaf_feats, root_centers, leaf_centers):
+    """[K] int64 leaf ids: option (2) of the reference's click selection (render_by_click.py:143-161) for K clicks at once.
+    ``root_feats`` / ``leaf_feats`` [K, D]: the click values read off the level-1 / level-2 feature maps (``click_features``);
+    ``root_centers`` [R, D + 3]: the root code book's ``ins_feat`` (its last three columns, the positions, are dropped);
+    ``leaf_centers`` [N + 1, D]: the leaf code book's ``ins_feat`` (its last row, the dummy, is dropped).  An unassigned leaf
+    (all-zero row sum) gets distance 999.  Per click: the nearest root, then the nearest leaf among that root's
+    ``[int(root * N / R), int((root + 1) * N / R))``.  Plain torch, no read-back."""
+    rc = root_centers[:, :-3].to(torch.float32)
+    lc = leaf_centers[:-1].to(torch.float32)
+    rf, lf = root_feats.to(torch.float32), leaf_feats.to(torch.float32)
+    if rf.dim() != 2 or lf.dim() != 2 or rf.shape[0] != lf.shape[0] or rf.shape[1] != rc.shape[1] or lf.shape[1] != lc.shape[1]:
+        raise ValueError(f"click values [K, {rc.shape[1]}] / [K, {lc.shape[1]}] expected, got {tuple(rf.shape)} and {tuple(lf.shape)}")
+    R, N = rc.shape[0], lc.shape[0]
+    if R < 1 or N < 1:
+        raise ValueError("need at least one root and one leaf")
+    d_root = torch.norm(rf[:, None, :] - rc[None, :, :], dim=2)
+    d_leaf = torch.norm(lf[:, None, :] - lc[None, :, :], dim=2)
+    d_leaf = torch.where((lc.sum(-1) == 0)[None, :], torch.full_like(d_leaf, 999.0), d_leaf)
+    root = torch.argmin(d_root, dim=1)
+    leaf_num = N / R                                                    # a Python float, as in the reference
+    start = torch.floor(root.to(torch.float64) * leaf_num).to(torch.int64)
+    end = torch.floor((root + 1).to(torch.float64) * leaf_num).to(torch.int64)
+    k = torch.arange(N, device=d_leaf.device)[None, :]
+    inside = (k >= start[:, None]) & (k < end[:, None])
+    return torch.argmin(torch.where(inside, d_leaf, torch.full_like(d_leaf, float("inf"))), dim=1)

@@ -288,7 +288,9 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings: GaussianRasterizationSettings, geom_channels: int = 0, sh_rgb_sink=None,
-                group_ids=None, num_groups: int = 1, keep_sink=None):
+                group_ids=None, num_groups: int = 1, keep_sink=None, force_streaming: bool = False):
+        # force_streaming (internal, label_map): a P <= TINY_MAX_P pass takes the streaming path, which leaves the state a
+        # label map walks; the default path selection is untouched
         rs = raster_settings
         ctx.geom_channels = int(geom_channels)
         ctx.sh_rgb_sink = sh_rgb_sink
@@ -361,7 +363,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         a = _fwd_args(rs, P, Cn, m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, color, depth, alpha, radii,
                       group_ids, G)
 
-        if G == 1 and not rs.debug and P <= _tiny_limit():
+        if G == 1 and not rs.debug and P <= _tiny_limit() and not force_streaming:
             # tiny pass: two launches, no read-back, nothing kept -- backward() re-renders through the streaming path
             stream = _stream()
             geom, geom_tmp = _tiny_scratch(dev, stream, lib)
@@ -399,7 +401,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         rs = ctx.raster_settings
         P, Cn = ctx.P, ctx.Cn
         if P == 0:
-            return (None,) * 14
+            return (None,) * 15
         lib = _lib.lib()
         H, W = int(rs.image_height), int(rs.image_width)
         scratch = None
@@ -476,7 +478,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             _DEBUG_KEEP_BWD_TMP.append(bwd_tmp)
         if sink is not None:
             sink.append(g_sh_rgb)
-        return g_m3, g_m2, g_sh, g_col, g_op, g_scl, g_rot, g_cov, None, None, None, None, None, None
+        return g_m3, g_m2, g_sh, g_col, g_op, g_scl, g_rot, g_cov, None, None, None, None, None, None, None
 
 
 # ---- kept passes: the frozen-geometry cache ------------------------------------------------------------------------------
@@ -734,6 +736,58 @@ class _ReblendKept(torch.autograd.Function):
         b.dL_dcolors = ptr(g_col)
         check(lib.ogs_raster_backward(C.byref(b), _stream()), "ogs_raster_backward")
         return g_col, None, None
+
+
+def _kept_state(kept):
+    """(P, W, H, Cn, image, sorted_rec, quad_list) of what a pass left in its keep_sink (a dict) or of a KeptPasses entry."""
+    if isinstance(kept, _KeptPass):
+        return kept.P, kept.W, kept.H, kept.Cn, kept.image, kept.sorted_rec, kept.quad_list
+    if isinstance(kept, dict) and all(k in kept for k in ("P", "W", "H", "Cn", "image", "sorted_rec", "quad_list")):
+        return (int(kept["P"]), int(kept["W"]), int(kept["H"]), int(kept["Cn"]), kept["image"], kept["sorted_rec"],
+                kept["quad_list"])
+    raise RuntimeError("label_map needs the state of an ungrouped streaming pass: the dict a pass leaves in keep_sink or a "
+                       "KeptPasses entry (grouped and tiny passes keep none)")
+
+
+def label_map(kept, labels, num_labels):
+    """Per-pixel dominant label of a finished pass (ogs_raster_label_map, include/ogs_query.h): ONE launch over the kept quadrant
+    streams, O(H * W) memory whatever `num_labels` is.
+
+    kept: what an ungrouped streaming pass left in ``keep_sink``, or a ``KeptPasses`` entry.  labels: [P] integer tensor on the
+    GPU; a value outside [0, num_labels) marks an unlabelled Gaussian, which occludes and never wins.
+    Returns ``(label [H,W] int32, weight [H,W], second [H,W], alpha [H,W])``: the label with the largest summed blend weight
+    (lowest label on an exact tie, -1 where no labelled Gaussian contributed), that weight, the runner-up label's weight, and
+    the pass's own alpha image bit for bit.  Forward only; two calls give the same bytes."""
+    P, W, H, Cn, image, sorted_rec, quad_list = _kept_state(kept)
+    if not torch.is_tensor(labels):
+        raise RuntimeError("labels must be a tensor")
+    if labels.is_floating_point() or labels.is_complex() or labels.dtype is torch.bool:
+        raise RuntimeError(f"labels must have an integer dtype, got {labels.dtype}")
+    if labels.numel() != P:
+        raise RuntimeError(f"the pass holds {P} Gaussians, labels has {labels.numel()} entries")
+    L = int(num_labels)
+    if L < 0 or L > 2 ** 31 - 1:
+        raise RuntimeError(f"num_labels must be in [0, 2^31), got {num_labels}")
+    _require_gpu(labels, "labels")
+    _require_gpu(image, "the kept pass")
+    dev = image.device
+    lab = labels.detach().reshape(-1).to(device=dev)
+    if lab.dtype is not torch.int32:
+        # a 64-bit value outside the int32 range is outside [0, L) too: it stays unlabelled instead of wrapping into range
+        lab = torch.where((lab >= 0) & (lab < L), lab, torch.full_like(lab, -1)).to(torch.int32)
+    lab = lab.contiguous()
+    out_label = torch.empty(H, W, dtype=torch.int32, device=dev)
+    weight = torch.empty(H, W, dtype=torch.float32, device=dev)
+    second = torch.empty(H, W, dtype=torch.float32, device=dev)
+    alpha = torch.empty(H, W, dtype=torch.float32, device=dev)
+    a = OgsRasterFwdArgs()
+    a.P, a.W, a.H, a.C = P, W, H, Cn
+    a.image_buffer, a.sorted_rec, a.quad_list = ptr(image), ptr(sorted_rec), ptr(quad_list)
+    lm = _lib.OgsLabelMapArgs()
+    lm.labels, lm.num_labels = ptr(lab), L
+    lm.out_label, lm.out_weight, lm.out_second, lm.out_alpha = ptr(out_label), ptr(weight), ptr(second), ptr(alpha)
+    check(_lib.lib().ogs_raster_label_map(C.byref(a), C.byref(lm), _stream()), "ogs_raster_label_map")
+    return out_label, weight, second, alpha
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
