@@ -70,6 +70,28 @@
  * with more than ogs_label_map_tile_capacity() distinct labels walks its streams once per that many labels; the result is
  * exact for any tile and any num_labels.  Forward only.  Asynchronous.
  *
+ * ---- label votes (ogs_raster_label_votes) --------------------------------------------------------------------------------
+ * Pixel labels -> Gaussians, the transpose of the label map: how much blend weight every Gaussian puts on every label of a
+ * label IMAGE of the view, through the occlusion of the whole pass.  `pass` is taken exactly as ogs_raster_label_map takes
+ * it (ungrouped streaming pass, either layout, only read), and w_i(p) = alpha_i * T_i are the same weights with the same
+ * arithmetic.  With
+ *     lab(p) = pixel_labels[p] if it lies in [0, num_labels), else num_labels        (column L: the "no label" bucket)
+ *     row(g) = g if rows == NULL, else rows[g]; a row outside [0, num_rows) is not counted (it still occludes)
+ * the call ADDS to the table (the caller clears it; V views sum into one table)
+ *     votes[row(g), l] += sum over the pixels p with lab(p) = l of w_{entry of g}(p)          int64 [R, L + 1], quantum 2^-32
+ * Rounding: for one entry of one 8 x 8 quadrant and one label the fp32 sum over that label's pixels is a PARTIAL; it is a
+ * function of the weights of those pixels and of their positions in the quadrant only (not of the label's value or of the
+ * other labels of the quadrant) and is rounded once, llrint(partial * 2^32); everything after that is integer addition.  So
+ * the table does not depend on the order of the atomics (two runs give the same bytes), is the same from both layouts,
+ * votes(rows = r) equals index_add of votes(rows = NULL) over r, an injective relabelling of the pixels permutes the columns,
+ * and two calls into one table give twice the table.
+ * Range: a partial is below 2^6 (64 pixels of weight < 1), i.e. below 2^38 units; a cell must stay below 2^31 of summed
+ * weight (2^63 units) over everything accumulated into it -- about 2000 full 1-megapixel images of weight 1 in ONE cell.
+ * Cell addresses are computed in 64 bits; every index (Gaussian id < P, 0 <= row < R, label <= L) is checked on the device
+ * before it is used, so no input makes the kernel write outside the table.  One launch whatever L is, any quadrant in one
+ * walk: a quadrant's up to ogs_label_votes_quadrant_capacity() distinct labels are folded ogs_label_votes_fold_columns() at a
+ * time over the same staged weights.  Forward only.  Asynchronous.
+ *
  * No entry point reads anything back from the device.  All pointers are device pointers, `stream` is a hipStream_t as
  * void*.  Returns 0 or a negative OGS_ERR_* code.
  */
@@ -125,6 +147,17 @@ typedef struct OgsLabelMapArgs {
 } OgsLabelMapArgs;
 int ogs_raster_label_map(const OgsRasterFwdArgs* pass, const OgsLabelMapArgs* lm, void* stream);
 size_t ogs_label_map_tile_capacity(void);   /* test hook: distinct labels of one tile handled per walk */
+
+typedef struct OgsLabelVotesArgs {
+    const int32_t* pixel_labels; /* [H,W]; a value outside [0, num_labels) counts in column num_labels */
+    int32_t num_labels;          /* L >= 0 */
+    const int32_t* rows;         /* [P] or NULL (row = Gaussian index); outside [0, num_rows): not counted */
+    int32_t num_rows;            /* R >= 1 */
+    int64_t* votes;              /* [R, L+1], quantum 2^-32, accumulated into */
+} OgsLabelVotesArgs;
+int ogs_raster_label_votes(const OgsRasterFwdArgs* pass, const OgsLabelVotesArgs* lv, void* stream);
+size_t ogs_label_votes_quadrant_capacity(void);  /* test hook: distinct labels of one quadrant folded per walk */
+size_t ogs_label_votes_fold_columns(void);       /* test hook: of those, the labels of one column block of the fold */
 
 #ifdef __cplusplus
 }

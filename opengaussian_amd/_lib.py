@@ -75,6 +75,11 @@ class OgsLabelMapArgs(C.Structure):
                 ("out_alpha", _vp)]
 
 
+class OgsLabelVotesArgs(C.Structure):
+    """include/ogs_query.h: a label image in, the [R, L + 1] fixed-point table accumulated into."""
+    _fields_ = [("pixel_labels", _vp), ("num_labels", C.c_int32), ("rows", _vp), ("num_rows", C.c_int32), ("votes", _vp)]
+
+
 class OgsRawModel(C.Structure):
     """include/ogs_model.h: the reference model's raw parameters."""
     _fields_ = [("features_dc", _vp), ("features_rest", _vp), ("scaling", _vp), ("rotation", _vp), ("opacity", _vp)]
@@ -189,6 +194,9 @@ SIGNATURES = {
     "ogs_query_split_scatter": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64, _vp]),
     "ogs_raster_label_map": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsLabelMapArgs), _vp]),
     "ogs_label_map_tile_capacity": (C.c_size_t, []),
+    "ogs_raster_label_votes": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsLabelVotesArgs), _vp]),
+    "ogs_label_votes_quadrant_capacity": (C.c_size_t, []),
+    "ogs_label_votes_fold_columns": (C.c_size_t, []),
 }
 
 _lib = None

@@ -9,10 +9,14 @@
                             one kNN launch, instead of one ``render(selected_leaf_id=...)`` call per query
 ``render_label_map``        pixel -> label: per pixel the leaf / instance / class with the largest blend weight, one launch over
                             the view's kept pass (``rasterizer.label_map``); ``labels_at_pixels`` reads clicks off it
+``lift_labels``             pixel labels -> Gaussians: the blend weight every Gaussian (or leaf) puts on every label of the views'
+                            label images, one launch per view (``rasterizer.label_votes``), an int64 fixed-point table;
+                            ``votes_as_float`` / ``labels_from_votes`` read it, ``select_leaves_by_masks`` turns mask prompts into
+                            the leaf selections ``render_queries`` takes (``leaves_from_votes`` is its rule)
 ``click_features`` /        the reference's own click route (scripts/render_by_click.py:35-66,138-166), batched over clicks, in
 ``select_leaves_by_click``  plain torch
 
-CPU tensors raise: there is no CPU path (the three plain-torch click helpers run wherever their inputs live).
+CPU tensors raise: there is no CPU path (the plain-torch click helpers and vote-table readers run wherever their inputs live).
 """
 from __future__ import annotations
 
@@ -413,6 +417,42 @@ def render_queries(view, pc, pipe, bg, iteration, leaf_cluster_idx, selections, 
 
 
 # ---- pixel -> label ------------------------------------------------------------------------------------------------------------
+def _kept_pass_of_view(view, pc, pipe, bg, xyz, scaling_modifier):
+    """The UN-RESCALED ungrouped streaming pass of a view, for the kernels that walk a finished pass again: the pass ``render()``
+    kept for this camera when the model is frozen (a look at ``rasterizer.KEPT_PASSES``, not a lookup: slots and counters stay
+    as they are), else one pass run here (its colour is never read, so the means stand in for it) whose state the caller drops.
+    None when nothing reaches a tile of the view.  Call under ``no_grad``."""
+    frozen = _renderer._frozen_geometry_key(view, pc, pipe, xyz, scaling_modifier)
+    if frozen is not None:
+        e = _rasterizer.KEPT_PASSES.slots.get(frozen[0])
+        if e is not None and e.key[0] == frozen[1] and e.full_binning == bool(_rasterizer.FULL_BINNING):
+            return e
+    if xyz.shape[0] == 0:
+        return None
+    settings = _rasterizer.GaussianRasterizationSettings(
+        image_height=int(view.image_height), image_width=int(view.image_width), tanfovx=math.tan(view.FoVx * 0.5),
+        tanfovy=math.tan(view.FoVy * 0.5), bg=bg, scale_modifier=float(scaling_modifier), viewmatrix=view.world_view_transform,
+        projmatrix=view.full_proj_transform, sh_degree=pc.active_sh_degree, campos=view.camera_center,
+        prefiltered=False, debug=pipe.debug)
+    means3D = xyz.detach()
+    scales = rotations = cov3D = None
+    if pipe.compute_cov3D_python:
+        cov3D = pc.get_covariance(scaling_modifier).detach()
+    else:
+        scales, rotations = pc.get_scaling.detach(), pc.get_rotation.detach()
+    sink: list = []
+    _rasterizer._RasterizeGaussians.apply(means3D, torch.zeros_like(means3D), None, means3D, pc.get_opacity.detach(),
+                                          scales, rotations, cov3D, settings, 0, None, None, 1, sink, True)
+    return sink[0] if sink else None
+
+
+def _forward_only(pc, pipe, xyz, who):
+    if torch.is_grad_enabled():
+        probe = [xyz, pc.get_opacity] + ([] if pipe.compute_cov3D_python else [pc.get_scaling, pc.get_rotation])
+        if any(t.requires_grad for t in probe):
+            raise RuntimeError(f"{who} is forward only: call it under torch.no_grad() or detach the model")
+
+
 def render_label_map(view, pc, pipe, bg, iteration, point_labels, num_labels, pre_mask=None, scaling_modifier=1.0):
     """``LabelMap(label [H,W] int32, weight, second, alpha [H,W] fp32)`` of one view: per pixel the label whose Gaussians carry the
     largest summed blend weight (lowest label on an exact tie, -1 where no labelled Gaussian contributes), that weight, the
@@ -435,39 +475,14 @@ def render_label_map(view, pc, pipe, bg, iteration, point_labels, num_labels, pr
         raise ValueError(f"point_labels must be [{P}], got {tuple(point_labels.shape)}")
     if pre_mask is not None and pre_mask.shape != (P,):
         raise ValueError(f"pre_mask must be [{P}], got {tuple(pre_mask.shape)}")
-    if torch.is_grad_enabled():
-        probe = [xyz, pc.get_opacity] + ([] if pipe.compute_cov3D_python else [pc.get_scaling, pc.get_rotation])
-        if any(t.requires_grad for t in probe):
-            raise RuntimeError("render_label_map is forward only: call it under torch.no_grad() or detach the model")
+    _forward_only(pc, pipe, xyz, "render_label_map")
     with torch.no_grad():
         dev = xyz.device
         H, W = int(view.image_height), int(view.image_width)
         labels = point_labels.to(dev)
         if pre_mask is not None:
             labels = torch.where(pre_mask.to(dev).to(torch.bool), labels, torch.full_like(labels, -1))
-        kept = None
-        frozen = _renderer._frozen_geometry_key(view, pc, pipe, xyz, scaling_modifier)
-        if frozen is not None:
-            # a look, not a lookup: the cache's slots and counters stay as they are
-            e = _rasterizer.KEPT_PASSES.slots.get(frozen[0])
-            if e is not None and e.key[0] == frozen[1] and e.full_binning == bool(_rasterizer.FULL_BINNING):
-                kept = e
-        if kept is None and P > 0:
-            settings = _rasterizer.GaussianRasterizationSettings(
-                image_height=H, image_width=W, tanfovx=math.tan(view.FoVx * 0.5), tanfovy=math.tan(view.FoVy * 0.5), bg=bg,
-                scale_modifier=float(scaling_modifier), viewmatrix=view.world_view_transform,
-                projmatrix=view.full_proj_transform, sh_degree=pc.active_sh_degree, campos=view.camera_center,
-                prefiltered=False, debug=pipe.debug)
-            means3D = xyz.detach()
-            scales = rotations = cov3D = None
-            if pipe.compute_cov3D_python:
-                cov3D = pc.get_covariance(scaling_modifier).detach()
-            else:
-                scales, rotations = pc.get_scaling.detach(), pc.get_rotation.detach()
-            sink: list = []
-            _rasterizer._RasterizeGaussians.apply(means3D, torch.zeros_like(means3D), None, means3D, pc.get_opacity.detach(),
-                                                  scales, rotations, cov3D, settings, 0, None, None, 1, sink, True)
-            kept = sink[0] if sink else None
+        kept = _kept_pass_of_view(view, pc, pipe, bg, xyz, scaling_modifier)
         if kept is None:
             # nothing reaches a tile of this view: an empty map
             z = lambda: torch.zeros(H, W, dtype=torch.float32, device=dev)
@@ -563,3 +578,106 @@ def select_leaves_by_click(root_feats, leaf_feats, root_centers, leaf_centers):
     k = torch.arange(N, device=d_leaf.device)[None, :]
     inside = (k >= start[:, None]) & (k < end[:, None])
     return torch.argmin(torch.where(inside, d_leaf, torch.full_like(d_leaf, float("inf"))), dim=1)
+
+
+# ---- pixel labels -> Gaussians -------------------------------------------------------------------------------------------------
+VOTE_QUANTUM = 2.0 ** -32          # one unit of a vote table (include/ogs_query.h: ogs_raster_label_votes)
+
+
+def lift_labels(views, pc, pipe, bg, iteration, label_images, num_labels, rows=None, num_rows=None, scaling_modifier=1.0):
+    """int64 [R, num_labels + 1] vote table over all ``views`` (fixed point, ``votes_as_float``): cell [r, l] = the blend weight
+    alpha * T that the Gaussians of row r put on the pixels whose label image says l, summed over the views and seen through the
+    occlusion of the full scene; column ``num_labels`` collects the pixels without a label (a value outside [0, num_labels)).
+    ``label_images``: per view an [H, W] integer tensor on the GPU (SAM instance ids, class ids, prompt masks); ``rows`` [P]
+    integers map the Gaussians to rows (leaf ids; outside [0, num_rows): not counted), None: one row per Gaussian.
+
+    One launch per view (``rasterizer.label_votes``) over the view's UN-RESCALED pass: the one ``render()`` kept for the camera
+    when the model is frozen, else a pass run here and dropped, the rule of ``render_label_map``.  A view no Gaussian reaches adds
+    nothing.  Forward only: runs under ``no_grad`` and raises when a model tensor requires grad while grad mode is on."""
+    xyz = pc.get_xyz
+    _need_gpu(xyz, "the model")
+    views, label_images = list(views), list(label_images)
+    if len(views) != len(label_images):
+        raise ValueError(f"{len(views)} views but {len(label_images)} label images")
+    P = xyz.shape[0]
+    if rows is not None:
+        if not torch.is_tensor(rows) or rows.shape != (P,):
+            raise ValueError(f"rows must be a [{P}] tensor")
+        if num_rows is None:
+            raise ValueError("num_rows must be given with rows")
+        _need_gpu(rows, "rows")
+    R = P if rows is None else int(num_rows)
+    L = int(num_labels)
+    if R < 1 or L < 0:
+        raise ValueError(f"need num_rows >= 1 and num_labels >= 0, got {R} and {L}")
+    for view, img in zip(views, label_images):
+        if not torch.is_tensor(img) or tuple(img.shape) != (int(view.image_height), int(view.image_width)):
+            raise ValueError(f"a label image must be a [{int(view.image_height)}, {int(view.image_width)}] tensor")
+        _need_gpu(img, "label_images")
+    _forward_only(pc, pipe, xyz, "lift_labels")
+    with torch.no_grad():
+        dev = xyz.device
+        table = torch.zeros(R, L + 1, dtype=torch.int64, device=dev)
+        row32 = None if rows is None else _rasterizer._int32_or_outside(rows, R, dev)
+        for view, img in zip(views, label_images):
+            kept = _kept_pass_of_view(view, pc, pipe, bg, xyz, scaling_modifier)
+            if kept is not None:
+                _rasterizer.label_votes(kept, img, L, rows=row32, num_rows=R, out=table)
+        return table
+
+
+def votes_as_float(table):
+    """a vote table in units of blend weight: fp64, ``table * 2^-32`` (exact below 2^21 of summed weight per cell)"""
+    if table.dtype is not torch.int64:
+        raise ValueError(f"a vote table is int64, got {table.dtype}")
+    return table.to(torch.float64) * VOTE_QUANTUM
+
+
+def labels_from_votes(table, min_weight=0.0, min_share=0.0):
+    """``(label [R] int64, weight, second, total [R] fp64)`` of a vote table [R, L + 1]: per row the label with the largest vote
+    among the columns 0..L-1 (an exact tie, decided on the integers, goes to the lowest label), that vote, the largest vote of any
+    other label, and the row's whole weight, column L included.  The label is -1 where the row holds no labelled weight, where
+    ``weight < min_weight`` or where ``weight / total < min_share``.  Plain torch where the table lives."""
+    if table.dim() != 2 or table.shape[1] < 1 or table.dtype is not torch.int64:
+        raise ValueError(f"a vote table is int64 [R, L + 1], got {table.dtype} {tuple(table.shape)}")
+    R, L = table.shape[0], table.shape[1] - 1
+    dev = table.device
+    total = table.sum(dim=1)
+    if L == 0:
+        zero = torch.zeros(R, dtype=torch.float64, device=dev)
+        return torch.full((R,), -1, dtype=torch.int64, device=dev), zero, zero.clone(), votes_as_float(total)
+    part = table[:, :L]
+    top = part.max(dim=1).values
+    cols = torch.arange(L, device=dev)[None, :]
+    arg = torch.where(part == top[:, None], cols, torch.full_like(cols, L)).min(dim=1).values       # first maximum: lowest label
+    rest = torch.where(cols == arg[:, None], torch.full_like(part, -1), part)
+    second = rest.max(dim=1).values.clamp_min(0)
+    weight, total_f = votes_as_float(top), votes_as_float(total)
+    # weight / total >= min_share without the quotient: total > 0 wherever top > 0
+    ok = (top > 0) & (weight >= float(min_weight)) & (weight >= float(min_share) * total_f)
+    label = torch.where(ok, arg, torch.full_like(arg, -1))
+    return label, weight, votes_as_float(second), total_f
+
+
+def leaves_from_votes(table, min_share=0.5, min_weight=1.0):
+    """The selection rule of ``select_leaves_by_masks`` on a table [leaves, M + 1] lifted with ``rows = leaf_ind``: for every
+    prompt m the ascending int64 ids of the leaves k with ``votes[k, m] >= min_weight`` (in units of blend weight) and
+    ``votes[k, m] >= min_share * total[k]``, ``total`` being the leaf's whole visible weight, outside every prompt included."""
+    if table.dim() != 2 or table.shape[1] < 1 or table.dtype is not torch.int64:
+        raise ValueError(f"a vote table is int64 [R, M + 1], got {table.dtype} {tuple(table.shape)}")
+    inside = votes_as_float(table[:, :-1])
+    total = votes_as_float(table.sum(dim=1))
+    ok = (inside > 0) & (inside >= float(min_weight)) & (inside >= float(min_share) * total[:, None])
+    return [torch.nonzero(ok[:, m]).flatten() for m in range(ok.shape[1])]
+
+
+def select_leaves_by_masks(views, pc, pipe, bg, iteration, prompt_images, num_prompts, leaf_ind, num_leaves, min_share=0.5,
+                           min_weight=1.0):
+    """Mask prompts -> leaves: ``prompt_images`` holds per view an [H, W] integer image with the value m in [0, num_prompts)
+    inside prompt m (a SAM mask, a box) and -1 elsewhere.  The images are lifted with ``rows = leaf_ind`` (``lift_labels``: one
+    launch per view, full-scene occlusion), and prompt m selects the leaves whose weight inside it is at least ``min_weight`` and
+    at least ``min_share`` of the leaf's visible weight over the views (``leaves_from_votes``).  Returns a list of
+    ``num_prompts`` ascending leaf-id tensors, what ``render_queries`` takes as ``selections``.  The two defaults (half of the
+    leaf's weight, one pixel's worth of weight) are conveniences, not tuned values."""
+    table = lift_labels(views, pc, pipe, bg, iteration, prompt_images, num_prompts, rows=leaf_ind, num_rows=num_leaves)
+    return leaves_from_votes(table, min_share=min_share, min_weight=min_weight)

@@ -790,6 +790,70 @@ def label_map(kept, labels, num_labels):
     return out_label, weight, second, alpha
 
 
+def _int32_or_outside(t, upper, dev):
+    """an integer tensor as contiguous int32 on `dev`; a value outside [0, upper) becomes -1 BEFORE the narrowing, so a 64-bit
+    value outside the int32 range stays outside instead of wrapping into range"""
+    t = t.detach().to(device=dev)
+    if t.dtype is not torch.int32:
+        t = torch.where((t >= 0) & (t < upper), t, torch.full_like(t, -1)).to(torch.int32)
+    return t.contiguous()
+
+
+def label_votes(kept, pixel_labels, num_labels, rows=None, num_rows=None, out=None):
+    """Pixel labels lifted to Gaussians (ogs_raster_label_votes, include/ogs_query.h): ONE launch over the kept quadrant streams.
+
+    kept: what an ungrouped streaming pass left in ``keep_sink``, or a ``KeptPasses`` entry.  pixel_labels: [H, W] integer tensor
+    on the GPU; a value outside [0, num_labels) counts in column ``num_labels`` (no label).  rows: [P] integer tensor mapping
+    every Gaussian to a table row (a leaf id, say), a row outside [0, num_rows) is not counted but still occludes; None: the
+    Gaussian's own index, num_rows = P.
+    Returns the int64 table [num_rows, num_labels + 1] in fixed point, quantum 2^-32 (``query.votes_as_float``):
+    cell [r, l] = summed blend weight alpha * T that the Gaussians of row r put on the pixels of label l.  ``out`` (same shape,
+    int64, on the GPU) is ACCUMULATED into and returned, so several views sum into one table; without it a zeroed table is made.
+    Forward only; integer accumulation: two calls give the same bytes."""
+    P, W, H, Cn, image, sorted_rec, quad_list = _kept_state(kept)
+    if not torch.is_tensor(pixel_labels):
+        raise RuntimeError("pixel_labels must be a tensor")
+    if pixel_labels.is_floating_point() or pixel_labels.is_complex() or pixel_labels.dtype is torch.bool:
+        raise RuntimeError(f"pixel_labels must have an integer dtype, got {pixel_labels.dtype}")
+    if tuple(pixel_labels.shape) != (H, W):
+        raise RuntimeError(f"the pass is {H} x {W} pixels, pixel_labels is {tuple(pixel_labels.shape)}")
+    L = int(num_labels)
+    if L < 0 or L > 2 ** 31 - 2:
+        raise RuntimeError(f"num_labels must be in [0, 2^31 - 1), got {num_labels}")
+    if rows is not None:
+        if not torch.is_tensor(rows) or rows.is_floating_point() or rows.is_complex() or rows.dtype is torch.bool:
+            raise RuntimeError("rows must be an integer tensor")
+        if rows.numel() != P:
+            raise RuntimeError(f"the pass holds {P} Gaussians, rows has {rows.numel()} entries")
+        if num_rows is None:
+            raise RuntimeError("num_rows must be given with rows")
+    Rn = P if num_rows is None else int(num_rows)
+    if Rn < 1 or Rn > 2 ** 31 - 1:
+        raise RuntimeError(f"num_rows must be in [1, 2^31), got {num_rows}")
+    if out is not None and (not torch.is_tensor(out) or out.dtype is not torch.int64 or tuple(out.shape) != (Rn, L + 1)
+                            or not out.is_contiguous()):
+        raise RuntimeError(f"out must be a contiguous int64 tensor [{Rn}, {L + 1}]")
+    _require_gpu(pixel_labels, "pixel_labels")
+    if rows is not None:
+        _require_gpu(rows, "rows")
+    if out is not None:
+        _require_gpu(out, "out")
+    _require_gpu(image, "the kept pass")
+    dev = image.device
+    lab = _int32_or_outside(pixel_labels, L, dev)
+    row = None if rows is None else _int32_or_outside(rows.reshape(-1), Rn, dev)
+    votes = torch.zeros(Rn, L + 1, dtype=torch.int64, device=dev) if out is None else out
+    a = OgsRasterFwdArgs()
+    a.P, a.W, a.H, a.C = P, W, H, Cn
+    a.image_buffer, a.sorted_rec, a.quad_list = ptr(image), ptr(sorted_rec), ptr(quad_list)
+    lv = _lib.OgsLabelVotesArgs()
+    lv.pixel_labels, lv.num_labels = ptr(lab), L
+    lv.rows, lv.num_rows = (None if row is None else ptr(row)), Rn
+    lv.votes = ptr(votes)
+    check(_lib.lib().ogs_raster_label_votes(C.byref(a), C.byref(lv), _stream()), "ogs_raster_label_votes")
+    return votes
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, sh_rgb_sink=None):
     """sh_rgb_sink (extension, data parallelism): a list.  When given, backward does NOT produce the dense
