@@ -92,6 +92,29 @@
  * walk: a quadrant's up to ogs_label_votes_quadrant_capacity() distinct labels are folded ogs_label_votes_fold_columns() at a
  * time over the same staged weights.  Forward only.  Asynchronous.
  *
+ * ---- feature votes (ogs_raster_feature_votes) ------------------------------------------------------------------------------
+ * Dense per-pixel vectors -> Gaussians: the label votes with a feature IMAGE F [D, H, W] (channel-planar fp32) in place of
+ * the label image.  `pass`, w_i(p) and row(g) are those of ogs_raster_label_votes.  With v(p) = 1 inside the image where
+ * valid == NULL or valid[p] != 0, else 0, the call ADDS to the table (the caller clears it; V views sum into one table)
+ *     votes[row(g), c] += sum over the pixels p of v(p) * w_{entry of g}(p) * F[c, p]      c < D     int64 [R, D + 1], 2^-32
+ *     votes[row(g), D] += sum over the pixels p of v(p) * w_{entry of g}(p)                          the weight column
+ * so votes[r, :D] / votes[r, D] is the blend-weighted mean feature of row r.  An invalid pixel contributes to no column; it
+ * is occluded and occludes as every other pixel (valid never changes a weight).
+ * Rounding: a PARTIAL -- one entry, one 8 x 8 quadrant, one column -- is the fp32 value (fma chain over the pixels 4 j + k of
+ * the even j) + (the same over the odd j), a function of the weights and of that column's 64 values v(p) * F[c, p] only, not
+ * of the column's index; it is rounded once, llrint(partial * 2^32), and added in two's complement (a partial may be
+ * negative).  Hence, as exact integer equalities: two runs and both layouts give the same bytes, rows = r equals index_add
+ * of rows = NULL, two calls give twice the table, -F negates the columns < D, a permutation of the channels permutes the
+ * columns, any split of the channels over several calls gives the columns of the one call, the weight column equals column 0
+ * of ogs_raster_label_votes over the image (valid ? 0 : -1) with num_labels = 1, and one-hot planes F[c] = (lab == c) give
+ * the columns of ogs_raster_label_votes.
+ * Range (the caller's contract, nothing is read back to check it): F finite; a partial below 2^31, i.e. 64 * max|F| < 2^31;
+ * a cell below 2^31 of summed magnitude.  Cell addresses are computed in 64 bits; every index (Gaussian id < P,
+ * 0 <= row < R, column <= D) is checked on the device before it is used.  ONE call and one launch whatever D is: a wave
+ * holds ogs_feature_votes_block_columns() columns in registers and the walk is repeated per such block along the grid's
+ * second dimension (D + 1 <= 65535 * that); inside, the columns are folded ogs_feature_votes_fold_columns() at a time.
+ * Forward only.  Asynchronous.
+ *
  * No entry point reads anything back from the device.  All pointers are device pointers, `stream` is a hipStream_t as
  * void*.  Returns 0 or a negative OGS_ERR_* code.
  */
@@ -158,6 +181,18 @@ typedef struct OgsLabelVotesArgs {
 int ogs_raster_label_votes(const OgsRasterFwdArgs* pass, const OgsLabelVotesArgs* lv, void* stream);
 size_t ogs_label_votes_quadrant_capacity(void);  /* test hook: distinct labels of one quadrant folded per walk */
 size_t ogs_label_votes_fold_columns(void);       /* test hook: of those, the labels of one column block of the fold */
+
+typedef struct OgsFeatureVotesArgs {
+    const float* features;       /* [D,H,W] channel-planar, finite, 64 * max|F| < 2^31 */
+    int32_t num_channels;        /* D >= 1 */
+    const uint8_t* valid;        /* [H,W] or NULL (every pixel counts); 0 = the pixel contributes to no column */
+    const int32_t* rows;         /* [P] or NULL (row = Gaussian index); outside [0, num_rows): not counted */
+    int32_t num_rows;            /* R >= 1 */
+    int64_t* votes;              /* [R, D+1], quantum 2^-32, accumulated into; column D = the weight */
+} OgsFeatureVotesArgs;
+int ogs_raster_feature_votes(const OgsRasterFwdArgs* pass, const OgsFeatureVotesArgs* fv, void* stream);
+size_t ogs_feature_votes_fold_columns(void);     /* test hook: columns of one MFMA block of the fold */
+size_t ogs_feature_votes_block_columns(void);    /* test hook: columns a wave holds per walk; D + 1 columns take ceil((D + 1) / this) walks */
 
 #ifdef __cplusplus
 }

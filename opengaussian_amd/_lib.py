@@ -80,6 +80,12 @@ class OgsLabelVotesArgs(C.Structure):
     _fields_ = [("pixel_labels", _vp), ("num_labels", C.c_int32), ("rows", _vp), ("num_rows", C.c_int32), ("votes", _vp)]
 
 
+class OgsFeatureVotesArgs(C.Structure):
+    """include/ogs_query.h: a feature image in, the [R, D + 1] fixed-point table accumulated into."""
+    _fields_ = [("features", _vp), ("num_channels", C.c_int32), ("valid", _vp), ("rows", _vp), ("num_rows", C.c_int32),
+                ("votes", _vp)]
+
+
 class OgsRawModel(C.Structure):
     """include/ogs_model.h: the reference model's raw parameters."""
     _fields_ = [("features_dc", _vp), ("features_rest", _vp), ("scaling", _vp), ("rotation", _vp), ("opacity", _vp)]
@@ -197,6 +203,9 @@ SIGNATURES = {
     "ogs_raster_label_votes": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsLabelVotesArgs), _vp]),
     "ogs_label_votes_quadrant_capacity": (C.c_size_t, []),
     "ogs_label_votes_fold_columns": (C.c_size_t, []),
+    "ogs_raster_feature_votes": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsFeatureVotesArgs), _vp]),
+    "ogs_feature_votes_fold_columns": (C.c_size_t, []),
+    "ogs_feature_votes_block_columns": (C.c_size_t, []),
 }
 
 _lib = None

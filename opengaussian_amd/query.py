@@ -13,6 +13,9 @@
                             label images, one launch per view (``rasterizer.label_votes``), an int64 fixed-point table;
                             ``votes_as_float`` / ``labels_from_votes`` read it, ``select_leaves_by_masks`` turns mask prompts into
                             the leaf selections ``render_queries`` takes (``leaves_from_votes`` is its rule)
+``lift_features``           dense per-pixel vectors -> Gaussians: the blend-weighted sum of the views' feature images per Gaussian (or
+                            leaf) with the weight beside it, one call per view (``rasterizer.feature_votes``) into one int64 table;
+                            ``features_from_votes`` divides; ``lift_mask_features`` is the route for features kept per 2D mask
 ``click_features`` /        the reference's own click route (scripts/render_by_click.py:35-66,138-166), batched over clicks, in
 ``select_leaves_by_click``  plain torch
 
@@ -631,6 +634,143 @@ def votes_as_float(table):
     if table.dtype is not torch.int64:
         raise ValueError(f"a vote table is int64, got {table.dtype}")
     return table.to(torch.float64) * VOTE_QUANTUM
+
+
+def _rows_of_call(xyz, rows, num_rows):
+    """(P, R) of a lift call after the checks ``lift_labels`` makes on ``rows`` / ``num_rows``"""
+    P = xyz.shape[0]
+    if rows is not None:
+        if not torch.is_tensor(rows) or rows.shape != (P,):
+            raise ValueError(f"rows must be a [{P}] tensor")
+        if num_rows is None:
+            raise ValueError("num_rows must be given with rows")
+        _need_gpu(rows, "rows")
+    R = P if rows is None else int(num_rows)
+    if R < 1:
+        raise ValueError(f"need num_rows >= 1, got {R}")
+    return P, R
+
+
+def lift_features(views, pc, pipe, bg, iteration, feature_images, valid_images=None, rows=None, num_rows=None,
+                  scaling_modifier=1.0):
+    """int64 [R, D + 1] table over all ``views`` (fixed point, ``features_from_votes``): cell [r, c < D] = the sum over the views'
+    valid pixels of alpha * T * F[c] of the Gaussians of row r, seen through the occlusion of the full scene; column D the summed
+    alpha * T itself.  ``feature_images``: per view a floating [D, H, W] tensor on the GPU (CLIP / DINO / LSeg maps,
+    ``pesudo_ins_feat``, an error image), the same D for all; ``valid_images``: None, or per view None or a bool / integer [H, W]
+    tensor whose zero pixels contribute nothing; ``rows`` [P] integers map the Gaussians to rows (leaf ids; outside
+    [0, num_rows): not counted), None: one row per Gaussian.
+
+    One call per view (``rasterizer.feature_votes``, whose range contract holds per view) into one table, over the view's
+    UN-RESCALED pass: the one ``render()`` kept for the camera when the model is frozen, else a pass run here and dropped, the
+    rule of ``lift_labels``.  A view no Gaussian reaches adds nothing.  Forward only: runs under ``no_grad`` and raises when a
+    model tensor requires grad while grad mode is on."""
+    xyz = pc.get_xyz
+    _need_gpu(xyz, "the model")
+    views, feature_images = list(views), list(feature_images)
+    if len(views) != len(feature_images):
+        raise ValueError(f"{len(views)} views but {len(feature_images)} feature images")
+    valid_images = [None] * len(views) if valid_images is None else list(valid_images)
+    if len(views) != len(valid_images):
+        raise ValueError(f"{len(views)} views but {len(valid_images)} valid images")
+    if not views:
+        raise ValueError("need at least one view: the table's width is that of its feature image")
+    P, R = _rows_of_call(xyz, rows, num_rows)
+    D = None
+    for view, img, ok in zip(views, feature_images, valid_images):
+        hw = (int(view.image_height), int(view.image_width))
+        if not torch.is_tensor(img) or not img.is_floating_point() or img.dim() != 3 or tuple(img.shape[1:]) != hw or img.shape[0] < 1:
+            raise ValueError(f"a feature image must be a floating [D, {hw[0]}, {hw[1]}] tensor")
+        D = int(img.shape[0]) if D is None else D
+        if int(img.shape[0]) != D:
+            raise ValueError(f"the feature images have {D} and {int(img.shape[0])} channels")
+        _need_gpu(img, "feature_images")
+        if ok is not None:
+            if not torch.is_tensor(ok) or ok.is_floating_point() or tuple(ok.shape) != hw:
+                raise ValueError(f"a valid image must be a bool or integer [{hw[0]}, {hw[1]}] tensor")
+            _need_gpu(ok, "valid_images")
+    _forward_only(pc, pipe, xyz, "lift_features")
+    with torch.no_grad():
+        dev = xyz.device
+        table = torch.zeros(R, D + 1, dtype=torch.int64, device=dev)
+        row32 = None if rows is None else _rasterizer._int32_or_outside(rows, R, dev)
+        for view, img, ok in zip(views, feature_images, valid_images):
+            kept = _kept_pass_of_view(view, pc, pipe, bg, xyz, scaling_modifier)
+            if kept is not None:
+                _rasterizer.feature_votes(kept, img, valid=ok, rows=row32, num_rows=R, out=table)
+        return table
+
+
+def features_from_votes(table, min_weight=0.0):
+    """``(feat [R, D] fp64, weight [R] fp64)`` of a feature-vote table [R, D + 1]: the blend-weighted mean feature of every row,
+    ``sums / weight``, and the row's weight (column D) in units of blend weight.  Rows with ``weight <= min_weight`` (never seen,
+    or seen too little to trust) get a zero feature.  Plain torch where the table lives."""
+    if table.dim() != 2 or table.shape[1] < 2 or table.dtype is not torch.int64:
+        raise ValueError(f"a feature-vote table is int64 [R, D + 1] with D >= 1, got {table.dtype} {tuple(table.shape)}")
+    weight = votes_as_float(table[:, -1])
+    sums = votes_as_float(table[:, :-1])
+    ok = weight > float(min_weight)
+    feat = torch.where(ok[:, None], sums / torch.where(ok, weight, torch.ones_like(weight))[:, None], torch.zeros_like(sums))
+    return feat, weight
+
+
+def lift_mask_features(views, pc, pipe, bg, iteration, label_images, mask_feats, rows=None, num_rows=None, scaling_modifier=1.0):
+    """Features that exist per 2D MASK lifted to Gaussians: ``label_images`` holds per view an [H, W] integer image of mask ids
+    (the SAM ids of ``association.sam_mask_ids``; a value outside [0, L_v) is no mask) and ``mask_feats`` per view an [L_v, D]
+    tensor with the feature of every mask (the reference's ``view.original_mask_feat``).  Returns ``(feat_sum [R, D] fp64,
+    weight [R] fp64)``: the sum over the views and masks of (blend weight alpha * T of row r on the mask's pixels) * (the mask's
+    feature), and the summed weight on masked pixels; ``feat_sum / weight`` is the row's mean feature, and with
+    ``rows = leaf_ind`` a ``leaf_feat`` for ``select_leaves_by_text``.
+
+    Per view ONE ``rasterizer.label_votes`` launch into a per-view table (reused while L_v stays the same), then
+    ``votes_as_float(table[:, :L_v]) @ mask_feats[v]`` in fp64: no feature image is ever made.  It equals ``lift_features`` of the
+    image F(p) = mask_feats[lab(p)] with the unmasked pixels invalid, up to fp32 rounding of that route's partials.  Pass rule and
+    forward-only rule as in ``lift_labels``."""
+    xyz = pc.get_xyz
+    _need_gpu(xyz, "the model")
+    views, label_images, mask_feats = list(views), list(label_images), list(mask_feats)
+    if not (len(views) == len(label_images) == len(mask_feats)):
+        raise ValueError(f"{len(views)} views, {len(label_images)} label images and {len(mask_feats)} mask feature tables")
+    if not views:
+        raise ValueError("need at least one view: the width of the result is that of its mask features")
+    P, R = _rows_of_call(xyz, rows, num_rows)
+    D = None
+    for view, img, mf in zip(views, label_images, mask_feats):
+        if not torch.is_tensor(img) or tuple(img.shape) != (int(view.image_height), int(view.image_width)):
+            raise ValueError(f"a label image must be a [{int(view.image_height)}, {int(view.image_width)}] tensor")
+        if not torch.is_tensor(mf) or not mf.is_floating_point() or mf.dim() != 2:
+            raise ValueError("mask features must be a floating [L, D] tensor per view")
+        D = int(mf.shape[1]) if D is None else D
+        if int(mf.shape[1]) != D:
+            raise ValueError(f"the mask features have {D} and {int(mf.shape[1])} channels")
+        _need_gpu(img, "label_images")
+        _need_gpu(mf, "mask_feats")
+    _forward_only(pc, pipe, xyz, "lift_mask_features")
+    with torch.no_grad():
+        dev = xyz.device
+        feat_sum = torch.zeros(R, D, dtype=torch.float64, device=dev)
+        weight = torch.zeros(R, dtype=torch.float64, device=dev)
+        row32 = None if rows is None else _rasterizer._int32_or_outside(rows, R, dev)
+        table = None
+        for view, img, mf in zip(views, label_images, mask_feats):
+            L = int(mf.shape[0])
+            kept = _kept_pass_of_view(view, pc, pipe, bg, xyz, scaling_modifier)
+            if kept is None:
+                continue
+            if table is None or table.shape[1] != L + 1:
+                table = torch.zeros(R, L + 1, dtype=torch.int64, device=dev)
+            else:
+                table.zero_()
+            _rasterizer.label_votes(kept, img, L, rows=row32, num_rows=R, out=table)
+            feat_sum, weight = _mask_votes_times_feats(table, mf, feat_sum, weight)
+        return feat_sum, weight
+
+
+def _mask_votes_times_feats(table, mask_feats, feat_sum, weight):
+    """one view of ``lift_mask_features``: the label-vote table [R, L + 1] of the view times its mask features [L, D], in fp64;
+    column L (no mask) carries no feature and no weight"""
+    L = table.shape[1] - 1
+    votes = votes_as_float(table[:, :L])
+    return feat_sum + votes @ mask_feats.detach().to(device=table.device, dtype=torch.float64), weight + votes.sum(dim=1)
 
 
 def labels_from_votes(table, min_weight=0.0, min_share=0.0):
