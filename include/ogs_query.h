@@ -115,6 +115,26 @@
  * second dimension (D + 1 <= 65535 * that); inside, the columns are folded ogs_feature_votes_fold_columns() at a time.
  * Forward only.  Asynchronous.
  *
+ * ---- feature map (ogs_raster_feature_map) ----------------------------------------------------------------------------------
+ * Gaussians -> dense per-pixel vectors, the transpose of the feature votes: a table X [R, D] (row-major fp32, one row per
+ * Gaussian or per row(g): a leaf's CLIP / DINO / LSeg feature, say) rendered into the image of the view.  `pass`, w_i(p) and
+ * row(g) are those of ogs_raster_feature_votes (ungrouped streaming pass, either layout, only read; R = P without rows).  For
+ * every pixel p inside the image and every column c < D the call WRITES (it does not accumulate)
+ *     out_map[c, p] = the chain acc = fmaf(w_i(p), X[row(g_i), c], acc) from +0 over the entries i of p's tile in depth order
+ * over the entries whose row is counted; an entry that puts no weight on the pixel leaves acc as it is, a row outside
+ * [0, num_rows) occludes and adds nothing.  That is the forward blend's own chain with a zero background: the planes equal those
+ * of ceil(D / 12) ogs_raster_forward_reblend launches over [P, 12] slices of X[row(g)], bit for bit, whatever the split of the
+ * columns over MFMA blocks, walks or calls.  channels_last = 0: out_map is [D, H, W]; 1: [H, W, D].
+ *     out_alpha (optional) = the sum of ALL w_i, counted or not: the pass's own alpha image, bit for bit
+ * so out_map / out_alpha is the blend-weighted mean feature where every row is counted, and (1 - out_alpha) * bg adds a
+ * background.  No atomics, one writer per element: two calls give the same bytes; -X negates the map; a permutation of the
+ * columns permutes the planes.  X must be finite (an entry without weight on a pixel is multiplied by 0, not skipped).
+ * Output addresses are computed in 64 bits; every index (Gaussian id < P, 0 <= row < R, column < D, pixel inside the image) is
+ * checked on the device where it is used.  ONE call and one launch whatever D is: a wave accumulates
+ * ogs_feature_map_block_columns() columns per walk, ogs_feature_map_fold_columns() per MFMA block, and the walk is repeated per
+ * such block along the grid's second dimension (D <= 65535 * that).  It is the adjoint of ogs_raster_feature_votes in X, which is
+ * therefore its backward.  Forward only.  Asynchronous.
+ *
  * No entry point reads anything back from the device.  All pointers are device pointers, `stream` is a hipStream_t as
  * void*.  Returns 0 or a negative OGS_ERR_* code.
  */
@@ -193,6 +213,19 @@ typedef struct OgsFeatureVotesArgs {
 int ogs_raster_feature_votes(const OgsRasterFwdArgs* pass, const OgsFeatureVotesArgs* fv, void* stream);
 size_t ogs_feature_votes_fold_columns(void);     /* test hook: columns of one MFMA block of the fold */
 size_t ogs_feature_votes_block_columns(void);    /* test hook: columns a wave holds per walk; D + 1 columns take ceil((D + 1) / this) walks */
+
+typedef struct OgsFeatureMapArgs {
+    const float* features;       /* [R, D] row-major fp32, finite */
+    int32_t num_channels;        /* D >= 1 */
+    const int32_t* rows;         /* [P] or NULL (row = Gaussian index, R = P); outside [0, num_rows): occludes, adds nothing */
+    int32_t num_rows;            /* R >= 1 */
+    int32_t channels_last;       /* 0: out_map [D,H,W] planar;  1: out_map [H,W,D] */
+    float* out_map;              /* every in-image element is written by the call (not accumulated into) */
+    float* out_alpha;            /* [H,W] or NULL: the sum of ALL weights of the pixel */
+} OgsFeatureMapArgs;
+int ogs_raster_feature_map(const OgsRasterFwdArgs* pass, const OgsFeatureMapArgs* fm, void* stream);
+size_t ogs_feature_map_fold_columns(void);       /* test hook: columns of one MFMA block */
+size_t ogs_feature_map_block_columns(void);      /* test hook: columns a wave accumulates per walk; D columns take ceil(D / this) walks */
 
 #ifdef __cplusplus
 }

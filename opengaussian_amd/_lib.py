@@ -86,6 +86,12 @@ class OgsFeatureVotesArgs(C.Structure):
                 ("votes", _vp)]
 
 
+class OgsFeatureMapArgs(C.Structure):
+    """include/ogs_query.h: a feature table [R, D] in, the rendered map (and the alpha) out."""
+    _fields_ = [("features", _vp), ("num_channels", C.c_int32), ("rows", _vp), ("num_rows", C.c_int32),
+                ("channels_last", C.c_int32), ("out_map", _vp), ("out_alpha", _vp)]
+
+
 class OgsRawModel(C.Structure):
     """include/ogs_model.h: the reference model's raw parameters."""
     _fields_ = [("features_dc", _vp), ("features_rest", _vp), ("scaling", _vp), ("rotation", _vp), ("opacity", _vp)]
@@ -206,6 +212,9 @@ SIGNATURES = {
     "ogs_raster_feature_votes": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsFeatureVotesArgs), _vp]),
     "ogs_feature_votes_fold_columns": (C.c_size_t, []),
     "ogs_feature_votes_block_columns": (C.c_size_t, []),
+    "ogs_raster_feature_map": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsFeatureMapArgs), _vp]),
+    "ogs_feature_map_fold_columns": (C.c_size_t, []),
+    "ogs_feature_map_block_columns": (C.c_size_t, []),
 }
 
 _lib = None

@@ -38,6 +38,8 @@ EXTRA = {
     "label_votes.hip": ["-ffp-contract=off"],
     # the same weights and the same fold with dense columns: with one-hot planes the partials are those of label_votes.hip, bit for bit
     "feature_votes.hip": ["-ffp-contract=off"],
+    # the same weights again, and alpha as their plain sum: the bits of the pass's alpha and of a re-blend with a zero background
+    "feature_map.hip": ["-ffp-contract=off"],
     # no SLP vectoriser: its v_pk_mul / v_pk_fma pairs in the box tests need even-aligned register pairs and push the six-wave
     # forward kernels into scratch (pack_blend_chunked_kernel<9>: 80 VGPRs + 3 spilled dwords -> 78, none); same operations, same bits.
     # Figures of AMD clang 22.0.0git (roc-7.2.0, HIP 7.2.26015), printed by -Rpass-analysis=kernel-resource-usage: they rest on that

@@ -16,6 +16,9 @@
 ``lift_features``           dense per-pixel vectors -> Gaussians: the blend-weighted sum of the views' feature images per Gaussian (or
                             leaf) with the weight beside it, one call per view (``rasterizer.feature_votes``) into one int64 table;
                             ``features_from_votes`` divides; ``lift_mask_features`` is the route for features kept per 2D mask
+``render_feature_map``      Gaussians -> dense per-pixel vectors, the way back: a feature table per Gaussian (or leaf) rendered into a view
+                            in one launch whatever D is (``rasterizer.feature_map``), differentiable in the features with
+                            ``rasterizer.feature_votes`` as its backward; ``relevancy_maps`` reads cosine / LERF relevancy off it
 ``click_features`` /        the reference's own click route (scripts/render_by_click.py:35-66,138-166), batched over clicks, in
 ``select_leaves_by_click``  plain torch
 
@@ -698,6 +701,117 @@ def lift_features(views, pc, pipe, bg, iteration, feature_images, valid_images=N
             if kept is not None:
                 _rasterizer.feature_votes(kept, img, valid=ok, rows=row32, num_rows=R, out=table)
         return table
+
+
+# ---- Gaussians -> dense per-pixel vectors: the lifted features back in the image -----------------------------------------------
+class _FeatureMapOfPass(torch.autograd.Function):
+    """forward: rasterizer.feature_map over a finished pass; backward: its adjoint in the features, rasterizer.feature_votes with the
+    upstream gradient as the feature image.  The geometry of the pass gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, features, kept, rows, channels_last):
+        out, alpha = _rasterizer.feature_map(kept, features, rows=rows, channels_last=channels_last, with_alpha=True)
+        ctx.kept, ctx.rows, ctx.channels_last = kept, rows, bool(channels_last)
+        ctx.shape, ctx.dtype = tuple(features.shape), features.dtype
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx, grad_map, grad_alpha):
+        if grad_map is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        R, D = ctx.shape
+        G = grad_map.detach().to(torch.float32)
+        if ctx.channels_last:
+            G = G.permute(2, 0, 1)
+        G = G.contiguous()
+        H, W = int(G.shape[1]), int(G.shape[2])
+        # The vote table is fixed point: quantum 2^-32, a partial and a cell below 2^31.  A cell is at most max|G| times the
+        # weight its row collects, and a view holds at most H * W of weight, so G is brought to max|G| in [2^(t-1), 2^t) with
+        # t = min(24, 30 - ceil(log2(H W))) by a power of two chosen on the device (no read-back; a zero gradient gives exponent 0 and
+        # stays zero), and the table is scaled back: exact both ways, so a tiny gradient (a mean loss) keeps its relative precision.
+        t = min(24, 30 - max(1, math.ceil(math.log2(H * W))))          # 24: a partial, 64 * max|G|, below 2^31 too
+        _, e = torch.frexp(G.abs().amax())
+        shift = (t - e).clamp(-120, 120).to(torch.int32)
+        votes = _rasterizer.feature_votes(ctx.kept, torch.ldexp(G, shift), rows=ctx.rows,
+                                          num_rows=None if ctx.rows is None else R)
+        grad = torch.ldexp(votes_as_float(votes[:, :D]), -shift).to(ctx.dtype)
+        return grad, None, None, None
+
+
+FeatureMap = namedtuple("FeatureMap", "features alpha")
+
+
+def render_feature_map(view, pc, pipe, bg, iteration, features, rows=None, normalize=False, channels_last=False,
+                       scaling_modifier=1.0):
+    """``FeatureMap(features [D,H,W] fp32 (``channels_last``: [H,W,D]), alpha [H,W] fp32)`` of one view: a feature table rendered
+    through the occlusion of the full scene, in one launch whatever D is (``rasterizer.feature_map``) -- the way back from
+    ``lift_features`` / ``features_from_votes`` to the image, and what ``relevancy_maps`` reads.  ``features``: floating [R, D] on
+    the GPU, finite; ``rows`` [P] integers map every Gaussian to its row (``leaf_ind`` with a [leaves, D] table; outside [0, R):
+    the Gaussian occludes and adds nothing), None: one row per Gaussian, R = P.  The map is ``sum alpha * T * X[row]`` with a zero
+    background; ``normalize=True`` divides it by ``clamp(alpha, 1e-8)``: the blend-weighted mean feature.
+
+    Differentiable in ``features`` (and nothing else): the backward is the adjoint kernel, ``rasterizer.feature_votes`` with the
+    upstream gradient as the feature image, scaled by a power of two into its fixed-point range and back, so features of any
+    width train on frozen geometry with both directions in HIP.  The geometry gets no gradient: the call raises when a model
+    tensor requires grad while grad mode is on.  The pass is the UN-RESCALED one ``render()`` kept for this camera when the model
+    is frozen, else one pass run here and dropped afterwards, the rule of ``render_label_map``."""
+    xyz = pc.get_xyz
+    _need_gpu(xyz, "the model")
+    if not torch.is_tensor(features) or not features.is_floating_point() or features.dim() != 2 or features.shape[0] < 1 \
+            or features.shape[1] < 1:
+        raise ValueError("features must be a floating [R, D] tensor")
+    _need_gpu(features, "features")
+    P = xyz.shape[0]
+    if rows is not None:
+        if not torch.is_tensor(rows) or rows.shape != (P,):
+            raise ValueError(f"rows must be a [{P}] tensor")
+        _need_gpu(rows, "rows")
+    elif features.shape[0] != P:
+        raise ValueError(f"features must be [{P}, D] without rows, got {tuple(features.shape)}")
+    _forward_only(pc, pipe, xyz, "render_feature_map")
+    dev = xyz.device
+    H, W, D = int(view.image_height), int(view.image_width), int(features.shape[1])
+    with torch.no_grad():
+        kept = _kept_pass_of_view(view, pc, pipe, bg, xyz, scaling_modifier)
+        row32 = None if rows is None else _rasterizer._int32_or_outside(rows, int(features.shape[0]), dev)
+    if kept is None:
+        # nothing reaches a tile of this view: an empty map that still hangs on the features
+        out = torch.zeros((H, W, D) if channels_last else (D, H, W), dtype=torch.float32, device=dev) + 0.0 * features.sum().float()
+        return FeatureMap(out, torch.zeros(H, W, dtype=torch.float32, device=dev))
+    out, alpha = _FeatureMapOfPass.apply(features, kept, row32, bool(channels_last))
+    if normalize:
+        out = out / (alpha[..., None] if channels_last else alpha[None]).clamp_min(1e-8)
+    return FeatureMap(out, alpha)
+
+
+def relevancy_maps(feature_map, text_feats, canon_feats=None, channels_last=False, chunk=1 << 16):
+    """[Q, H, W] fp32: per pixel the cosine similarity of the rendered feature (``render_feature_map``: [D, H, W], or [H, W, D]
+    with ``channels_last``) to every row of ``text_feats`` [Q, D]; both sides normalised as ``F.normalize`` does, so a pixel
+    without a feature scores 0.  With ``canon_feats`` [K, D] (LERF's canonical negatives: "object", "things", "stuff",
+    "texture") the LERF relevancy instead: ``min over k of softmax(10 * [sim_q, sim_canon_k])[0]``, 0.5 where the pixel has no
+    feature.  Plain torch where the map lives, differentiable, ``chunk`` pixels at a time over views of the map: no [H * W, D]
+    copy is made in either layout."""
+    if feature_map.dim() != 3 or text_feats.dim() != 2:
+        raise ValueError("feature_map must be [D, H, W] (or [H, W, D] with channels_last) and text_feats [Q, D]")
+    H, W, D = (feature_map.shape if channels_last else (feature_map.shape[1], feature_map.shape[2], feature_map.shape[0]))
+    if text_feats.shape[1] != D or (canon_feats is not None and (canon_feats.dim() != 2 or canon_feats.shape[1] != D)):
+        raise ValueError(f"the map has {D} channels, text_feats / canon_feats must be [*, {D}]")
+    fm = feature_map.to(torch.float32)
+    norm = lambda t: torch.nn.functional.normalize(t.to(device=fm.device, dtype=torch.float32), dim=1)
+    text = norm(text_feats)
+    canon = None if canon_feats is None else norm(canon_feats)
+    flat = fm.reshape(H * W, D) if channels_last else fm.reshape(D, H * W)
+    parts = []
+    for p0 in range(0, H * W, int(chunk)):
+        f = flat[p0:p0 + int(chunk)] if channels_last else flat[:, p0:p0 + int(chunk)]
+        length = f.norm(dim=1 if channels_last else 0).clamp_min(1e-12)
+        dots = (lambda t: (t @ f.t() if channels_last else t @ f) / length[None])
+        sim = dots(text)                                                       # [Q, n]
+        if canon is not None:
+            sim = torch.sigmoid(10.0 * (sim[:, None, :] - dots(canon)[None, :, :])).amin(dim=1)     # the pairwise softmax's first entry
+        parts.append(sim)
+    return torch.cat(parts, dim=1).reshape(text.shape[0], H, W)
 
 
 def features_from_votes(table, min_weight=0.0):

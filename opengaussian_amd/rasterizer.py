@@ -929,6 +929,62 @@ def feature_votes(kept, features, valid=None, rows=None, num_rows=None, out=None
     return votes
 
 
+def feature_map(kept, features, rows=None, channels_last=False, with_alpha=False):
+    """A feature table rendered into the view of a finished pass (ogs_raster_feature_map, include/ogs_query.h): ONE call and one
+    launch over the kept quadrant streams whatever D is -- the transpose of ``feature_votes``.
+
+    kept: what an ungrouped streaming pass left in ``keep_sink``, or a ``KeptPasses`` entry.  features: floating tensor [R, D]
+    on the GPU (lifted CLIP / DINO / LSeg features per Gaussian or per leaf, instance features), used as contiguous fp32; it
+    must be finite.  rows: [P] integer tensor mapping every Gaussian to a row of the table (``leaf_ind``), a row outside [0, R)
+    occludes and adds nothing; None: the Gaussian's own index, and R must be P.
+    Returns the map, fp32 [D, H, W] (``channels_last``: [H, W, D]): per pixel and column the forward blend's own chain
+    ``acc = fmaf(alpha * T, X[row, c], acc)`` in depth order with a zero background, bit for bit what ``ceil(D / 12)`` re-blends
+    of a 12-channel kept pass over slices of ``X[rows]`` give.  ``with_alpha``: ``(map, alpha [H, W])``, the pass's own alpha
+    image, so ``map / alpha`` is the blend-weighted mean feature and ``map + (1 - alpha) * bg`` adds a background.
+    Forward only (``query.render_feature_map`` is differentiable in the features); no atomics: two calls give the same bytes.
+
+    Cost: one walk of the pass per 64 columns (``ogs_feature_map_block_columns()``) plus the map itself, D * H * W * 4 bytes
+    written once.  Against the re-blend route it is 2.1-2.4 x faster at D = 64 and 512 and needs neither a [P, D] copy of a
+    per-leaf table nor a 12-channel kept pass; at D = 16 the two routes cost the same, and a map of up to 12 channels is ONE
+    re-blend of a kept pass, which is the better call there (0.21 against 0.37 ms on the bench scene)."""
+    P, W, H, Cn, image, sorted_rec, quad_list = _kept_state(kept)
+    if not torch.is_tensor(features):
+        raise RuntimeError("features must be a tensor")
+    if not features.is_floating_point():
+        raise RuntimeError(f"features must have a floating dtype, got {features.dtype}")
+    if features.dim() != 2 or features.shape[0] < 1 or features.shape[1] < 1:
+        raise RuntimeError(f"features must be [R >= 1, D >= 1], got {tuple(features.shape)}")
+    Rn, D = int(features.shape[0]), int(features.shape[1])
+    if Rn > 2 ** 31 - 1 or D > 2 ** 31 - 1:
+        raise RuntimeError(f"features is {Rn} x {D}, the limit is 2^31 - 1 each way")
+    if rows is not None:
+        if not torch.is_tensor(rows) or rows.is_floating_point() or rows.is_complex() or rows.dtype is torch.bool:
+            raise RuntimeError("rows must be an integer tensor")
+        if rows.numel() != P:
+            raise RuntimeError(f"the pass holds {P} Gaussians, rows has {rows.numel()} entries")
+    elif Rn != P:
+        raise RuntimeError(f"the pass holds {P} Gaussians, features has {Rn} rows (give rows to map Gaussians to rows)")
+    _require_gpu(features, "features")
+    if rows is not None:
+        _require_gpu(rows, "rows")
+    _require_gpu(image, "the kept pass")
+    dev = image.device
+    feat = features.detach().to(device=dev, dtype=torch.float32).contiguous()
+    row = None if rows is None else _int32_or_outside(rows.reshape(-1), Rn, dev)
+    out = torch.empty((H, W, D) if channels_last else (D, H, W), dtype=torch.float32, device=dev)
+    alpha = torch.empty(H, W, dtype=torch.float32, device=dev) if with_alpha else None
+    a = OgsRasterFwdArgs()
+    a.P, a.W, a.H, a.C = P, W, H, Cn
+    a.image_buffer, a.sorted_rec, a.quad_list = ptr(image), ptr(sorted_rec), ptr(quad_list)
+    fm = _lib.OgsFeatureMapArgs()
+    fm.features, fm.num_channels = ptr(feat), D
+    fm.rows, fm.num_rows = (None if row is None else ptr(row)), Rn
+    fm.channels_last = int(bool(channels_last))
+    fm.out_map, fm.out_alpha = ptr(out), ptr(alpha)
+    check(_lib.lib().ogs_raster_feature_map(C.byref(a), C.byref(fm), _stream()), "ogs_raster_feature_map")
+    return (out, alpha) if with_alpha else out
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, sh_rgb_sink=None):
     """sh_rgb_sink (extension, data parallelism): a list.  When given, backward does NOT produce the dense
