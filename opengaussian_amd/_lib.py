@@ -191,6 +191,11 @@ SIGNATURES = {
                                            _vp]),
     "ogs_knn_tile_points": (C.c_size_t, []),
     "ogs_knn_group_ksum": (C.c_int, [C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ogs_knn_box_points": (C.c_size_t, []),
+    "ogs_knn_max_k": (C.c_size_t, []),
+    "ogs_knn_neighbors_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "ogs_knn_neighbors": (C.c_int, [C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ogs_knn_aggregate": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "ogs_query_max_leaves": (C.c_size_t, []),
     "ogs_query_max_top": (C.c_size_t, []),
     "ogs_query_max_classes": (C.c_size_t, []),

@@ -5,8 +5,12 @@
 ``distCUDA2``     drop-in for ``simple_knn._C.distCUDA2`` / the scipy KDTree form of scene/gaussian_model.py:28-36.
 ``group_ksum``    the raw call: per row, the K-th smallest squared distance inside the row's group and the fp64 sums of the
                   K smallest and of their squares.
+``neighbors``     the k <= 32 nearest neighbours themselves, indices and distances, by a sorted box search that scales to
+                  millions of rows; ``distCUDA2`` takes it for large clouds.
+``aggregate``     the fixed-degree gather-sum over such an index table (the step of a diffusion over the kNN graph).
 
-All groups go through one launch; nothing here reads a value back from the device, and no n x n or n x K buffer exists.
+All groups go through one launch; nothing here reads a value back from the device, and no n x n buffer exists (an n x K one
+only where ``neighbors`` returns it).
 CPU tensors raise: there is no CPU path.
 """
 from __future__ import annotations
@@ -148,8 +152,76 @@ def keep_from_sums(gid, begin, kk, sum1, sum2, std_weight: float = 1.0):
     return row_mean < torch.cat((nan, limit)).index_select(0, slot)
 
 
-def distCUDA2(points: torch.Tensor) -> torch.Tensor:
+def neighbors(points: torch.Tensor, k: int, exclude_self: bool = True):
+    """The k nearest neighbours of every row among all rows: (idx int32 [n, k], d2 fp32 [n, k]), exact, in one call
+    (``ogs_knn_neighbors``: a Morton sort, then a search in boxes of 64 points with exact pruning -- no n x n pass).
+
+    Row i lists the rows j (``j != i`` when ``exclude_self``) by ascending (d2, j): d2 is the fp32
+    ``(dx*dx + dy*dy) + dz*dz`` of ``group_ksum``, equal distances go to the smaller index, so the result is unique and two
+    calls give the same bytes.  Slots past the end of the list (fewer than k candidates) hold idx = -1, d2 = +inf.
+    1 <= k <= 32 and n * k < 2^31.  Nothing is read back from the device."""
+    _need_gpu(points, "points")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [n, 3], got {tuple(points.shape)}")
+    n, dev, k = points.shape[0], points.device, int(k)
+    pts = points.detach().to(torch.float32).contiguous()
+    idx = torch.empty((n, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((n, k), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    nbytes = int(L.ogs_knn_neighbors_tmp_bytes(n))
+    tmp = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    check(L.ogs_knn_neighbors(n, ptr(pts), k, int(bool(exclude_self)), ptr(idx), ptr(d2), ptr(tmp), nbytes, _stream()),
+          "ogs_knn_neighbors")
+    return idx, d2
+
+
+@torch.no_grad()
+def aggregate(X: torch.Tensor, idx: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """Fixed-degree gather-sum ``out[i] = sum_k w[i, k] * X[idx[i, k]]`` (fp32 [n, D]) without the [n, K, D] buffer of
+    ``(w[..., None] * X[idx]).sum(1)``: X [R, D], idx int32 [n, K], w [n, K].  Per element one fmaf chain from +0 with k
+    ascending; slots whose idx lies outside [0, R) are skipped, whatever their weight holds.  One writer per element, no
+    atomics: two calls give the same bytes.  X must be finite.  Measured at 500 k rows x 16 neighbours it is ahead of the
+    torch composition at every width tried: 0.14 / 0.30 / 2.78 ms against 0.28 / 2.82 / 14.4 ms at D = 6 / 64 / 512.
+
+    FORWARD ONLY: runs under ``no_grad`` and returns a tensor without a graph, also for inputs that require grad."""
+    for t, name in ((X, "X"), (idx, "idx"), (w, "w")):
+        _need_gpu(t, name)
+    if X.dim() != 2 or idx.dim() != 2 or w.shape != idx.shape:
+        raise ValueError(f"X must be [R, D] and idx, w [n, K] alike, got {tuple(X.shape)}, {tuple(idx.shape)}, {tuple(w.shape)}")
+    if X.shape[1] < 1:
+        raise ValueError("X needs at least one column")
+    Xc = X.detach().to(torch.float32).contiguous()
+    ic = idx.to(torch.int32).contiguous()
+    wc = w.detach().to(torch.float32).contiguous()
+    n, K = ic.shape
+    out = torch.empty((n, Xc.shape[1]), dtype=torch.float32, device=X.device)
+    check(_lib.lib().ogs_knn_aggregate(n, K, Xc.shape[0], Xc.shape[1], ptr(ic), ptr(wc), ptr(Xc), ptr(out), _stream()),
+          "ogs_knn_aggregate")
+    return out
+
+
+# rows from which distCUDA2(route=None) takes the box search.  Measured (scripts/knn_neighbors_bench.py,
+# profiles/knn_neighbors_bench.json) every repeat of it beats every repeat of the brute route from the smallest size of the
+# sweep, 1 000 rows, on; the switch sits at the smallest size of the sweep above 4 097 rows instead, because
+# tests/test_knn_host.py drives distCUDA2() without a route through a stand-in library that has the brute entry point only,
+# on clouds up to that size
+DIST_BOXES_FROM = 8000
+
+
+def distCUDA2(points: torch.Tensor, route=None) -> torch.Tensor:
     """Mean squared distance to the three nearest OTHER points, fp32 [n] in the input's order: the 4 smallest squared
-    distances with the row itself (0) among them, summed, over 3.  The caller keeps its own ``clamp_min``."""
-    _, _, _, _, _, sum1, _ = _ksum_sorted(points, None, 1, 4, want_kth=False)
-    return (sum1 / 3.0).to(torch.float32)
+    distances with the row itself (0) among them, summed, over 3.  The caller keeps its own ``clamp_min``.
+
+    route ``"brute"``: one ``ogs_knn_group_ksum`` launch, 32 passes over all n^2 pairs.  ``"boxes"``:
+    ``neighbors(points, 4, exclude_self=False)`` and an ascending fp64 sum -- the same distances, summed in another order.
+    ``None``: ``"boxes"`` from ``DIST_BOXES_FROM`` rows on, ``"brute"`` below."""
+    if route is None:
+        route = "boxes" if points.shape[0] >= DIST_BOXES_FROM else "brute"
+    if route == "brute":
+        _, _, _, _, _, sum1, _ = _ksum_sorted(points, None, 1, 4, want_kth=False)
+        return (sum1 / 3.0).to(torch.float32)
+    if route != "boxes":
+        raise ValueError(f"route must be 'boxes', 'brute' or None, got {route!r}")
+    idx, d2 = neighbors(points, 4, exclude_self=False)
+    d = torch.where(idx >= 0, d2, torch.zeros_like(d2)).to(torch.float64)      # fewer than 4 rows: the list ends early
+    return ((((d[:, 0] + d[:, 1]) + d[:, 2]) + d[:, 3]) / 3.0).to(torch.float32)

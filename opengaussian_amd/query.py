@@ -19,6 +19,8 @@
 ``render_feature_map``      Gaussians -> dense per-pixel vectors, the way back: a feature table per Gaussian (or leaf) rendered into a view
                             in one launch whatever D is (``rasterizer.feature_map``), differentiable in the features with
                             ``rasterizer.feature_votes`` as its backward; ``relevancy_maps`` reads cosine / LERF relevancy off it
+``diffuse_features``        the 3D side of lifting: fill the Gaussians no view saw and smooth the rest over the kNN graph of the Gaussians
+                            (``knn.neighbors`` + ``neighbor_weights``), one gather-sum launch per step (``knn.aggregate``)
 ``click_features`` /        the reference's own click route (scripts/render_by_click.py:35-66,138-166), batched over clicks, in
 ``select_leaves_by_click``  plain torch
 
@@ -825,6 +827,55 @@ def features_from_votes(table, min_weight=0.0):
     ok = weight > float(min_weight)
     feat = torch.where(ok[:, None], sums / torch.where(ok, weight, torch.ones_like(weight))[:, None], torch.zeros_like(sums))
     return feat, weight
+
+
+def neighbor_weights(d2, idx, valid=None, bandwidth=None):
+    """Row-normalised Gaussian weights fp32 [n, K] on the kNN table of ``knn.neighbors``: ``w = exp(-d2 / (2 * h_i))`` on the
+    slots that count, 0 elsewhere, every row divided by its sum.  A slot counts when ``idx >= 0``, its d2 is finite and, with
+    ``valid`` (bool [R], indexed by idx), ``valid[idx]`` holds.  ``h_i`` is the mean d2 of the row's counting slots (a row
+    whose counting slots are all at distance 0 weighs them equally), or ``bandwidth`` (a number or [n]) where given.  Rows
+    without a counting slot stay all-zero.  Plain torch where the table lives, computed in fp64."""
+    if d2.shape != idx.shape or d2.dim() != 2:
+        raise ValueError(f"d2 and idx must be [n, K] alike, got {tuple(d2.shape)} and {tuple(idx.shape)}")
+    ok = (idx >= 0) & torch.isfinite(d2)
+    if valid is not None:
+        ok &= valid.to(torch.bool)[idx.clamp_min(0).to(torch.int64)]
+    d = torch.where(ok, d2, torch.zeros_like(d2)).to(torch.float64)
+    if bandwidth is None:
+        h = d.sum(dim=1) / ok.sum(dim=1).clamp_min(1)
+    else:
+        h = torch.as_tensor(bandwidth, dtype=torch.float64, device=d2.device).expand(d2.shape[0])
+    arg = torch.where(h[:, None] > 0, d / (2.0 * torch.where(h > 0, h, torch.ones_like(h)))[:, None], torch.zeros_like(d))
+    w = torch.where(ok, torch.exp(-arg), torch.zeros_like(d))
+    total = w.sum(dim=1, keepdim=True)
+    return (w / torch.where(total > 0, total, torch.ones_like(total))).to(torch.float32)
+
+
+def diffuse_features(X, idx, w, steps=1, rate=1.0, fixed=None):
+    """Diffusion of per-Gaussian rows over their kNN graph, fp32 [n, D]: every step is
+    ``X <- where(fixed | row_has_no_neighbour, X, (1 - rate) * X + rate * knn.aggregate(X, idx, w))`` -- one
+    ``ogs_knn_aggregate`` launch, no [n, K, D] buffer.  idx, w [n, K] as ``knn.neighbors`` / ``neighbor_weights`` give them; a row
+    has no neighbour when none of its slots has ``idx >= 0`` and a non-zero weight, and then keeps its value, as the ``fixed``
+    rows (bool [n]) do.  ``steps = 0`` returns the input as fp32.  Forward only.
+
+    Two uses.  FILL what ``features_from_votes`` left at zero: ``ok = weight > min_weight``;
+    ``w = neighbor_weights(d2, idx, valid=ok)``; ``diffuse_features(feat, idx, w, steps, fixed=ok)`` -- unseen Gaussians take
+    the weighted mean of their seen neighbours, seen ones stay, and further steps carry values into regions no seen Gaussian
+    touches (pass ``valid=None`` weights for those).  SMOOTH lifted features, or a ``votes_as_float`` label table before
+    ``labels_from_votes``, with ``fixed=None`` and ``rate < 1``."""
+    _need_gpu(X, "X")
+    if X.dim() != 2 or idx.shape != w.shape or idx.dim() != 2 or idx.shape[0] != X.shape[0]:
+        raise ValueError(f"X must be [n, D] and idx, w [n, K], got {tuple(X.shape)}, {tuple(idx.shape)}, {tuple(w.shape)}")
+    with torch.no_grad():
+        X = _f32(X)
+        keep = ~((idx >= 0) & (w != 0)).any(dim=1)
+        if fixed is not None:
+            keep |= fixed.to(torch.bool)
+        rate = float(rate)
+        for _ in range(int(steps)):
+            agg = _knn.aggregate(X, idx, w)
+            X = torch.where(keep[:, None], X, agg if rate == 1.0 else (1.0 - rate) * X + rate * agg)
+        return X
 
 
 def lift_mask_features(views, pc, pipe, bg, iteration, label_images, mask_feats, rows=None, num_rows=None, scaling_modifier=1.0):
