@@ -56,10 +56,76 @@ int ogs_knn_neighbors(int64_t n, const float* points, int32_t K, int32_t exclude
 /*
  * Fixed-degree gather-sum: out[i, c] = the chain acc = fmaf(w[i, k], X[idx[i, k], c], acc) from +0, k ascending, over the slots
  * with 0 <= idx[i, k] < R; other slots are skipped and their w is not read as a value.  idx, w [n, K]; X [R, D] finite;
- * out [n, D], one writer per element, no atomics.  Any D >= 1.  Forward only.
+ * out [n, D], one writer per element, no atomics.  Any D >= 1.  Its adjoint is ogs_knn_aggregate_t (gradient with respect to
+ * X) and ogs_knn_edge_dots (with respect to w), below.
  */
 int ogs_knn_aggregate(int64_t n, int32_t K, int64_t R, int32_t D, const int32_t* idx, const float* w, const float* X, float* out,
                       void* stream);
+
+/*
+ * ---- the graph backwards (csrc/knn_graph.hip) ------------------------------------------------------------------------------------
+ * Common to everything below: no float atomics, one writer per element, no read-back; n * K < 2^31, 0 <= R <= INT32_MAX,
+ * D >= 1; bad sizes, NULL pointers and a tmp that is too small return OGS_ERR_INVALID_ARG.  A slot e = i * K + k is VALID when
+ * 0 <= idx[e] < R.  Two identical calls give the same bytes.
+ *
+ * Reverse-edge lists of idx [n, K] over R rows (R != n is allowed): begin [R + 1], slots [n * K], both int32.  For r in
+ * [0, R), slots[begin[r] : begin[r + 1]] holds the valid slots e with idx[e] == r, ascending; begin[0] = 0, begin[R] = the number
+ * of valid slots; a row without an incoming edge has begin[r] == begin[r + 1].  slots from begin[R] on is unspecified (written or
+ * not) and nothing below reads it.  The result is unique.  tmp: ogs_knn_transpose_tmp_bytes(n, K, R) bytes.
+ */
+size_t ogs_knn_transpose_chunk(void);            /* slots of a list that one work item sums (tests sit on both sides of it) */
+size_t ogs_knn_transpose_tmp_bytes(int64_t n, int32_t K, int64_t R);
+int ogs_knn_transpose(int64_t n, int32_t K, int64_t R, const int32_t* idx, int32_t* begin, int32_t* slots, void* tmp,
+                      size_t tmp_bytes, void* stream);
+
+/*
+ * Transposed gather-sum: out[r, c] = sum over the list of r of w[e] * G[e / K, c].  G [n, D], w [n, K], out [R, D]; a row with
+ * an empty list gets +0.  Summation order, a function of (begin, K, D) alone -- C = ogs_knn_transpose_chunk(), m = the list's
+ * length:
+ *   m <= C   one chain acc = fmaf(w[e], G[e / K, c], acc) from +0 over the list in its order;
+ *   m >  C   the list is cut into chunks of C slots (the last one shorter); every chunk is such a chain from +0, computed by a
+ *            work item of its own, and the partials are added left to right in chunk order: ((p0 + p1) + p2) + ...
+ * The four-columns-per-thread form (D % 4 == 0, G and out 16-byte aligned) and the one-column form give the same bytes.
+ * begin values are clamped to [0, n * K], a pair with begin[r + 1] < begin[r] is an empty list and a slot outside [0, n * K) is
+ * skipped, so no content of begin / slots makes a wild address.  The weight of an invalid slot is never read.
+ * tmp: ogs_knn_aggregate_t_tmp_bytes(n, K, R, D) bytes (the work list of the split rows and their partials).
+ */
+size_t ogs_knn_aggregate_t_tmp_bytes(int64_t n, int32_t K, int64_t R, int32_t D);
+int ogs_knn_aggregate_t(int64_t n, int32_t K, int64_t R, int32_t D, const int32_t* begin, const int32_t* slots, const float* w,
+                        const float* G, float* out, void* tmp, size_t tmp_bytes, void* stream);
+
+/*
+ * Edge dots: gw[i, k] = sum_c G[i, c] * X[idx[i, k], c] on the valid slots, exactly 0 on the others.  G [n, D], X [R, D],
+ * gw [n, K].  Reduction order, a function of D alone: L = the smallest power of two with 8 L >= D, at most 64; lane l of L sums the
+ * columns l, l + L, ... as one chain acc = fmaf(g, x, acc) from +0; the L partials fold pairwise with the lane masks L / 2,
+ * L / 4, ..., 1 (at every step the partial of lane a takes the one of lane a ^ mask).
+ */
+int ogs_knn_edge_dots(int64_t n, int32_t K, int64_t R, int32_t D, const int32_t* idx, const float* G, const float* X, float* gw,
+                      void* stream);
+
+/*
+ * Neighbour smoothness of F [n, D] over a square graph (R = n): E = sum_i sum_k w[i, k] * |F_i - F_idx[i, k]|^2 over the valid
+ * slots, differences first (coincident rows give exactly 0).
+ * fwd: energy [n] fp32, energy[i] = the chain acc = fmaf(w[i, k], d2(i, k), acc) from +0, k ascending over the valid slots, with
+ *      d2 = sum_c (F[i, c] - F[j, c])^2 reduced as the edge dots are (fmaf(d, d, acc) per lane, then the fold); total [2] fp64:
+ *      total[0] = the sum of energy[] (two stages, both in a fixed order), total[1] = the number of valid slots.  No [n, K, D]
+ *      buffer.  tmp: ogs_knn_smoothness_fwd_tmp_bytes(n) bytes.
+ * bwd: gF [n, D] = 2 * scale * (sum_k w[i, k] * (F_i - F_j) + sum over the list of i of w[e] * (F_i - F_{e / K})) with `scale` a
+ *      DEVICE fp32 scalar (the upstream gradient times the normalisation); begin / slots are the reverse lists of idx with R = n.
+ *      Per element: the out-edge chain fmaf(w[i, k], F[i, c] - F[j, c], acc) from +0, k ascending; then the list, continued on
+ *      the same accumulator when it has at most C slots, and otherwise as chunk partials from +0 that are added to it in chunk
+ *      order (the split of ogs_knn_aggregate_t, the same work list); the product with 2 * scale last.  gw [n, K] (may be NULL)
+ *      = scale * d2(i, k) on the valid slots, 0 on the others.  The walk over all rows and chunks is one launch; the partials of
+ *      the split rows are added by a second, small one (no kernel waits on another workgroup), and gw is a launch of its own.
+ *      tmp: ogs_knn_smoothness_bwd_tmp_bytes(n, K, D) bytes.
+ */
+size_t ogs_knn_smoothness_fwd_tmp_bytes(int64_t n);
+int ogs_knn_smoothness_fwd(int64_t n, int32_t K, int32_t D, const int32_t* idx, const float* w, const float* F, float* energy,
+                           double* total, void* tmp, size_t tmp_bytes, void* stream);
+size_t ogs_knn_smoothness_bwd_tmp_bytes(int64_t n, int32_t K, int32_t D);
+int ogs_knn_smoothness_bwd(int64_t n, int32_t K, int32_t D, const int32_t* idx, const float* w, const float* F, const int32_t* begin,
+                           const int32_t* slots, const float* scale, float* gF, float* gw, void* tmp, size_t tmp_bytes,
+                           void* stream);
 
 #ifdef __cplusplus
 }

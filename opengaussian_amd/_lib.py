@@ -196,6 +196,18 @@ SIGNATURES = {
     "ogs_knn_neighbors_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "ogs_knn_neighbors": (C.c_int, [C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
     "ogs_knn_aggregate": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "ogs_knn_transpose_chunk": (C.c_size_t, []),
+    "ogs_knn_transpose_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64]),
+    "ogs_knn_transpose": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ogs_knn_aggregate_t_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
+    "ogs_knn_aggregate_t": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                      _vp]),
+    "ogs_knn_edge_dots": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "ogs_knn_smoothness_fwd_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "ogs_knn_smoothness_fwd": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ogs_knn_smoothness_bwd_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "ogs_knn_smoothness_bwd": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         C.c_size_t, _vp]),
     "ogs_query_max_leaves": (C.c_size_t, []),
     "ogs_query_max_top": (C.c_size_t, []),
     "ogs_query_max_classes": (C.c_size_t, []),
@@ -236,6 +248,10 @@ def lib() -> C.CDLL:
         if not os.path.exists(LIB_PATH):
             raise OgsError(f"{LIB_PATH} not found -- build it with `python -m opengaussian_amd.build` "
                            "(the product path has no CPU fallback)")
+        # torch first: its wheel carries a HIP runtime of its own (soname libamdhip64.so.7, which satisfies this library's
+        # NEEDED entry once it is loaded).  Loaded the other way round the process ends up with TWO runtimes, and the one that
+        # initialises second finds no device -- build() followed by smoke() in one process did that.
+        import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(l, name)
