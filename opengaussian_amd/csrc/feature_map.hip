@@ -5,8 +5,7 @@
 //     out[c, p] = sum over the entries e of p's tile, in depth order, of w_e(p) * X[row(g_e), c]          c < D
 // over the same walk with the same weights: one workgroup per (tile, block of DB = 16 NB columns), wave = 8x8 quadrant, lane =
 // pixel, the quadrant's stream 64 entries at a time with the records and rows parked in LDS and broadcast, T / done / the stop
-// rule per lane -- the walk of feature_votes_kernel, restated with the same arithmetic (blend_power, |power + h| <= h,
-// min(0.99, opacity * __expf(power)), the 1/255 skip, the stop at T * (1 - alpha) < 1e-4, w = alpha * T with T from before the
+// rule per lane -- KeptQuad::walk of kept_walk.h, the walk of feature_votes_kernel (w = alpha * T with T from before the
 // update; this file is compiled with -ffp-contract=off).
 //
 // The fold is transposed too.  Entries that put weight on the quadrant and map to a counted row are staged sixteen at a time:
@@ -27,16 +26,14 @@
 // x of one image row.  Planar [D, H, W]: one 16-byte store per (M-block, column block) where W, H * W and the base allow it, else
 // four 4-byte stores; channels-last [H, W, D]: 64 contiguous bytes per 16 lanes.  Pixels outside the image and columns >= D are
 // not written; inside the image every column is, also by a quadrant without entries (zeros).
-#include "ogs_common.h"
+#include "kept_walk.h"
 #include "../../include/ogs_query.h"
 
 namespace ogs {
 namespace {
 
-constexpr float kAlphaMin = 1.0f / 255.0f;
-constexpr int kWaves = kBlock / kWave;
-constexpr int kFoldRows = 16;                        // entries per batch: K of the fold, four k-steps
-constexpr int kFoldCols = 16;                        // columns per MFMA block: N
+// The transposed fold has no second user and stays here: kFoldRows entries per batch are its K (four k-steps), kFoldCols
+// columns per MFMA block its N.
 // columns a wave accumulates during one walk, 16 accumulator registers per kFoldCols of them.  Wider blocks divide the number of
 // walks and cost registers and LDS, i.e. waves per SIMD: 64 is the widest that keeps four (DESIGN section 6m has the table: it
 // ties with 32 for a single walk, wins from D = 33 on, and 128 loses everywhere).  The -DOGS_EXPERIMENTS builds of
@@ -48,7 +45,6 @@ constexpr int kBlockCols = 64;
 #endif
 static_assert(kBlockCols % 32 == 0 && kBlockCols >= 32, "whole MFMA blocks, and staged feature rows the k groups read without bank conflicts");
 constexpr int kMaxGridY = 65535;
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 // Timing ablations (scripts/feature_map_bench.py: where the time goes), as in feature_votes.hip: the results are WRONG by
 // construction, so the switches exist only in a -DOGS_EXPERIMENTS variant build; the shipped library compiles both to `false`.
 #if defined(OGS_EXPERIMENTS) && defined(OGS_FMAP_WALK_ONLY)
@@ -69,7 +65,7 @@ struct FeatureMapLds {
     static constexpr int kXStride = NB * kFoldCols >= kWave ? NB * kFoldCols : NB * kFoldCols + 16;
     static constexpr int kXSwizzle = NB * kFoldCols >= kWave ? 16 : 0;
 
-    float4 rec[kWaves][kWave * 2];                   // per wave: geometry of the 64 entries of a sub-chunk, the feature row (-1 = not counted) in slot 7
+    float4 rec[kWaves][kWave * 2];                   // per wave: the 64 parked entries of a sub-chunk (KeptQuad::walk)
     float w[kWaves][kFoldRows * kWave];              // per wave: the weights of the staged entries, [entry][pixel ^ 16 (entry & 3)]
     float x[kWaves][kFoldRows * kXStride];           // per wave: the feature rows of the staged entries, [entry][column of the walk]
 };
@@ -84,28 +80,15 @@ __global__ __launch_bounds__(kBlock, NB <= 4 ? 4 : 1) void feature_map_kernel(
     constexpr int kXStride = FeatureMapLds<NB>::kXStride, kXSwizzle = FeatureMapLds<NB>::kXSwizzle;
     constexpr int kGather = (NB * kFoldCols + kWave - 1) / kWave;      // feature values a lane gathers per staged entry
     __shared__ FeatureMapLds<NB> lds;
-    const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;
-    if ((unsigned)tile >= (unsigned)tiles) return;            // block-uniform; an order the pass never wrote addresses nothing
+    KeptQuad q;
+    if (!q.find_tile(tiles, tile_order)) return;              // block-uniform
     const int cbase = (int)blockIdx.y * (NB * kFoldCols);     // first column of this walk
     const int ncols = min(NB * kFoldCols, D - cbase);
     if (ncols <= 0) return;                                   // block-uniform
     const int nblk = (ncols + kFoldCols - 1) / kFoldCols;
-    const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int qx0 = tx * kTile + (wave & 1) * 8, qy0 = ty * kTile + (wave >> 1) * 8;
-    const int px = qx0 + (lane & 7), py = qy0 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float fx = (float)px, fy = (float)py;
+    q.setup(ranges, qcount, stream, RS, quad_list, W, H, gx);
+    const int lane = q.lane, wave = q.wave, qx0 = q.qx0, qy0 = q.qy0;      // q.n <= 0 is no exit: the quadrant owes zeros and alpha
 
-    // both layouts with one formula (label_map_kernel): the tile owns n_tile slots at range.x, of which it packed n_kept
-    const uint2 range = ranges[tile];
-    const int n_tile = (int)(range.y - range.x);
-    const int n = min((int)qcount[tile * 5 + wave], n_tile), n_kept = min((int)qcount[tile * 5 + 4], n_tile);
-    const float* __restrict__ tb = stream + (size_t)range.x * RS;
-    const uint32_t* __restrict__ qi = quad_list + ((size_t)range.x * 5 + (size_t)wave * n_tile);
-    const uint32_t lim = n_kept > 0 ? (uint32_t)n_kept - 1u : 0u;
-
-    float4* __restrict__ recs = lds.rec[wave];
     float* __restrict__ wbuf = lds.w[wave];
     float* __restrict__ xbuf = lds.x[wave];
 
@@ -173,55 +156,21 @@ __global__ __launch_bounds__(kBlock, NB <= 4 ? 4 : 1) void feature_map_kernel(
     };
 
     // ---- the quadrant's stream, 64 entries at a time ------------------------------------------------------------------------------
-    float T = 1.0f, wacc = 0.f;
-    bool done = !inside;
-    for (int c0 = 0; c0 < n && __ballot(!done) != 0ull; c0 += kWave) {
-        const int chunk = min(kWave, n - c0);
-        if (lane < chunk) {
-            const uint32_t ridx = min(qi[c0 + lane], lim);
-            const float4* __restrict__ rp = reinterpret_cast<const float4*>(tb + (size_t)ridx * RS);
-            const float4 g0 = rp[0], g1 = rp[1];
-            const uint32_t id = __float_as_uint(g1.w);
-            int32_t row = -1;
-            if (id < (uint32_t)P) {
-                const int32_t r = rows_of ? rows_of[id] : (int32_t)id;
-                if (r >= 0 && r < R) row = r;                 // outside [0, R): occludes, adds nothing
-            }
-            recs[lane * 2] = g0;
-            recs[lane * 2 + 1] = make_float4(g1.x, g1.y, g1.z, __int_as_float(row));     // the id has served: its slot carries the row
+    float wacc = 0.f;
+    q.walk(lds.rec[wave], TableRow{rows_of, P, R}, [&](int32_t row, float w) {
+        wacc += w;
+        if (row >= 0 && __ballot(w != 0.f) != 0ull && (!kSkipFold || w == -1.f)) {
+            park();                                                          // the previous entry's row: its load has had the walk since
+            wbuf[cnt * kWave + (lane ^ (16 * (cnt & 3)))] = w;
+            gather(row);
+            pend = cnt;
+            if (++cnt == kFoldRows) fold();
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        for (int e = 0; e < chunk && __ballot(!done) != 0ull; ++e) {
-            const float4 g0 = recs[e * 2], g1 = recs[e * 2 + 1];             // x y a2 c2 | b2 h opacity row
-            const float dx = g0.x - fx, dy = g0.y - fy;
-            const float power = blend_power(g0.z, g1.x, g0.w, dx, dy);
-            const bool cand = !done && fabsf(power + g1.y) <= g1.y;
-            if (__ballot(cand) == 0ull) continue;
-            const float araw = fminf(0.99f, g1.z * __expf(power));
-            const bool act = cand && araw >= kAlphaMin;
-            const float alpha = act ? araw : 0.f;
-            const float test_T = T * (1.0f - alpha);
-            const bool stop = test_T < 0.0001f;
-            const float w = stop ? 0.f : alpha * T;
-            T = stop ? T : test_T;
-            done = done || stop;
-            wacc += w;
-            const int32_t row = __builtin_amdgcn_readfirstlane(__float_as_int(g1.w));     // the same word in every lane
-            if (row >= 0 && __ballot(w != 0.f) != 0ull && (!kSkipFold || T == -1.f)) {
-                park();                                                      // the previous entry's row: its load has had the walk since
-                wbuf[cnt * kWave + (lane ^ (16 * (cnt & 3)))] = w;
-                gather(row);
-                pend = cnt;
-                if (++cnt == kFoldRows) fold();
-            }
-        }
-        __builtin_amdgcn_wave_barrier();                                     // the record staging may be rewritten
-    }
+    });
     if (cnt > 0) fold();
 
     // ---- the outputs: every in-image pixel of the quadrant, every column of this walk ------------------------------------------------
-    if (out_alpha && blockIdx.y == 0 && inside) out_alpha[(size_t)py * (size_t)W + (size_t)px] = wacc;
+    if (out_alpha && blockIdx.y == 0 && q.inside) out_alpha[(size_t)q.py * (size_t)W + (size_t)q.px] = wacc;
     const size_t plane = (size_t)H * (size_t)W;
     const int x0 = qx0 + 4 * (kq & 1);                        // the lane's four pixels: x0 .. x0 + 3 of row qy0 + 2 mb + (kq >> 1)
 #pragma unroll
@@ -265,33 +214,22 @@ size_t ogs_feature_map_fold_columns(void) { return (size_t)kFoldCols; }
 size_t ogs_feature_map_block_columns(void) { return (size_t)kBlockCols; }
 
 int ogs_raster_feature_map(const OgsRasterFwdArgs* a, const OgsFeatureMapArgs* fm, void* stream_) {
-    if (!a || !fm) { set_error("feature_map: args == NULL"); return OGS_ERR_INVALID_ARG; }
-    if (a->P <= 0 || a->W <= 0 || a->H <= 0) { set_error("feature_map: bad sizes P=%d W=%d H=%d", a->P, a->W, a->H); return OGS_ERR_INVALID_ARG; }
-    if (a->C != 3 && a->C != 6 && a->C != 9 && a->C != 12) { set_error("C=%d unsupported (3, 6, 9, 12)", a->C); return OGS_ERR_UNSUPPORTED; }
-    if (a->num_groups > 1) { set_error("feature_map: grouped passes are not supported"); return OGS_ERR_UNSUPPORTED; }
+    KeptPass kp;
+    if (const int rc = kept_pass_of("feature_map", a, fm, stream_, &kp)) return rc;
     if (fm->num_channels < 1) { set_error("feature_map: num_channels=%d", fm->num_channels); return OGS_ERR_INVALID_ARG; }
     if (fm->num_rows < 1) { set_error("feature_map: num_rows=%d", fm->num_rows); return OGS_ERR_INVALID_ARG; }
-    if (!a->image_buffer || !a->sorted_rec || !a->quad_list || !fm->features || !fm->out_map) {
-        set_error("feature_map: NULL required pointer (image_buffer, sorted_rec, quad_list, features, out_map)");
-        return OGS_ERR_INVALID_ARG;
-    }
+    if (!kp.pointers || !fm->features || !fm->out_map) return kept_pass_null("feature_map", "features, out_map");
     const int64_t walks = ((int64_t)fm->num_channels + kBlockCols - 1) / kBlockCols;
     if (walks > kMaxGridY) {
         set_error("feature_map: num_channels=%d needs %lld column blocks, the limit is %d", fm->num_channels, (long long)walks, kMaxGridY);
         return OGS_ERR_UNSUPPORTED;
     }
-    const ImageState is = ImageState::carve(a->image_buffer, a->W, a->H, 1);
-    hipStream_t s = static_cast<hipStream_t>(stream_);
-    const int gx = (a->W + kTile - 1) / kTile, gy = (a->H + kTile - 1) / kTile;
-    const int tiles = gx * gy;
-    const uint32_t* order = tile_order_of(is, tiles, a->P);        // heaviest first, as the kept pass ran
     // planar 16-byte stores: every (column, row, x0 = multiple of 4) address is a multiple of 16 bytes
     const int vec_ok = !fm->channels_last && a->W % 4 == 0 && ((int64_t)a->W * a->H) % 4 == 0 && ((uintptr_t)fm->out_map & 15u) == 0;
-    OGS_LAUNCH_NAMED("feature_map_kernel", feature_map_kernel<kBlockCols / kFoldCols>, dim3((unsigned)tiles, (unsigned)walks),
-               dim3(kBlock), 0, s, (const uint2*)is.ranges, (const uint32_t*)is.qcount, (const float*)a->sorted_rec, stream_vec4(a->C) * 4,
-               (const uint32_t*)quad_base(a->quad_list), a->W, a->H, gx, tiles, order, a->P, fm->features, fm->num_channels,
-               fm->rows, fm->num_rows, fm->channels_last ? 1 : 0, vec_ok, fm->out_map, fm->out_alpha);
-    OGS_LAUNCH_CHECK(a->debug, s);
+    OGS_LAUNCH_NAMED("feature_map_kernel", feature_map_kernel<kBlockCols / kFoldCols>, dim3((unsigned)kp.tiles, (unsigned)walks),
+                     dim3(kBlock), 0, kp.s, OGS_KEPT_PASS_ARGS(kp), fm->features, fm->num_channels, fm->rows, fm->num_rows,
+                     fm->channels_last ? 1 : 0, vec_ok, fm->out_map, fm->out_alpha);
+    OGS_LAUNCH_CHECK(a->debug, kp.s);
     return OGS_OK;
 }
 

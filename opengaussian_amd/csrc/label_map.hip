@@ -20,27 +20,21 @@
 // Every lane owns its pixel's column of the table (address row * 256 + pixel: consecutive lanes, consecutive banks), so the update
 // is a plain LDS read-add-write; nothing is an atomic on the outputs and two runs give the same bits.
 //
-// The per-pixel arithmetic restates QuadWalk::consume (blend_fwd.hip) as refine.hip does: blend_power, the candidate window
-// |power + h| <= h, min(0.99, opacity * __expf(power)), the 1/255 skip and the stop at T * (1 - alpha) < 1e-4, in the same
-// operation order; this file is compiled with -ffp-contract=off, so the sums are the plain adds the blend makes.  The 4x4-block
-// sublists of QuadWalk::step are a speed device of the blend (a skipped (entry, block) pair is one every pixel of the block skips
-// anyway) and are not restated: a wave takes its quadrant's stream 64 entries at a time, lane e parks record e and its row in
-// LDS, and the wave walks the 64 entries with the record broadcast from LDS.
-#include "ogs_common.h"
+// The walk itself -- quadrant set-up, the 64-entry staging with the entry's table row in the record's id slot, and the per-pixel
+// chain whose sums are the plain adds the blend makes -- is KeptQuad of kept_walk.h; this file is compiled with
+// -ffp-contract=off.
+#include "kept_walk.h"
 #include "../../include/ogs_query.h"
 
 namespace ogs {
 namespace {
 
-constexpr float kAlphaMin = 1.0f / 255.0f;
 constexpr int kLabelCap = 64;                        // rows of the dense table: 64 x 256 x 4 B = 64 KiB, two workgroups per CU
 constexpr int kWindowBits = 32 * kBlock;             // label values per window: one bitmap word per thread
-constexpr int kWaves = kBlock / kWave;
 
 struct LabelLds {
     float table[kLabelCap * kBlock];                 // [row][pixel]
-    float4 rec[kWaves][kWave * 2];                   // per wave: geometry of the 64 entries of a sub-chunk
-    int32_t row[kWaves][kWave];                      // per wave: table row of each of them, -1 = none
+    float4 rec[kWaves][kWave * 2];                   // per wave: the 64 parked entries of a sub-chunk (KeptQuad::walk)
     uint32_t bits[kBlock];                           // labels of the window present in the tile
     uint32_t prefix[kBlock];                         // set bits in front of each word
     int32_t row_label[kLabelCap];                    // global label of each row of the current sub-pass
@@ -54,22 +48,11 @@ __global__ __launch_bounds__(kBlock) void label_map_kernel(
     const int32_t* __restrict__ labels, int L, int32_t* __restrict__ out_label, float* __restrict__ out_weight,
     float* __restrict__ out_second, float* __restrict__ out_alpha) {
     __shared__ LabelLds lds;
-    const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;
-    if ((unsigned)tile >= (unsigned)tiles) return;            // block-uniform; an order the pass never wrote addresses nothing
-    const int tx = tile % gx, ty = tile / gx;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int px = tx * kTile + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * kTile + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float fx = (float)px, fy = (float)py;
-
-    // both layouts with one formula (blend_forward_rows_kernel): the tile owns n_tile slots at range.x, of which it packed n_kept
-    const uint2 range = ranges[tile];
-    const int n_tile = (int)(range.y - range.x);
-    const int n = min((int)qcount[tile * 5 + wave], n_tile), n_kept = min((int)qcount[tile * 5 + 4], n_tile);
-    const float* __restrict__ tb = stream + (size_t)range.x * RS;
-    const uint32_t* __restrict__ qi = quad_list + ((size_t)range.x * 5 + (size_t)wave * n_tile);
-    const uint32_t lim = n_kept > 0 ? (uint32_t)n_kept - 1u : 0u;
+    KeptQuad q;
+    if (!q.find_tile(tiles, tile_order)) return;              // block-uniform
+    q.setup(ranges, qcount, stream, RS, quad_list, W, H, gx);
+    const int tid = threadIdx.x, lane = q.lane, wave = q.wave, n_kept = q.n_kept;
+    const float* __restrict__ tb = q.tb;
 
     auto label_of = [&](float id_bits) -> int32_t {
         const uint32_t id = __float_as_uint(id_bits);
@@ -129,8 +112,6 @@ __global__ __launch_bounds__(kBlock) void label_map_kernel(
     float best = 0.f, second = 0.f, wacc = 0.f;
     int32_t best_label = -1;
     float* __restrict__ col = lds.table + tid;                // this pixel's column
-    float4* __restrict__ recs = lds.rec[wave];
-    int32_t* __restrict__ rows = lds.row[wave];
 
     for (;;) {                                                // windows (block-uniform: K and next come from LDS)
         const int subs = max(1, (K + kLabelCap - 1) / kLabelCap);      // a tile without labels still owes its alpha: one walk
@@ -151,49 +132,21 @@ __global__ __launch_bounds__(kBlock) void label_map_kernel(
             __syncthreads();
 
             // ---- phase B: the quadrant's stream, 64 entries at a time ------------------------------------------------------------
-            float T = 1.0f;
-            bool done = !inside;
             wacc = 0.f;
-            for (int c0 = 0; c0 < n && __ballot(!done) != 0ull; c0 += kWave) {
-                const int cnt = min(kWave, n - c0);
-                if (lane < cnt) {
-                    const uint32_t ridx = min(qi[c0 + lane], lim);
-                    const float4* __restrict__ rp = reinterpret_cast<const float4*>(tb + (size_t)ridx * RS);
-                    const float4 g0 = rp[0], g1 = rp[1];
-                    int32_t row = -1;
-                    const int32_t l = label_of(g1.w);
-                    if (l >= 0 && (int64_t)l >= lo && (int64_t)l < lo + kWindowBits) {
-                        const uint32_t rel = (uint32_t)((int64_t)l - lo);
-                        const uint32_t word = lds.bits[rel >> 5], bit = 1u << (rel & 31u);
-                        const int rank = (int)lds.prefix[rel >> 5] + __popc(word & (bit - 1u)) - r0;
-                        if ((word & bit) != 0u && rank >= 0 && rank < nrows) row = rank;
-                    }
-                    recs[lane * 2] = g0;
-                    recs[lane * 2 + 1] = g1;
-                    rows[lane] = row;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                for (int e = 0; e < cnt && __ballot(!done) != 0ull; ++e) {
-                    const float4 g0 = recs[e * 2], g1 = recs[e * 2 + 1];         // x y a2 c2 | b2 h opacity id
-                    const float dx = g0.x - fx, dy = g0.y - fy;
-                    const float power = blend_power(g0.z, g1.x, g0.w, dx, dy);
-                    const bool cand = !done && fabsf(power + g1.y) <= g1.y;
-                    if (__ballot(cand) == 0ull) continue;
-                    const float araw = fminf(0.99f, g1.z * __expf(power));
-                    const bool act = cand && araw >= kAlphaMin;
-                    const float alpha = act ? araw : 0.f;
-                    const float test_T = T * (1.0f - alpha);
-                    const bool stop = test_T < 0.0001f;
-                    const float w = stop ? 0.f : alpha * T;
-                    T = stop ? T : test_T;
-                    done = done || stop;
+            q.walk(
+                lds.rec[wave],
+                [&](float id_bits) -> int32_t {               // the label's rank in the window, where this sub-pass holds it
+                    const int32_t l = label_of(id_bits);
+                    if (l < 0 || (int64_t)l < lo || (int64_t)l >= lo + kWindowBits) return -1;
+                    const uint32_t rel = (uint32_t)((int64_t)l - lo);
+                    const uint32_t word = lds.bits[rel >> 5], bit = 1u << (rel & 31u);
+                    const int rank = (int)lds.prefix[rel >> 5] + __popc(word & (bit - 1u)) - r0;
+                    return ((word & bit) != 0u && rank >= 0 && rank < nrows) ? rank : -1;
+                },
+                [&](int32_t row, float w) {
                     wacc += w;
-                    const int32_t row = rows[e];
-                    if (row >= 0) col[row * kBlock] += w;                       // wave-uniform row, the lane's own slot
-                }
-                __builtin_amdgcn_wave_barrier();                                 // the staging may be rewritten
-            }
+                    if (row >= 0) col[row * kBlock] += w;     // wave-uniform row, the lane's own slot
+                });
 
             // ---- the rows of this sub-pass, ascending in the label ---------------------------------------------------------------
             for (int r = 0; r < nrows; ++r) {
@@ -212,8 +165,8 @@ __global__ __launch_bounds__(kBlock) void label_map_kernel(
         K = scan_window(lo, next);
     }
 
-    if (inside) {
-        const size_t pix = (size_t)py * W + px;
+    if (q.inside) {
+        const size_t pix = (size_t)q.py * W + q.px;
         out_label[pix] = best_label;
         out_weight[pix] = best;
         out_second[pix] = second;
@@ -231,25 +184,14 @@ extern "C" {
 size_t ogs_label_map_tile_capacity(void) { return (size_t)kLabelCap; }
 
 int ogs_raster_label_map(const OgsRasterFwdArgs* a, const OgsLabelMapArgs* lm, void* stream_) {
-    if (!a || !lm) { set_error("label_map: args == NULL"); return OGS_ERR_INVALID_ARG; }
-    if (a->P <= 0 || a->W <= 0 || a->H <= 0) { set_error("label_map: bad sizes P=%d W=%d H=%d", a->P, a->W, a->H); return OGS_ERR_INVALID_ARG; }
-    if (a->C != 3 && a->C != 6 && a->C != 9 && a->C != 12) { set_error("C=%d unsupported (3, 6, 9, 12)", a->C); return OGS_ERR_UNSUPPORTED; }
-    if (a->num_groups > 1) { set_error("label_map: grouped passes are not supported"); return OGS_ERR_UNSUPPORTED; }
+    KeptPass kp;
+    if (const int rc = kept_pass_of("label_map", a, lm, stream_, &kp)) return rc;
     if (lm->num_labels < 0) { set_error("label_map: num_labels=%d", lm->num_labels); return OGS_ERR_INVALID_ARG; }
-    if (!a->image_buffer || !a->sorted_rec || !a->quad_list || !lm->labels || !lm->out_label || !lm->out_weight || !lm->out_second ||
-        !lm->out_alpha) {
-        set_error("label_map: NULL required pointer (image_buffer, sorted_rec, quad_list, labels, out_*)");
-        return OGS_ERR_INVALID_ARG;
-    }
-    const ImageState is = ImageState::carve(a->image_buffer, a->W, a->H, 1);
-    hipStream_t s = static_cast<hipStream_t>(stream_);
-    const int gx = (a->W + kTile - 1) / kTile, gy = (a->H + kTile - 1) / kTile;
-    const int tiles = gx * gy;
-    const uint32_t* order = tile_order_of(is, tiles, a->P);        // heaviest first, as the kept pass ran
-    OGS_LAUNCH(label_map_kernel, dim3((unsigned)tiles), dim3(kBlock), 0, s, (const uint2*)is.ranges, (const uint32_t*)is.qcount,
-               (const float*)a->sorted_rec, stream_vec4(a->C) * 4, (const uint32_t*)quad_base(a->quad_list), a->W, a->H, gx, tiles,
-               order, a->P, lm->labels, lm->num_labels, lm->out_label, lm->out_weight, lm->out_second, lm->out_alpha);
-    OGS_LAUNCH_CHECK(a->debug, s);
+    if (!kp.pointers || !lm->labels || !lm->out_label || !lm->out_weight || !lm->out_second || !lm->out_alpha)
+        return kept_pass_null("label_map", "labels, out_*");
+    OGS_LAUNCH(label_map_kernel, dim3((unsigned)kp.tiles), dim3(kBlock), 0, kp.s, OGS_KEPT_PASS_ARGS(kp), lm->labels, lm->num_labels,
+               lm->out_label, lm->out_weight, lm->out_second, lm->out_alpha);
+    OGS_LAUNCH_CHECK(a->debug, kp.s);
     return OGS_OK;
 }
 

@@ -738,15 +738,72 @@ class _ReblendKept(torch.autograd.Function):
         return g_col, None, None
 
 
-def _kept_state(kept):
+def _kept_state(kept, who):
     """(P, W, H, Cn, image, sorted_rec, quad_list) of what a pass left in its keep_sink (a dict) or of a KeptPasses entry."""
     if isinstance(kept, _KeptPass):
         return kept.P, kept.W, kept.H, kept.Cn, kept.image, kept.sorted_rec, kept.quad_list
     if isinstance(kept, dict) and all(k in kept for k in ("P", "W", "H", "Cn", "image", "sorted_rec", "quad_list")):
         return (int(kept["P"]), int(kept["W"]), int(kept["H"]), int(kept["Cn"]), kept["image"], kept["sorted_rec"],
                 kept["quad_list"])
-    raise RuntimeError("label_map needs the state of an ungrouped streaming pass: the dict a pass leaves in keep_sink or a "
+    raise RuntimeError(f"{who} needs the state of an ungrouped streaming pass: the dict a pass leaves in keep_sink or a "
                        "KeptPasses entry (grouped and tiny passes keep none)")
+
+
+def _kept_args(state):
+    """the OgsRasterFwdArgs every call over a kept pass gives: sizes and the three kept buffers of a `_kept_state`"""
+    P, W, H, Cn, image, sorted_rec, quad_list = state
+    a = OgsRasterFwdArgs()
+    a.P, a.W, a.H, a.C = P, W, H, Cn
+    a.image_buffer, a.sorted_rec, a.quad_list = ptr(image), ptr(sorted_rec), ptr(quad_list)
+    return a
+
+
+def _int32_or_outside(t, upper, dev):
+    """an integer tensor as contiguous int32 on `dev`; a value outside [0, upper) becomes -1 BEFORE the narrowing, so a 64-bit
+    value outside the int32 range stays outside instead of wrapping into range"""
+    t = t.detach().to(device=dev)
+    if t.dtype is not torch.int32:
+        t = torch.where((t >= 0) & (t < upper), t, torch.full_like(t, -1)).to(torch.int32)
+    return t.contiguous()
+
+
+def _check_rows(rows, P):
+    if rows is None:
+        return
+    if not torch.is_tensor(rows) or rows.is_floating_point() or rows.is_complex() or rows.dtype is torch.bool:
+        raise RuntimeError("rows must be an integer tensor")
+    if rows.numel() != P:
+        raise RuntimeError(f"the pass holds {P} Gaussians, rows has {rows.numel()} entries")
+
+
+def _votes_rows(rows, num_rows, P):
+    """the row count of a vote table: num_rows (required with `rows`), else one row per Gaussian"""
+    _check_rows(rows, P)
+    if rows is not None and num_rows is None:
+        raise RuntimeError("num_rows must be given with rows")
+    Rn = P if num_rows is None else int(num_rows)
+    if Rn < 1 or Rn > 2 ** 31 - 1:
+        raise RuntimeError(f"num_rows must be in [1, 2^31), got {num_rows}")
+    return Rn
+
+
+def _rows_int32(rows, Rn, dev):
+    return None if rows is None else _int32_or_outside(rows.reshape(-1), Rn, dev)
+
+
+def _check_votes_out(out, Rn, cols):
+    if out is not None and (not torch.is_tensor(out) or out.dtype is not torch.int64 or tuple(out.shape) != (Rn, cols)
+                            or not out.is_contiguous()):
+        raise RuntimeError(f"out must be a contiguous int64 tensor [{Rn}, {cols}]")
+
+
+def _require_gpu_all(state, **tensors):
+    """the named arguments that were given, then the kept pass itself, in that order; returns the pass's device"""
+    for name, t in tensors.items():
+        if t is not None:
+            _require_gpu(t, name)
+    _require_gpu(state[4], "the kept pass")
+    return state[4].device
 
 
 def label_map(kept, labels, num_labels):
@@ -758,7 +815,8 @@ def label_map(kept, labels, num_labels):
     Returns ``(label [H,W] int32, weight [H,W], second [H,W], alpha [H,W])``: the label with the largest summed blend weight
     (lowest label on an exact tie, -1 where no labelled Gaussian contributed), that weight, the runner-up label's weight, and
     the pass's own alpha image bit for bit.  Forward only; two calls give the same bytes."""
-    P, W, H, Cn, image, sorted_rec, quad_list = _kept_state(kept)
+    state = _kept_state(kept, "label_map")
+    P, W, H = state[:3]
     if not torch.is_tensor(labels):
         raise RuntimeError("labels must be a tensor")
     if labels.is_floating_point() or labels.is_complex() or labels.dtype is torch.bool:
@@ -768,35 +826,17 @@ def label_map(kept, labels, num_labels):
     L = int(num_labels)
     if L < 0 or L > 2 ** 31 - 1:
         raise RuntimeError(f"num_labels must be in [0, 2^31), got {num_labels}")
-    _require_gpu(labels, "labels")
-    _require_gpu(image, "the kept pass")
-    dev = image.device
-    lab = labels.detach().reshape(-1).to(device=dev)
-    if lab.dtype is not torch.int32:
-        # a 64-bit value outside the int32 range is outside [0, L) too: it stays unlabelled instead of wrapping into range
-        lab = torch.where((lab >= 0) & (lab < L), lab, torch.full_like(lab, -1)).to(torch.int32)
-    lab = lab.contiguous()
+    dev = _require_gpu_all(state, labels=labels)
+    lab = _int32_or_outside(labels.reshape(-1), L, dev)
     out_label = torch.empty(H, W, dtype=torch.int32, device=dev)
     weight = torch.empty(H, W, dtype=torch.float32, device=dev)
     second = torch.empty(H, W, dtype=torch.float32, device=dev)
     alpha = torch.empty(H, W, dtype=torch.float32, device=dev)
-    a = OgsRasterFwdArgs()
-    a.P, a.W, a.H, a.C = P, W, H, Cn
-    a.image_buffer, a.sorted_rec, a.quad_list = ptr(image), ptr(sorted_rec), ptr(quad_list)
     lm = _lib.OgsLabelMapArgs()
     lm.labels, lm.num_labels = ptr(lab), L
     lm.out_label, lm.out_weight, lm.out_second, lm.out_alpha = ptr(out_label), ptr(weight), ptr(second), ptr(alpha)
-    check(_lib.lib().ogs_raster_label_map(C.byref(a), C.byref(lm), _stream()), "ogs_raster_label_map")
+    check(_lib.lib().ogs_raster_label_map(C.byref(_kept_args(state)), C.byref(lm), _stream()), "ogs_raster_label_map")
     return out_label, weight, second, alpha
-
-
-def _int32_or_outside(t, upper, dev):
-    """an integer tensor as contiguous int32 on `dev`; a value outside [0, upper) becomes -1 BEFORE the narrowing, so a 64-bit
-    value outside the int32 range stays outside instead of wrapping into range"""
-    t = t.detach().to(device=dev)
-    if t.dtype is not torch.int32:
-        t = torch.where((t >= 0) & (t < upper), t, torch.full_like(t, -1)).to(torch.int32)
-    return t.contiguous()
 
 
 def label_votes(kept, pixel_labels, num_labels, rows=None, num_rows=None, out=None):
@@ -810,7 +850,8 @@ def label_votes(kept, pixel_labels, num_labels, rows=None, num_rows=None, out=No
     cell [r, l] = summed blend weight alpha * T that the Gaussians of row r put on the pixels of label l.  ``out`` (same shape,
     int64, on the GPU) is ACCUMULATED into and returned, so several views sum into one table; without it a zeroed table is made.
     Forward only; integer accumulation: two calls give the same bytes."""
-    P, W, H, Cn, image, sorted_rec, quad_list = _kept_state(kept)
+    state = _kept_state(kept, "label_votes")
+    P, W, H = state[:3]
     if not torch.is_tensor(pixel_labels):
         raise RuntimeError("pixel_labels must be a tensor")
     if pixel_labels.is_floating_point() or pixel_labels.is_complex() or pixel_labels.dtype is torch.bool:
@@ -820,37 +861,17 @@ def label_votes(kept, pixel_labels, num_labels, rows=None, num_rows=None, out=No
     L = int(num_labels)
     if L < 0 or L > 2 ** 31 - 2:
         raise RuntimeError(f"num_labels must be in [0, 2^31 - 1), got {num_labels}")
-    if rows is not None:
-        if not torch.is_tensor(rows) or rows.is_floating_point() or rows.is_complex() or rows.dtype is torch.bool:
-            raise RuntimeError("rows must be an integer tensor")
-        if rows.numel() != P:
-            raise RuntimeError(f"the pass holds {P} Gaussians, rows has {rows.numel()} entries")
-        if num_rows is None:
-            raise RuntimeError("num_rows must be given with rows")
-    Rn = P if num_rows is None else int(num_rows)
-    if Rn < 1 or Rn > 2 ** 31 - 1:
-        raise RuntimeError(f"num_rows must be in [1, 2^31), got {num_rows}")
-    if out is not None and (not torch.is_tensor(out) or out.dtype is not torch.int64 or tuple(out.shape) != (Rn, L + 1)
-                            or not out.is_contiguous()):
-        raise RuntimeError(f"out must be a contiguous int64 tensor [{Rn}, {L + 1}]")
-    _require_gpu(pixel_labels, "pixel_labels")
-    if rows is not None:
-        _require_gpu(rows, "rows")
-    if out is not None:
-        _require_gpu(out, "out")
-    _require_gpu(image, "the kept pass")
-    dev = image.device
+    Rn = _votes_rows(rows, num_rows, P)
+    _check_votes_out(out, Rn, L + 1)
+    dev = _require_gpu_all(state, pixel_labels=pixel_labels, rows=rows, out=out)
     lab = _int32_or_outside(pixel_labels, L, dev)
-    row = None if rows is None else _int32_or_outside(rows.reshape(-1), Rn, dev)
+    row = _rows_int32(rows, Rn, dev)
     votes = torch.zeros(Rn, L + 1, dtype=torch.int64, device=dev) if out is None else out
-    a = OgsRasterFwdArgs()
-    a.P, a.W, a.H, a.C = P, W, H, Cn
-    a.image_buffer, a.sorted_rec, a.quad_list = ptr(image), ptr(sorted_rec), ptr(quad_list)
     lv = _lib.OgsLabelVotesArgs()
     lv.pixel_labels, lv.num_labels = ptr(lab), L
-    lv.rows, lv.num_rows = (None if row is None else ptr(row)), Rn
+    lv.rows, lv.num_rows = ptr(row), Rn
     lv.votes = ptr(votes)
-    check(_lib.lib().ogs_raster_label_votes(C.byref(a), C.byref(lv), _stream()), "ogs_raster_label_votes")
+    check(_lib.lib().ogs_raster_label_votes(C.byref(_kept_args(state)), C.byref(lv), _stream()), "ogs_raster_label_votes")
     return votes
 
 
@@ -876,7 +897,8 @@ def feature_votes(kept, features, valid=None, rows=None, num_rows=None, out=None
     gradient it is 1.6-1.9 x faster at D = 64 and 512; at D <= 16 (one or two such launches) the two routes cost the same
     within the spread of the measurement, and with ``rows`` at D = 16 the backward route was 2 % ahead.
     That route is not reproducible to the byte, has no ``valid`` / ``rows`` and needs a [P, D + 1] fp32 table."""
-    P, W, H, Cn, image, sorted_rec, quad_list = _kept_state(kept)
+    state = _kept_state(kept, "feature_votes")
+    P, W, H = state[:3]
     if not torch.is_tensor(features):
         raise RuntimeError("features must be a tensor")
     if not features.is_floating_point():
@@ -891,41 +913,19 @@ def feature_votes(kept, features, valid=None, rows=None, num_rows=None, out=None
             raise RuntimeError("valid must be a bool or integer tensor")
         if tuple(valid.shape) != (H, W):
             raise RuntimeError(f"the pass is {H} x {W} pixels, valid is {tuple(valid.shape)}")
-    if rows is not None:
-        if not torch.is_tensor(rows) or rows.is_floating_point() or rows.is_complex() or rows.dtype is torch.bool:
-            raise RuntimeError("rows must be an integer tensor")
-        if rows.numel() != P:
-            raise RuntimeError(f"the pass holds {P} Gaussians, rows has {rows.numel()} entries")
-        if num_rows is None:
-            raise RuntimeError("num_rows must be given with rows")
-    Rn = P if num_rows is None else int(num_rows)
-    if Rn < 1 or Rn > 2 ** 31 - 1:
-        raise RuntimeError(f"num_rows must be in [1, 2^31), got {num_rows}")
-    if out is not None and (not torch.is_tensor(out) or out.dtype is not torch.int64 or tuple(out.shape) != (Rn, D + 1)
-                            or not out.is_contiguous()):
-        raise RuntimeError(f"out must be a contiguous int64 tensor [{Rn}, {D + 1}]")
-    _require_gpu(features, "features")
-    if valid is not None:
-        _require_gpu(valid, "valid")
-    if rows is not None:
-        _require_gpu(rows, "rows")
-    if out is not None:
-        _require_gpu(out, "out")
-    _require_gpu(image, "the kept pass")
-    dev = image.device
+    Rn = _votes_rows(rows, num_rows, P)
+    _check_votes_out(out, Rn, D + 1)
+    dev = _require_gpu_all(state, features=features, valid=valid, rows=rows, out=out)
     feat = features.detach().to(device=dev, dtype=torch.float32).contiguous()
     ok = None if valid is None else (valid.detach().to(device=dev) != 0).to(torch.uint8).contiguous()
-    row = None if rows is None else _int32_or_outside(rows.reshape(-1), Rn, dev)
+    row = _rows_int32(rows, Rn, dev)
     votes = torch.zeros(Rn, D + 1, dtype=torch.int64, device=dev) if out is None else out
-    a = OgsRasterFwdArgs()
-    a.P, a.W, a.H, a.C = P, W, H, Cn
-    a.image_buffer, a.sorted_rec, a.quad_list = ptr(image), ptr(sorted_rec), ptr(quad_list)
     fv = _lib.OgsFeatureVotesArgs()
     fv.features, fv.num_channels = ptr(feat), D
-    fv.valid = None if ok is None else ptr(ok)
-    fv.rows, fv.num_rows = (None if row is None else ptr(row)), Rn
+    fv.valid = ptr(ok)
+    fv.rows, fv.num_rows = ptr(row), Rn
     fv.votes = ptr(votes)
-    check(_lib.lib().ogs_raster_feature_votes(C.byref(a), C.byref(fv), _stream()), "ogs_raster_feature_votes")
+    check(_lib.lib().ogs_raster_feature_votes(C.byref(_kept_args(state)), C.byref(fv), _stream()), "ogs_raster_feature_votes")
     return votes
 
 
@@ -947,7 +947,8 @@ def feature_map(kept, features, rows=None, channels_last=False, with_alpha=False
     written once.  Against the re-blend route it is 2.1-2.4 x faster at D = 64 and 512 and needs neither a [P, D] copy of a
     per-leaf table nor a 12-channel kept pass; at D = 16 the two routes cost the same, and a map of up to 12 channels is ONE
     re-blend of a kept pass, which is the better call there (0.21 against 0.37 ms on the bench scene)."""
-    P, W, H, Cn, image, sorted_rec, quad_list = _kept_state(kept)
+    state = _kept_state(kept, "feature_map")
+    P, W, H = state[:3]
     if not torch.is_tensor(features):
         raise RuntimeError("features must be a tensor")
     if not features.is_floating_point():
@@ -957,31 +958,20 @@ def feature_map(kept, features, rows=None, channels_last=False, with_alpha=False
     Rn, D = int(features.shape[0]), int(features.shape[1])
     if Rn > 2 ** 31 - 1 or D > 2 ** 31 - 1:
         raise RuntimeError(f"features is {Rn} x {D}, the limit is 2^31 - 1 each way")
-    if rows is not None:
-        if not torch.is_tensor(rows) or rows.is_floating_point() or rows.is_complex() or rows.dtype is torch.bool:
-            raise RuntimeError("rows must be an integer tensor")
-        if rows.numel() != P:
-            raise RuntimeError(f"the pass holds {P} Gaussians, rows has {rows.numel()} entries")
-    elif Rn != P:
+    _check_rows(rows, P)
+    if rows is None and Rn != P:
         raise RuntimeError(f"the pass holds {P} Gaussians, features has {Rn} rows (give rows to map Gaussians to rows)")
-    _require_gpu(features, "features")
-    if rows is not None:
-        _require_gpu(rows, "rows")
-    _require_gpu(image, "the kept pass")
-    dev = image.device
+    dev = _require_gpu_all(state, features=features, rows=rows)
     feat = features.detach().to(device=dev, dtype=torch.float32).contiguous()
-    row = None if rows is None else _int32_or_outside(rows.reshape(-1), Rn, dev)
+    row = _rows_int32(rows, Rn, dev)
     out = torch.empty((H, W, D) if channels_last else (D, H, W), dtype=torch.float32, device=dev)
     alpha = torch.empty(H, W, dtype=torch.float32, device=dev) if with_alpha else None
-    a = OgsRasterFwdArgs()
-    a.P, a.W, a.H, a.C = P, W, H, Cn
-    a.image_buffer, a.sorted_rec, a.quad_list = ptr(image), ptr(sorted_rec), ptr(quad_list)
     fm = _lib.OgsFeatureMapArgs()
     fm.features, fm.num_channels = ptr(feat), D
-    fm.rows, fm.num_rows = (None if row is None else ptr(row)), Rn
+    fm.rows, fm.num_rows = ptr(row), Rn
     fm.channels_last = int(bool(channels_last))
     fm.out_map, fm.out_alpha = ptr(out), ptr(alpha)
-    check(_lib.lib().ogs_raster_feature_map(C.byref(a), C.byref(fm), _stream()), "ogs_raster_feature_map")
+    check(_lib.lib().ogs_raster_feature_map(C.byref(_kept_args(state)), C.byref(fm), _stream()), "ogs_raster_feature_map")
     return (out, alpha) if with_alpha else out
 
 
