@@ -64,6 +64,52 @@ int ogs_kmeans_assign(const float* feat, int64_t N, int32_t d, const float* cent
 int ogs_kmeans_gather(const float* centers, const int64_t* ids, int64_t N, int32_t vec_dim, int32_t out_dim,
                       float* out, void* stream);
 
+/*
+ * ---- wide k-means (csrc/kmeans_wide.hip) -------------------------------------------------------------------------------------------
+ * Codebooks for lifted per-Gaussian feature vectors: rows X [N, D], centres C [k, D], 1 <= D <= ogs_kmeans_wide_max_dim(),
+ * 1 <= k <= ogs_kmeans_wide_max_k(), N < 2^31 (N = 0: nothing is read or launched; an update then keeps every centre).
+ * Device pointers, contiguous fp32, any D and any 4-byte alignment of X, C and the outputs; tmp: 16-byte aligned device
+ * scratch of ogs_kmeans_wide_tmp_bytes(N, D, k) bytes, nothing in it survives a call.  Bad sizes, an unknown metric, NULL where
+ * not allowed or a tmp that is too small return OGS_ERR_INVALID_ARG.  No float atomics anywhere: two identical calls give the
+ * same bytes.  Nothing is read back; everything runs on `stream`.
+ *
+ * assign   ids[i] = arg-max over c of  x_i . c + b_c,   b_c = -|c|^2 / 2 (L2: the nearest centre) or 0 (COSINE: C must hold
+ *          unit rows; the row's own norm does not change the arg-max).  The products run on the matrix pipe as three-term bf16
+ *          splits that carry both operands' 24-bit significands (six partial products per term, fp32 accumulate); for L2 both
+ *          sides are first shifted by the centroid of a fixed sample of the rows.  A score is within (8 D + 64) 2^-24 of
+ *          max_c (sum_j |x'_j| |c'_j| + |c'|^2 / 2) of its exact value (x', c': the shifted operands), so ids equal the exact
+ *          arg-max except on near-ties of that size; exact ties go to the LOWEST centre index.  ids [N] int32.
+ *          dist [N] (may be NULL) is recomputed for the winner from the inputs: L2 the fp32 sum of (x_j - c_j)^2, differences
+ *          first; COSINE 1 - x . c / |x|, and 1 for a zero row.  No [N, k] buffer exists.
+ * update   centre c = sum over its rows of w_i x_i / sum w_i (COSINE: then normalised), each sum in the fixed order of
+ *          ogs_knn_aggregate_t over the centre's ascending row list (include/ogs_knn.h); w [N] >= 0 may be NULL (= 1).  A centre
+ *          whose weights sum to 0 (COSINE: or whose sum has zero norm) keeps its previous value bit for bit.  counts [k] (may be
+ *          NULL) = sum w_i.  C is read (previous) and written (new).
+ * inertia  total[0] = sum_i w_i dist_i in fp64, two stages in an order that depends on N alone.
+ * lloyd    iters x (assign, inertia, update), then the final assign and its inertia: inertia [iters + 1] (may be NULL),
+ *          inertia[t] belongs to the assignment of iteration t; dist may be NULL; counts is what the last update wrote (not
+ *          written when iters = 0).  Exactly the bytes of the same sequence made from the three calls above.
+ * The sizes that shape the kernel: a workgroup scores ogs_kmeans_wide_row_tile() rows (64; 48 for D > 384, 32 for D > 512, 16 for
+ * D > 768: what fits in LDS) against tiles of ogs_kmeans_wide_centre_tile() centres in steps of ogs_kmeans_wide_dim_step() dimensions, and
+ * centres are packed ogs_kmeans_wide_stage() at a time.
+ */
+#define OGS_KMEANS_WIDE_L2 0
+#define OGS_KMEANS_WIDE_COSINE 1
+size_t ogs_kmeans_wide_row_tile(void);
+size_t ogs_kmeans_wide_centre_tile(void);
+size_t ogs_kmeans_wide_dim_step(void);
+size_t ogs_kmeans_wide_stage(void);
+size_t ogs_kmeans_wide_max_dim(void);
+size_t ogs_kmeans_wide_max_k(void);
+size_t ogs_kmeans_wide_tmp_bytes(int64_t N, int32_t D, int32_t k);      /* 0 for sizes outside the limits */
+int ogs_kmeans_wide_assign(const float* X, int64_t N, int32_t D, const float* C, int32_t k, int32_t metric, int32_t* ids, float* dist,
+                           void* tmp, size_t tmp_bytes, void* stream);
+int ogs_kmeans_wide_update(const float* X, const float* w, int64_t N, int32_t D, const int32_t* ids, int32_t k, int32_t metric, float* C,
+                           float* counts, void* tmp, size_t tmp_bytes, void* stream);
+int ogs_kmeans_wide_inertia(const float* dist, const float* w, int64_t N, double* total, void* tmp, size_t tmp_bytes, void* stream);
+int ogs_kmeans_wide_lloyd(const float* X, const float* w, int64_t N, int32_t D, float* C, int32_t k, int32_t metric, int32_t iters,
+                          int32_t* ids, float* dist, float* counts, double* inertia, void* tmp, size_t tmp_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

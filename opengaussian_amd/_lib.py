@@ -208,6 +208,19 @@ SIGNATURES = {
     "ogs_knn_smoothness_bwd_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "ogs_knn_smoothness_bwd": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          C.c_size_t, _vp]),
+    "ogs_kmeans_wide_row_tile": (C.c_size_t, []),
+    "ogs_kmeans_wide_centre_tile": (C.c_size_t, []),
+    "ogs_kmeans_wide_dim_step": (C.c_size_t, []),
+    "ogs_kmeans_wide_stage": (C.c_size_t, []),
+    "ogs_kmeans_wide_max_dim": (C.c_size_t, []),
+    "ogs_kmeans_wide_max_k": (C.c_size_t, []),
+    "ogs_kmeans_wide_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "ogs_kmeans_wide_assign": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ogs_kmeans_wide_update": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t,
+                                         _vp]),
+    "ogs_kmeans_wide_inertia": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
+    "ogs_kmeans_wide_lloyd": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp,
+                                        _vp, C.c_size_t, _vp]),
     "ogs_query_max_leaves": (C.c_size_t, []),
     "ogs_query_max_top": (C.c_size_t, []),
     "ogs_query_max_classes": (C.c_size_t, []),

@@ -25,6 +25,8 @@ EXTRA = {
     "preprocess_fwd.hip": ["-ffp-contract=off"],
     # k-means argmin: same sum-of-squares operation order as oracle/kmeans_oracle.py (HBM-bound, FMA buys nothing)
     "kmeans.hip": ["-ffp-contract=off"],
+    # wide k-means: every fmaf of the bias, distance and norm chains is written out; the scores themselves are MFMA sums
+    "kmeans_wide.hip": ["-ffp-contract=off"],
     "adam.hip": ["-ffp-contract=off"],
     # footprint alpha and the uint8 pixel made of it: the bits of a P = 1 pass through the blend kernels
     "refine.hip": ["-ffp-contract=off"],

@@ -88,6 +88,98 @@ def assign(feat: torch.Tensor, centers: torch.Tensor, id_offset: int = 0) -> tor
     return ids
 
 
+# ---- wide k-means: codebooks for lifted feature vectors (include/ogs_kmeans.h, the ogs_kmeans_wide_* block) ---------------------
+WIDE_METRICS = {"l2": 0, "cosine": 1}
+
+
+def _wide_check(feat, centers, metric, weights=None, ids=None):
+    """Shapes, metric and limits, before anything touches the GPU; returns (N, D, k, metric code)."""
+    if metric not in WIDE_METRICS:
+        raise ValueError(f"metric must be one of {sorted(WIDE_METRICS)}, got {metric!r}")
+    if feat.dim() != 2 or centers.dim() != 2:
+        raise ValueError(f"feat must be [N, D] and centers [k, D], got {tuple(feat.shape)} and {tuple(centers.shape)}")
+    (N, D), k = feat.shape, centers.shape[0]
+    if centers.shape[1] != D:
+        raise ValueError(f"centers are {centers.shape[1]} wide, feat is {D} wide")
+    lib = _lib.lib()
+    if not 1 <= D <= lib.ogs_kmeans_wide_max_dim():
+        raise ValueError(f"D={D}: the wide k-means takes 1 <= D <= {lib.ogs_kmeans_wide_max_dim()}")
+    if not 1 <= k <= lib.ogs_kmeans_wide_max_k():
+        raise ValueError(f"k={k}: the wide k-means takes 1 <= k <= {lib.ogs_kmeans_wide_max_k()}")
+    if N >= 1 << 31:
+        raise ValueError(f"N={N}: at most 2^31 - 1 rows")
+    if weights is not None and tuple(weights.shape) != (N,):
+        raise ValueError(f"weights must be [{N}], got {tuple(weights.shape)}")
+    if ids is not None and tuple(ids.shape) != (N,):
+        raise ValueError(f"ids must be [{N}], got {tuple(ids.shape)}")
+    return int(N), int(D), int(k), WIDE_METRICS[metric]
+
+
+def _wide_centers(centers):
+    _need_gpu(centers, "centers")
+    if not (centers.dtype == torch.float32 and centers.is_contiguous()):
+        raise RuntimeError("centers must be a contiguous fp32 GPU tensor (updated in place)")
+
+
+def _wide_tmp(N, D, k, dev):
+    nbytes = int(_lib.lib().ogs_kmeans_wide_tmp_bytes(N, D, k))
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+def wide_assign(feat: torch.Tensor, centers: torch.Tensor, metric: str = "l2"):
+    """(ids int64 [N], dist fp32 [N]): the nearest centre of every row of ``feat`` [N, D], D up to 1024, among ``centers``
+    [k, D], k up to 16384, on the matrix cores with fp32-class accuracy; exact ties go to the lowest index.  ``"l2"``: squared
+    Euclidean distance.  ``"cosine"``: ``centers`` must hold unit rows (the rows of ``feat`` need not), dist = 1 - cos."""
+    N, D, k, m = _wide_check(feat, centers, metric)
+    _need_gpu(feat, "feat")
+    _need_gpu(centers, "centers")
+    f, c = feat.detach().to(torch.float32).contiguous(), centers.detach().to(torch.float32).contiguous()
+    ids = torch.empty(N, dtype=torch.int32, device=f.device)
+    dist = torch.empty(N, dtype=torch.float32, device=f.device)
+    tmp, nbytes = _wide_tmp(N, D, k, f.device)
+    check(_lib.lib().ogs_kmeans_wide_assign(ptr(f), N, D, ptr(c), k, m, ptr(ids), ptr(dist), ptr(tmp), nbytes, _stream()),
+          "ogs_kmeans_wide_assign")
+    return ids.to(torch.int64), dist
+
+
+def wide_update(feat: torch.Tensor, ids: torch.Tensor, centers: torch.Tensor, metric: str = "l2", weights=None):
+    """One centre update in place: ``centers[c]`` becomes the ``weights``-weighted mean of the rows with ``ids == c`` (cosine:
+    normalised), summed in a fixed order without float atomics; a centre without weight keeps its value.  Returns counts fp32
+    [k], the weight every centre received."""
+    N, D, k, m = _wide_check(feat, centers, metric, weights, ids)
+    _need_gpu(feat, "feat")
+    _wide_centers(centers)
+    f = feat.detach().to(torch.float32).contiguous()
+    w = None if weights is None else weights.detach().to(device=f.device, dtype=torch.float32).contiguous()
+    i32 = ids.detach().to(device=f.device, dtype=torch.int32).contiguous()
+    counts = torch.empty(k, dtype=torch.float32, device=f.device)
+    tmp, nbytes = _wide_tmp(N, D, k, f.device)
+    check(_lib.lib().ogs_kmeans_wide_update(ptr(f), ptr(w), N, D, ptr(i32), k, m, ptr(centers), ptr(counts), ptr(tmp), nbytes,
+                                            _stream()), "ogs_kmeans_wide_update")
+    return counts
+
+
+def wide_lloyd(feat: torch.Tensor, centers: torch.Tensor, iters: int, metric: str = "l2", weights=None):
+    """``iters`` Lloyd iterations and the final re-assignment, one C call, no read-back; ``centers`` [k, D] is updated in place.
+    Returns (ids int64 [N], dist fp32 [N], counts fp32 [k] of the last update, inertia fp64 [iters + 1]: ``sum w * dist`` of
+    every assignment).  Rows with weight 0 are assigned but move nothing.  The same bytes every run."""
+    N, D, k, m = _wide_check(feat, centers, metric, weights)
+    if int(iters) < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    _need_gpu(feat, "feat")
+    _wide_centers(centers)
+    f = feat.detach().to(torch.float32).contiguous()
+    w = None if weights is None else weights.detach().to(device=f.device, dtype=torch.float32).contiguous()
+    ids = torch.empty(N, dtype=torch.int32, device=f.device)
+    dist = torch.empty(N, dtype=torch.float32, device=f.device)
+    counts = torch.zeros(k, dtype=torch.float32, device=f.device)
+    inertia = torch.empty(int(iters) + 1, dtype=torch.float64, device=f.device)
+    tmp, nbytes = _wide_tmp(N, D, k, f.device)
+    check(_lib.lib().ogs_kmeans_wide_lloyd(ptr(f), ptr(w), N, D, ptr(centers), k, m, int(iters), ptr(ids), ptr(dist), ptr(counts),
+                                           ptr(inertia), ptr(tmp), nbytes, _stream()), "ogs_kmeans_wide_lloyd")
+    return ids.to(torch.int64), dist, counts, inertia
+
+
 class _GatherSTE(torch.autograd.Function):
     """value = centres[ids][:, :out_dim]; gradient goes straight through to the instance features
     (kmeans_quantize.py:273-275: ins_feat - ins_feat.detach() + sampled_centers[:, :6])."""

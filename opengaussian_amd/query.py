@@ -24,6 +24,8 @@
 ``diffuse`` /               the same graph inside a training loss: the diffusion with a backward (``knn.gather_sum`` per step) and
 ``neighbor_smoothness``     the loss sum w |F_i - F_j|^2 fused forward and backward; gradients through the reverse-edge lists
                             (``knn.reverse_edges``), no float atomics
+``build_codebook``          lifted features -> leaves: wide k-means (``kmeans.wide_lloyd``, D up to 1024) into the ``leaf_ind`` /
+                            ``leaf_lang_feat`` / ``occu_count`` the text queries above take -- no trained instance features needed
 ``click_features`` /        the reference's own click route (scripts/render_by_click.py:35-66,138-166), batched over clicks, in
 ``select_leaves_by_click``  plain torch
 
@@ -830,6 +832,59 @@ def features_from_votes(table, min_weight=0.0):
     ok = weight > float(min_weight)
     feat = torch.where(ok[:, None], sums / torch.where(ok, weight, torch.ones_like(weight))[:, None], torch.zeros_like(sums))
     return feat, weight
+
+
+Codebook = namedtuple("Codebook", "leaf_ind leaf_feat occu_count dist valid")
+
+
+def build_codebook(features, k, weights=None, metric="cosine", iters=10, init=None, seed=0):
+    """Cluster lifted per-Gaussian features into the per-leaf table the text queries take: the training-free route
+    lift -> (diffuse) -> cluster -> ``select_leaves_by_text`` / ``classify_points`` / ``render_queries``.
+
+    ``features`` [N, D] and ``weights`` [N] are what ``features_from_votes`` returns (fp64 is cast to fp32); D up to 1024, k up to
+    16384.  A row is VALID when its weight is positive (no weights: every row) and it is not all zero; the other rows are
+    assigned like any row but move no centre.  ``init`` [k, D] are the starting centres, or ``None``: the valid rows at a
+    ``torch.randperm`` seeded with ``seed`` (ValueError when there are fewer than k).  ``"cosine"`` normalises the starting
+    centres and keeps them unit vectors; ``"l2"`` clusters the raw vectors.  ``iters`` Lloyd iterations of
+    ``kmeans.wide_lloyd`` (HIP, the same bytes every run), then the final assignment.
+
+    Returns ``Codebook(leaf_ind [N] int64, leaf_feat [k, D] fp32, occu_count [k] int64 -- valid rows per leaf, dist [N] fp32,
+    valid [N] bool)``: ``leaf_feat`` / ``occu_count`` are ``select_leaves_by_text``'s ``leaf_lang_feat`` / ``occu_count`` and
+    ``leaf_ind`` is ``classify_points``'s."""
+    from . import kmeans as _kmeans
+    if features.dim() != 2:
+        raise ValueError(f"features must be [N, D], got {tuple(features.shape)}")
+    N, D = features.shape
+    k = int(k)
+    if weights is not None and tuple(weights.shape) != (N,):
+        raise ValueError(f"weights must be [{N}], got {tuple(weights.shape)}")
+    if init is not None and tuple(init.shape) != (k, D):
+        raise ValueError(f"init must be [{k}, {D}], got {tuple(init.shape)}")
+    if metric not in _kmeans.WIDE_METRICS:
+        raise ValueError(f"metric must be one of {sorted(_kmeans.WIDE_METRICS)}, got {metric!r}")
+    lib = _lib.lib()
+    if not 1 <= D <= lib.ogs_kmeans_wide_max_dim() or not 1 <= k <= lib.ogs_kmeans_wide_max_k():
+        raise ValueError(f"D={D}, k={k}: the wide k-means takes 1 <= D <= {lib.ogs_kmeans_wide_max_dim()} and "
+                         f"1 <= k <= {lib.ogs_kmeans_wide_max_k()}")
+    with torch.no_grad():
+        valid = (features != 0).any(dim=1)
+        if weights is not None:
+            valid &= weights.to(features.device) > 0
+        if init is None:
+            rows = torch.nonzero(valid).reshape(-1)
+            if rows.numel() < k:
+                raise ValueError(f"{rows.numel()} valid rows cannot seed k={k} centres")
+            gen = torch.Generator().manual_seed(int(seed))
+            init = features[rows[torch.randperm(rows.numel(), generator=gen)[:k].to(rows.device)]]
+        _need_gpu(features, "features")
+        feat = _f32(features)
+        centers = init.detach().to(device=feat.device, dtype=torch.float32).contiguous().clone()
+        if metric == "cosine":
+            centers = torch.nn.functional.normalize(centers, dim=1)
+        w = valid.to(torch.float32) if weights is None else torch.where(valid, weights.to(feat.device, torch.float32), 0.0)
+        ids, dist, _, _ = _kmeans.wide_lloyd(feat, centers, int(iters), metric, w)
+        occu = torch.bincount(ids[valid], minlength=k)
+        return Codebook(ids, centers, occu, dist, valid)
 
 
 def neighbor_weights(d2, idx, valid=None, bandwidth=None):
