@@ -227,6 +227,13 @@ int ogs_raster_forward_render(const OgsRasterFwdArgs* args, int64_t num_rendered
 int ogs_raster_read_num_rendered_async(const OgsRasterFwdArgs* args, void* stream, uint32_t* host_pinned);
 int ogs_raster_forward_render_deferred(const OgsRasterFwdArgs* args, int64_t capacity, void* stream);
 
+/* Diagnostics: how many (Gaussian, tile) pairs the render phase of this pass expands, read back with a BLOCKING 4-byte copy into
+ * *host.  num_rendered stays the sum of the reference's tile rects (what the buffers are sized from); an ungrouped default-mode
+ * pass of more than 1024 Gaussians expands each Gaussian's rect cut down to the bounding box of the ellipse inside which it can
+ * reach alpha >= 1/255, so its count is smaller.  Every other pass: num_rendered.  Valid after ogs_raster_forward_geometry on the
+ * same args while geom_tmp is alive. */
+int ogs_raster_read_num_emitted(const OgsRasterFwdArgs* args, void* stream, uint32_t* host);
+
 /* Tiny pass: the whole forward in TWO launches for P <= ogs_raster_tiny_max_points() Gaussians (ungrouped) -- the
  * single-Gaussian footprint renders of the SAM refiner (utils/sam_refinement_utils.py:330-403: one P = 1 call per
  * Gaussian and camera, thousands of times) and other very small subset renders, where the ~25 launches of the

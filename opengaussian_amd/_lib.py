@@ -117,6 +117,7 @@ SIGNATURES = {
     "ogs_raster_forward_render": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.c_int64, _vp]),
     "ogs_raster_read_num_rendered_async": (C.c_int, [C.POINTER(OgsRasterFwdArgs), _vp, _vp]),
     "ogs_raster_forward_render_deferred": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.c_int64, _vp]),
+    "ogs_raster_read_num_emitted": (C.c_int, [C.POINTER(OgsRasterFwdArgs), _vp, C.POINTER(C.c_uint32)]),
     "ogs_raster_stats_image_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "ogs_raster_stats_tmp_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "ogs_raster_forward_group_stats": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsGroupStatsArgs), C.c_int64, _vp]),

@@ -185,7 +185,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 407; }
+int ogs_version(void) { return 408; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 
@@ -278,8 +278,9 @@ static int forward_geometry_impl(const OgsRasterFwdArgs* a_in, void* stream_, in
         // (full-list passes; a default pass leaves offsets[] unwritten, see below)
         rc = launch_preprocess(*a, gs, gt, s, raw);
         if (rc != OGS_OK) return rc;
-        // default mode: preprocess left one sum per workgroup, one small launch makes them offsets and the total, and duplicate
-        // scans its own 256 counts (block_sum_offsets); the full-list export keeps the scan
+        // default mode: preprocess left two sums per workgroup (emitted and reference tiles), one small launch makes the emitted
+        // ones offsets and forms both totals, and duplicate scans its own 256 counts (block_sum_offsets); the full-list export
+        // keeps the scan
         rc = block_sum_offsets(*a) ? launch_block_offsets(*a, gt, s)
                                    : exclusive_scan_u32(gt.tiles_touched, nullptr, gt.offsets, a->P, gt.num_rendered, gt.sort_tmp, s, a->debug);
         if (rc != OGS_OK) return rc;
@@ -357,6 +358,20 @@ int ogs_raster_read_num_rendered_async(const OgsRasterFwdArgs* a, void* stream_,
     return OGS_OK;
 }
 
+// The count of (Gaussian, tile) pairs the pass's duplicate_kernel writes, by a blocking 4-byte copy (tests, scripts: no pass
+// needs it on the host).  Call between the geometry phase and the release of geom_tmp.
+int ogs_raster_read_num_emitted(const OgsRasterFwdArgs* a, void* stream_, uint32_t* host) {
+    if (!a || !host) { set_error("read_num_emitted: NULL pointer"); return OGS_ERR_INVALID_ARG; }
+    *host = 0;
+    if (a->P == 0) return OGS_OK;
+    if (!a->geom_tmp) { set_error("read_num_emitted: geom_tmp == NULL"); return OGS_ERR_INVALID_ARG; }
+    const GeomTmp gt = GeomTmp::carve(a->geom_tmp, a->P);
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    OGS_HIP_CHECK(hipMemcpyAsync(host, block_sum_offsets(*a) ? gt.emitted() : gt.num_rendered, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    OGS_HIP_CHECK(hipStreamSynchronize(s));
+    return OGS_OK;
+}
+
 // D = exact num_rendered (deferred == false) or the CAPACITY of point_list / binning_tmp / sorted_rec while the
 // binning kernels read the true count from device memory (deferred == true).
 // stats != NULL: the statistics pass of ogs_raster_forward_group_stats (no images; its own, smaller image state).
@@ -389,7 +404,10 @@ static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipS
         uint32_t* vbuf[2];
         vbuf[passes & 1] = a->point_list;        // buffer index after `passes` flips from 0
         vbuf[(passes & 1) ^ 1] = bt.vals;
-        const uint32_t* n_dev = deferred ? gt.num_rendered : nullptr;
+        // How many keys there are.  A block-sum pass emits the pairs of the reach ellipse's rects (preprocess_one, "8b"): fewer
+        // than the D the host sized the buffers for, whether D is exact or a capacity, so its kernels always read the emitted
+        // count from device memory.  Every other pass emits the reference rects: D itself, or gt.num_rendered when deferred.
+        const uint32_t* n_dev = block_sum_offsets(*a) ? gt.emitted() : deferred ? gt.num_rendered : nullptr;
         // The (Gaussian, tile) pairs that cannot reach a pixel of their tile (52 % on the bench scene) leave the list in the FIRST
         // pass of the tile sort: duplicate gives them the key kDropKey, the pass leaves those out of its histograms and of its
         // output and reports how many keys it wrote; every later pass, the tile ranges and pack see the reachable pairs only,

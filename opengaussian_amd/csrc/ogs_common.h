@@ -291,6 +291,10 @@ int radix_pass(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_
                int64_t n, int shift, int bits, void* tmp, hipStream_t stream, int debug,
                const uint32_t* n_dev = nullptr, bool drop = false, uint32_t* kept_out = nullptr);
 
+// words of one run of GeomTmp::block_sum holding nb sums: padded, so that block_offsets_kernel loads both runs 16 bytes at a time
+constexpr int kBlockSumPad = 8;
+__host__ __device__ constexpr int block_sum_run(int nb) { return (nb + kBlockSumPad - 1) / kBlockSumPad * kBlockSumPad; }
+
 struct GeomTmp {        // transient, but must survive from forward_geometry to forward_render
     uint32_t* tiles_touched;   // [P]
     uint32_t* keys[2];         // [P] depth bits ping-pong; keys[0] by Gaussian index as preprocess wrote it on the per-tile path
@@ -298,15 +302,24 @@ struct GeomTmp {        // transient, but must survive from forward_geometry to 
     uint32_t* order[2];        // [P] Gaussian ids ping-pong; order[0] holds the depth order at the end (depth-sorted paths only)
     uint32_t* offsets;         // [P] exclusive scan of tiles_touched in the order duplicate walks (index or depth order); not
                                // written by a pass that takes its offsets from block_sum (block_sum_offsets)
-    uint32_t* num_rendered;    // [64] word 0: num_rendered; word 1 (`visible()`, depth-sorted paths only): Gaussians in the depth
+    uint32_t* num_rendered;    // [64] word 0: num_rendered (sum of the reference rects); word 2: emitted(), below; word 1 (`visible()`, depth-sorted paths only): Gaussians in the depth
                                // order -- the culled ones (key kDropKey: behind the near plane, outside every group, empty tile
                                // rect) leave the depth sort in its first pass, so the later passes, the scan and duplicate only
                                // see what is drawn
     void* sort_tmp;
-    uint32_t* block_sum;       // [ceil(P / kBlock)] block-sum scheme (block_sum_offsets): preprocess leaves the sum of tiles_touched
-                               // of each of its workgroups here, block_offsets_kernel turns the sums into their exclusive prefix
-                               // in place, and the workgroup of duplicate_kernel with the same index starts its range there
+    uint32_t* block_sum;       // [2 block_sum_run(ceil(P / kBlock))] block-sum scheme (block_sum_offsets): preprocess leaves two sums per workgroup,
+                               // first run: the tiles of its EMITTED rects (emit_rect), which block_offsets_kernel turns into their
+                               // exclusive prefix in place and where the workgroup of duplicate_kernel with the same index starts
+                               // its range; second run: the tiles of its reference rects, summed into num_rendered[0]
+    uint2* emit_rect;          // [P] block-sum scheme: the tile rect duplicate_kernel expands for the Gaussian, x = min | max << 16 of
+                               // the columns, y of the rows (max exclusive; all zero: nothing).  The reference rect cut down to the
+                               // bounding box of the reach ellipse (preprocess_one, "8b"): never larger, so the count of emitted
+                               // pairs, word kEmittedWord of num_rendered, is at most the reported num_rendered
+    static constexpr int kEmittedWord = 2;
     uint32_t* visible() const { return num_rendered + 1; }
+    // how many (Gaussian, tile) pairs duplicate_kernel writes: what the render phase's kernels read as their key count on a
+    // block-sum pass; on every other pass the pairs are the reference rects' and num_rendered[0] is that count
+    uint32_t* emitted() const { return num_rendered + kEmittedWord; }
     static GeomTmp carve(void* p, int P) {
         Carver c(p);
         GeomTmp g;
@@ -318,7 +331,8 @@ struct GeomTmp {        // transient, but must survive from forward_geometry to 
         g.offsets = c.take<uint32_t>(P);
         g.num_rendered = c.take<uint32_t>(64);
         g.sort_tmp = c.take<char>(sort_tmp_bytes(P));
-        g.block_sum = c.take<uint32_t>((size_t)(P + kBlock - 1) / kBlock);
+        g.block_sum = c.take<uint32_t>(2 * (size_t)block_sum_run((P + kBlock - 1) / kBlock));
+        g.emit_rect = c.take<uint2>(P);
         return g;
     }
     static size_t bytes(int P) {
@@ -326,7 +340,8 @@ struct GeomTmp {        // transient, but must survive from forward_geometry to 
         for (int i = 0; i < 6; ++i) c.take<uint32_t>(P);
         c.take<uint32_t>(64);
         c.take<char>(sort_tmp_bytes(P));
-        c.take<uint32_t>((size_t)(P + kBlock - 1) / kBlock);
+        c.take<uint32_t>(2 * (size_t)block_sum_run((P + kBlock - 1) / kBlock));
+        c.take<uint2>(P);
         return c.off;
     }
 };
@@ -359,8 +374,8 @@ struct BinTmp {         // transient, render phase
 // raw (here and in the two single-workgroup launchers below): the raw-model form of the kernel (include/ogs_model.h); the
 // pointer slots of `a` then hold the raw arrays (capi.hip::raw_fwd_args)
 int launch_preprocess(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s, bool raw = false);
-// block-sum scheme: gt.block_sum (one sum of tiles_touched per preprocess workgroup) -> exclusive prefix in place, total ->
-// gt.num_rendered[0]; one workgroup
+// block-sum scheme: gt.block_sum (per preprocess workgroup, emitted tiles | reference tiles) -> exclusive prefix of the emitted sums
+// in place, their total -> gt.emitted(), the reference total -> gt.num_rendered[0]; one workgroup
 int launch_block_offsets(const OgsRasterFwdArgs& a, const GeomTmp& gt, hipStream_t s);
 int launch_tiny_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, uint32_t* order, hipStream_t s, bool raw = false);
 int launch_small_geometry(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomTmp& gt, hipStream_t s, bool raw = false);
@@ -387,9 +402,11 @@ int launch_tile_ranges(const uint32_t* tile_keys_sorted, int64_t D, uint2* range
 // Gaussians.  Decided from the arguments alone, so that the geometry and the render phase of a pass agree.
 inline bool per_tile_depth_order(const OgsRasterFwdArgs& a) { return a.num_groups <= 1 && a.P > kSmallMaxP; }
 // The default-mode passes among those need no scan over the P Gaussians either: preprocess_kernel and duplicate_kernel cut the
-// Gaussians into the same 256-wide workgroups, so preprocess leaves one sum of tiles_touched per workgroup, one small launch
-// turns the sums into offsets, and every workgroup of duplicate scans its own 256 counts in LDS.  A full_binning pass (the
-// parity export) keeps the scan and offsets[].  Also decided from the arguments alone.
+// Gaussians into the same 256-wide workgroups, so preprocess leaves one sum of emitted tiles per workgroup, one small launch
+// turns the sums into offsets, and every workgroup of duplicate scans its own 256 counts in LDS.  These are also the passes
+// whose pairs come from the reach ellipse's rect (GeomTmp::emit_rect) instead of the reference's: the count of pairs is then
+// gt.emitted(), below the reported num_rendered.  A full_binning pass (the parity export) keeps the reference rects, the scan
+// and offsets[].  Also decided from the arguments alone.
 inline bool block_sum_offsets(const OgsRasterFwdArgs& a) { return per_tile_depth_order(a) && a.full_binning == 0; }
 // Every tile's segment of point_list into (depth key, id) order in place, keys gathered by id from depth_keys (the 32-bit keys
 // preprocess wrote); workgroup b takes tiles tile_order[4b .. 4b+3] (b.. when NULL).  Lists up to kWaveSortCap entries are sorted by

@@ -112,7 +112,11 @@ __device__ __forceinline__ uint32_t preprocess_one(
     const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, const float* __restrict__ viewmatrix,
     const float* __restrict__ projmatrix, const float* __restrict__ campos, float4* __restrict__ rec_row,
     uint32_t* __restrict__ clamped_out, int32_t* __restrict__ radii, uint32_t* __restrict__ tiles_touched,
-    const int32_t* __restrict__ group_ids, int num_groups, uint32_t* touched_ret = nullptr) {
+    const int32_t* __restrict__ group_ids, int num_groups, uint32_t* touched_ret = nullptr,
+    uint2* __restrict__ emit_rect = nullptr, uint32_t* emitted_ret = nullptr) {
+    // emit_rect (block-sum passes only, kernel-uniform): where the tile rect duplicate_kernel expands goes -- the reference rect
+    // cut down to the reach ellipse's bounding box ("8b" below); *emitted_ret gets its tile count.  `touched` stays the reference's
+    // rect: the count the API reports.
     // rec_row: where this Gaussian's record goes (its row of the record array, or of the workgroup's LDS staging tile)
     constexpr int NV = rec_vec4(C);
     // camera matrices: wave-uniform addresses -> scalar loads
@@ -130,7 +134,8 @@ __device__ __forceinline__ uint32_t preprocess_one(
     uint32_t clamped = 0;
 
     int radius = 0;
-    uint32_t touched = 0;
+    uint32_t touched = 0, emitted = 0;
+    uint2 erect = make_uint2(0u, 0u);
     float pxl = 0.f, pyl = 0.f, depth = 0.f, cA = 0.f, cB = 0.f, cC = 0.f;
 
     // 1. view space + near cull
@@ -216,6 +221,50 @@ __device__ __forceinline__ uint32_t preprocess_one(
                 radius = my_radius;
                 touched = (uint32_t)area;
                 depth = pvz;
+                if (emit_rect != nullptr) {
+                    // 8b. The rect duplicate_kernel expands: the reference rect cut down to the bounding box of the reach ellipse.
+                    // duplicate_kernel keeps the pair (this Gaussian, tile) iff  m >= thr  with thr = -L, L = ln(255 opacity) +
+                    // kThrMargin and m = max_power_in_box over the tile's box of d = centre - pixel.  In fp32 that m is at most
+                    //     max over the box of -Q(d) / 2  +  1.04e-6 T,      Q(d) = A dx^2 + 2 B dx dy + C dy^2,
+                    // T = (A X^2 + C Y^2) / 2 + |B| X Y the largest term over the box: 8e-7 T is the test's own slack and every
+                    // evaluation of the form rounds by less than 4 x 2^-24 T.  No tile of the reference rect has a pixel further than
+                    // radius + 16 from the centre on either axis, so T <= tmax below (one pixel more for the rounding of the rect).
+                    // A kept tile therefore has a point with  Q(d) <= t,  t = 2 (L + 1.04e-6 tmax), and with A, C > 0 and
+                    // A C - B^2 > 0 the set Q <= t is an ellipse whose bounding box is |dx| <= sqrt(t C / (A C - B^2)),
+                    // |dy| <= sqrt(t A / (A C - B^2)).  A, B, C are the fp32 conic duplicate_kernel reads, not the covariance they were
+                    // inverted from: for a needle the fp32 determinant above is off by per cent.  A C - B^2 cancels just as badly in
+                    // fp32; both products are exact in fp64 and their difference rounds once, relative to itself.
+                    // Margins: 1.25e-6 for 1.04e-6 and 1e-4 on L cover the roundings of tmax, of t and of the test's final add
+                    // (all ~1e-6 at most); 1.00001 covers the five fp32 roundings of the extent; the additive pad covers the
+                    // roundings of the box corners in duplicate_kernel and of the two sums below (each < 2^-23 of |centre| +
+                    // radius).  Tile tx (pixels 16 tx .. 16 tx + 15) meets |x - pxl| <= hx iff
+                    // ceil((pxl - hx - 15) / 16) <= tx <= floor((pxl + hx) / 16): the divisions by 16 are exact.
+                    // t < 0: no tile can be kept -- empty rect.  Anything not finite or not an ellipse: the reference rect.
+                    const float Rr = rf + 17.0f;
+                    const float tmax = (0.5f * (cA + cC) + fabsf(cB)) * (Rr * Rr);
+                    const float t = 2.0f * ((__logf(255.0f * opacity) + kThrMargin) + (1.0e-4f + 1.25e-6f * tmax));
+                    const float dcf = (float)((double)cA * (double)cC - (double)cB * (double)cB);
+                    const float pad = 1.0e-6f * (fmaxf(fabsf(pxl), fabsf(pyl)) + Rr) + 1.0e-3f;
+                    const float hx = sqrtf(t * (cC / dcf)) * 1.00001f + pad;
+                    const float hy = sqrtf(t * (cA / dcf)) * 1.00001f + pad;
+                    int ex0 = rminx, ex1 = rmaxx, ey0 = rminy, ey1 = rmaxy;
+                    // A reference rect wider than 255 tiles stays as it is: duplicate_kernel flags its pairs without a test, so every
+                    // one of them is in the reference's list as this project keeps it, and a cut would take some out.
+                    const bool ellipse = cA > 0.f && cC > 0.f && dcf > 0.f        // (a determinant that rounded below zero: no)
+                                         && rmaxx - rminx <= 255;
+                    if (ellipse && t < 0.f) {
+                        ex0 = ex1 = ey0 = ey1 = 0;
+                    } else if (ellipse && hx < 3.0e38f && hy < 3.0e38f) {
+                        ex0 = max(ex0, tr(ceilf((pxl - hx - 15.0f) / (float)kTile)));
+                        ey0 = max(ey0, tr(ceilf((pyl - hy - 15.0f) / (float)kTile)));
+                        ex1 = min(ex1, tr(floorf((pxl + hx) / (float)kTile)) + 1);
+                        ey1 = min(ey1, tr(floorf((pyl + hy) / (float)kTile)) + 1);
+                        if (ex1 <= ex0 || ey1 <= ey0) ex0 = ex1 = ey0 = ey1 = 0;      // (the cut ends may lie anywhere: not packed)
+                    }
+                    emitted = (uint32_t)((ex1 - ex0) * (ey1 - ey0));
+                    // both ends in 16 bits each (grids up to 4095 tiles a side): nothing is rounded, no rect can shrink
+                    erect = make_uint2((uint32_t)ex0 | ((uint32_t)ex1 << 16), (uint32_t)ey0 | ((uint32_t)ey1 << 16));
+                }
             }
         }
     }
@@ -249,6 +298,7 @@ __device__ __forceinline__ uint32_t preprocess_one(
     radii[idx] = radius;
     if (tiles_touched) tiles_touched[idx] = touched;
     if (touched_ret) *touched_ret = touched;
+    if (emit_rect) { emit_rect[idx] = erect; *emitted_ret = emitted; }
     return ok ? __float_as_uint(depth) : 0xFFFFFFFFu;
 }
 
@@ -261,37 +311,38 @@ __global__ __launch_bounds__(kBlock) void preprocess_kernel(
     const float* __restrict__ projmatrix, const float* __restrict__ campos, float4* __restrict__ rec,
     uint32_t* __restrict__ clamped_out, int32_t* __restrict__ radii, uint32_t* __restrict__ tiles_touched,
     uint32_t* __restrict__ depth_keys, uint32_t* __restrict__ order, const int32_t* __restrict__ group_ids,
-    int num_groups, uint32_t* __restrict__ block_sum) {
+    int num_groups, uint32_t* __restrict__ block_sum, uint2* __restrict__ emit_rect) {
     // The workgroup's records are staged in LDS and written as ONE contiguous range: a thread storing its own 48..80-byte
     // record makes every store instruction touch 64 different cache lines.
     constexpr int NV = rec_vec4(C);
     __shared__ float4 s_rec[kBlock * NV];
-    __shared__ uint32_t s_wave_sum[kBlock / kWave];
+    __shared__ uint32_t s_wave_sum[2][kBlock / kWave];
     const int tid = threadIdx.x;
     const int idx = blockIdx.x * kBlock + tid;
-    uint32_t touched = 0;
+    uint32_t touched = 0, emitted = 0;
     if (idx < P) {
         depth_keys[idx] = preprocess_one<C, RAW>(idx, W, H, sh_degree, sh_coeffs, tanfovx, tanfovy, focal_x, focal_y, scale_modifier,
                                             means3D, colors_precomp, shs, opacities, scales, rotations, cov3D_precomp, viewmatrix,
                                             projmatrix, campos, s_rec + tid * NV, clamped_out, radii, tiles_touched, group_ids,
-                                            num_groups, &touched);
+                                            num_groups, &touched, emit_rect, &emitted);
         if (order) order[idx] = (uint32_t)idx;          // the start of the global depth sort (grouped passes only)
     }
-    // block-sum scheme (block_sum_offsets): this workgroup's sum of tiles_touched, the share of the scan that duplicate_kernel's
-    // workgroup of the same index cannot form itself.  Wave reduction, then the four wave sums through LDS behind the barrier
-    // the record staging needs anyway
+    // block-sum scheme (block_sum_offsets): this workgroup's sum of the tiles duplicate_kernel emits for it (the emitted rects),
+    // the share of the scan that duplicate_kernel's workgroup of the same index cannot form itself, and -- in the second run of
+    // block_sum -- its sum of the reference rects, of which only the total is needed (num_rendered).  Wave reductions, then the
+    // four wave sums of each through LDS behind the barrier the record staging needs anyway
     if (block_sum != nullptr) {           // kernel-uniform
-        uint32_t t = touched;
+        uint32_t t = emitted, u = touched;
 #pragma unroll
-        for (int d = kWave / 2; d >= 1; d >>= 1) t += __shfl_down(t, d, kWave);
-        if ((tid & (kWave - 1)) == 0) s_wave_sum[tid / kWave] = t;
+        for (int d = kWave / 2; d >= 1; d >>= 1) { t += __shfl_down(t, d, kWave); u += __shfl_down(u, d, kWave); }
+        if ((tid & (kWave - 1)) == 0) { s_wave_sum[0][tid / kWave] = t; s_wave_sum[1][tid / kWave] = u; }
     }
     __syncthreads();
-    if (block_sum != nullptr && tid == 0) {
+    if (block_sum != nullptr && tid < 2) {
         uint32_t t = 0;
 #pragma unroll
-        for (int w = 0; w < kBlock / kWave; ++w) t += s_wave_sum[w];
-        block_sum[blockIdx.x] = t;
+        for (int w = 0; w < kBlock / kWave; ++w) t += s_wave_sum[tid][w];
+        block_sum[tid * block_sum_run((int)gridDim.x) + blockIdx.x] = t;
     }
     const size_t row0 = (size_t)blockIdx.x * kBlock;
     const int n4 = min(kBlock, P - (int)row0) * NV;
@@ -400,7 +451,7 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
                                                            const float4* __restrict__ rec,
                                                            const uint32_t* __restrict__ order,
                                                            const uint32_t* __restrict__ offsets,
-                                                           const uint32_t* __restrict__ tiles_touched,
+                                                           const uint2* __restrict__ emit_rect,
                                                            const uint32_t* __restrict__ block_base,
                                                            uint32_t* __restrict__ tile_keys,
                                                            uint32_t* __restrict__ vals, uint32_t capacity,
@@ -421,7 +472,8 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
     //
     // Where the range starts: offsets[] (the scan of the geometry phase, in the order of this walk), or -- block_base != NULL,
     // index order only (block_sum_offsets) -- block_base[blockIdx.x], the exclusive prefix of the sums preprocess_kernel's
-    // workgroups left, plus the exclusive prefix of this workgroup's own 256 tiles_touched, scanned here.
+    // workgroups left (sums of the EMITTED rects, preprocess_one "8b"), plus the exclusive prefix of this workgroup's own 256
+    // emitted counts, formed from emit_rect[] and scanned here.
     __shared__ uint32_t s_wave_sum[kBlock / kWave];
     __shared__ uint32_t s_off[kBlock];      // output offset relative to the workgroup's first slot
     __shared__ uint32_t s_gid[kBlock];
@@ -447,36 +499,47 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
     int wide_x0 = 0, wide_x1 = 0, wide_y0 = 0, wide_y1 = 0;      // tile rect of a footprint wider than 255 tiles (else empty)
     if (r < P) {
         gid = order ? order[r] : (uint32_t)r;
-        if (block_base != nullptr) touched = tiles_touched[r];
-        else off = offsets[r];
         // culled Gaussians (radius 0) may carry any group id: they emit nothing
         if (group_ids != nullptr) key0 = (uint32_t)max(group_ids[gid], 0) * (uint32_t)(gx * gy);
-        const float4 a = rec[(size_t)gid * NV];
-        const int radius = __float_as_int(a.w);
-        if (radius > 0) {
+        int rminx = 0, rminy = 0, rmaxx = 0, rmaxy = 0;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (block_base != nullptr) {
+            // the rect preprocess_kernel counted into this workgroup's sum, as it packed it (never re-derived here: a rect
+            // that disagreed with that count would shift every offset behind it); (0, 0) for a culled Gaussian
+            const uint2 e = emit_rect[r];
+            rminx = (int)(e.x & 0xFFFFu); rmaxx = (int)(e.x >> 16);
+            rminy = (int)(e.y & 0xFFFFu); rmaxy = (int)(e.y >> 16);
+            touched = (uint32_t)((rmaxx - rminx) * (rmaxy - rminy));
+            if (touched != 0u) a = rec[(size_t)gid * NV];
+        } else {
+            off = offsets[r];
+            a = rec[(size_t)gid * NV];
+            const int radius = __float_as_int(a.w);
+            if (radius > 0) {
+                const float rf = (float)radius;
+                auto tr = [](float v) -> int {
+                    if (!(fabsf(v) < 3.0e38f)) v = 0.f;
+                    v = fminf(fmaxf(v, -2.0e9f), 2.0e9f);
+                    return (int)v;
+                };
+                rminx = min(gx, max(0, tr((a.x - rf) / (float)kTile)));
+                rminy = min(gy, max(0, tr((a.y - rf) / (float)kTile)));
+                rmaxx = min(gx, max(0, tr((a.x + rf + (float)kTile - 1.0f) / (float)kTile)));
+                rmaxy = min(gy, max(0, tr((a.y + rf + (float)kTile - 1.0f) / (float)kTile)));
+            }
+        }
+        const int w = rmaxx - rminx, h = rmaxy - rminy;
+        if (w > 0 && h > 0) {
             const float4 b = rec[(size_t)gid * NV + 1];
             ctr = make_float4(a.x, a.y, -(__logf(255.0f * b.w) + kThrMargin), b.y);
             con = make_float4(b.x, b.z, -b.y / b.x, -b.y / b.z);
-            const float rf = (float)radius;
-            auto tr = [](float v) -> int {
-                if (!(fabsf(v) < 3.0e38f)) v = 0.f;
-                v = fminf(fmaxf(v, -2.0e9f), 2.0e9f);
-                return (int)v;
-            };
-            const int rminx = min(gx, max(0, tr((a.x - rf) / (float)kTile)));
-            const int rminy = min(gy, max(0, tr((a.y - rf) / (float)kTile)));
-            const int rmaxx = min(gx, max(0, tr((a.x + rf + (float)kTile - 1.0f) / (float)kTile)));
-            const int rmaxy = min(gy, max(0, tr((a.y + rf + (float)kTile - 1.0f) / (float)kTile)));
-            const int w = rmaxx - rminx, h = rmaxy - rminy;
-            if (w > 0 && h > 0) {
-                cnt = (uint32_t)(w * h);
-                // width field is 8 bits: wider footprints (> 255 tiles = 4080 px) keep the per-thread loop below
-                rect = (uint32_t)rminx | ((uint32_t)rminy << 12) | ((uint32_t)min(w, 255) << 24);
-                if (w > 255) { wide_x0 = rminx; wide_x1 = rmaxx; wide_y0 = rminy; wide_y1 = rmaxy; }
-            }
+            cnt = (uint32_t)(w * h);
+            // width field is 8 bits: wider footprints (> 255 tiles = 4080 px) keep the per-thread loop below
+            rect = (uint32_t)rminx | ((uint32_t)rminy << 12) | ((uint32_t)min(w, 255) << 24);
+            if (w > 255) { wide_x0 = rminx; wide_x1 = rmaxx; wide_y0 = rminy; wide_y1 = rmaxy; }
         }
     }
-    uint32_t before = 0;                   // block_base: tiles_touched of the workgroup's Gaussians in front of this one
+    uint32_t before = 0;                   // block_base: emitted tiles of the workgroup's Gaussians in front of this one
     if (block_base != nullptr) {           // kernel-uniform
         const int lane = tid & (kWave - 1);
         uint32_t incl = touched;
@@ -551,36 +614,54 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
     }
 }
 
-// Block-sum scheme: the sums preprocess_kernel's workgroups left (nb = ceil(P / 256) words, a few KB) into their exclusive prefix,
-// in place, and their total into num_rendered[0] -- what is left of the scan over the P Gaussians.  One workgroup of 1024
-// threads, 8192 sums (2 M Gaussians) per trip: coalesced loads into LDS, all in flight at once (a thread walking its own run
-// through global memory waited for one load after the other: 6.4 us for 3 907 sums), eight sums per thread from there, wave
-// scan, sixteen wave totals.  32-bit sums, as the scan's (num_rendered >= 2^31 is refused by the render phase).
+// Block-sum scheme: the sums preprocess_kernel's workgroups left (two runs of nb = ceil(P / 256) words, a few KB, the second
+// starting block_sum_run(nb) words behind the first).  The first run, the tiles duplicate_kernel emits, becomes its exclusive
+// prefix, in place, and its total goes to total_out[kEmittedWord]: the key count of the render phase.  Of the second run, the
+// reference rects, only the total is formed: total_out[0], the num_rendered the API reports.  That is what is left of the scan over
+// the P Gaussians.  One workgroup of 1024 threads, 8192 sums (2 M Gaussians) per trip.  A thread owns eight consecutive sums of
+// each run and loads them as two 16-byte words per run, all four loads in flight at once: both runs start 32-byte aligned and are
+// padded to a multiple of eight words, so the loads stay inside them and only the values are masked at the end.  (A thread
+// walking its run with one 4-byte load after the other took 6.4 us for 3 907 sums; coalesced 4-byte loads staged through LDS
+// 5.6 us; this form carries the second run at the price of the first alone.)  Then the wave scan of the emitted sums, one wave
+// reduction of the reference sums, and the sixteen wave totals of each behind one barrier.  32-bit sums, as the scan's
+// (num_rendered >= 2^31 is refused by the render phase).
 constexpr int kOffsThreads = 1024, kOffsItems = 8, kOffsChunk = kOffsThreads * kOffsItems;
+static_assert(kOffsItems == 8 && kBlockSumPad == 8, "two uint4 per thread and run");
 __global__ __launch_bounds__(kOffsThreads) void block_offsets_kernel(uint32_t* __restrict__ block_sum, int nb,
                                                                      uint32_t* __restrict__ total_out) {
-    __shared__ uint32_t s_val[kOffsChunk];
     __shared__ uint32_t s_wave_sum[kOffsThreads / kWave];
+    __shared__ uint32_t s_ref_sum[kOffsThreads / kWave];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    uint32_t carry = 0;
+    const uint32_t* __restrict__ ref_sum = block_sum + block_sum_run(nb);
+    uint32_t carry = 0, ref_total = 0;
     for (int c0 = 0; c0 < nb; c0 += kOffsChunk) {
         const int n = min(kOffsChunk, nb - c0);
+        const int e0 = tid * kOffsItems;
+        uint32_t v[kOffsItems], u[kOffsItems], sum = 0, ref = 0;
+#pragma unroll
+        for (int k = 0; k < kOffsItems; ++k) v[k] = u[k] = 0u;
+        if (e0 < n) {
+            const uint4 a0 = *reinterpret_cast<const uint4*>(block_sum + c0 + e0), a1 = *reinterpret_cast<const uint4*>(block_sum + c0 + e0 + 4);
+            const uint4 r0 = *reinterpret_cast<const uint4*>(ref_sum + c0 + e0), r1 = *reinterpret_cast<const uint4*>(ref_sum + c0 + e0 + 4);
+            v[0] = a0.x; v[1] = a0.y; v[2] = a0.z; v[3] = a0.w; v[4] = a1.x; v[5] = a1.y; v[6] = a1.z; v[7] = a1.w;
+            u[0] = r0.x; u[1] = r0.y; u[2] = r0.z; u[3] = r0.w; u[4] = r1.x; u[5] = r1.y; u[6] = r1.z; u[7] = r1.w;
+        }
 #pragma unroll
         for (int k = 0; k < kOffsItems; ++k) {
-            const int e = k * kOffsThreads + tid;
-            s_val[e] = e < n ? block_sum[c0 + e] : 0u;
+            if (e0 + k >= n) v[k] = u[k] = 0u;            // the padding of the last eight words holds anything
+            sum += v[k];
+            ref += u[k];
         }
-        __syncthreads();
-        uint32_t v[kOffsItems], sum = 0;
-#pragma unroll
-        for (int k = 0; k < kOffsItems; ++k) { v[k] = s_val[tid * kOffsItems + k]; sum += v[k]; }
         uint32_t incl = sum;
 #pragma unroll
         for (int d = 1; d < kWave; d <<= 1) {
             const uint32_t o = __shfl_up(incl, d, kWave);
             if (lane >= d) incl += o;
         }
+#pragma unroll
+        for (int d = kWave / 2; d >= 1; d >>= 1) ref += __shfl_down(ref, d, kWave);
         if (lane == kWave - 1) s_wave_sum[wave] = incl;
+        if (lane == 0) s_ref_sum[wave] = ref;
         __syncthreads();
         uint32_t run = carry + incl - sum, total = 0;
 #pragma unroll
@@ -588,17 +669,17 @@ __global__ __launch_bounds__(kOffsThreads) void block_offsets_kernel(uint32_t* _
             const uint32_t t = s_wave_sum[w];
             if (w < wave) run += t;
             total += t;
+            ref_total += s_ref_sum[w];
         }
 #pragma unroll
         for (int k = 0; k < kOffsItems; ++k) {
-            const int e = tid * kOffsItems + k;
-            if (e < n) block_sum[c0 + e] = run;
+            if (e0 + k < n) block_sum[c0 + e0 + k] = run;
             run += v[k];
         }
         carry += total;
-        __syncthreads();                  // s_val and s_wave_sum are rewritten by the next trip
+        __syncthreads();                  // the wave sums are rewritten by the next trip
     }
-    if (tid == 0) total_out[0] = carry;
+    if (tid == 0) { total_out[0] = ref_total; total_out[GeomTmp::kEmittedWord] = carry; }
 }
 
 __global__ __launch_bounds__(kBlock) void mark_visible_kernel(int P, const float* __restrict__ means3D,
@@ -655,9 +736,9 @@ int launch_preprocess_c(const OgsRasterFwdArgs& a, const GeomState& gs, const Ge
     OGS_LAUNCH_NAMED(chan_name<C>(RAW ? kRawNames : kNames), (preprocess_kernel<C, RAW>), dim3(grid), dim3(kBlock), 0, s, a.P, a.W, a.H, a.sh_degree, a.sh_coeffs,
                        a.tanfovx, a.tanfovy, focal_x, focal_y, a.scale_modifier, a.means3D, a.colors_precomp, a.shs,
                        a.opacities, a.scales, a.rotations, a.cov3D_precomp, a.viewmatrix, a.projmatrix, a.campos,
-                       gs.rec, gs.clamped, a.radii, gt.tiles_touched, gt.keys[0],
+                       gs.rec, gs.clamped, a.radii, block_sum_offsets(a) ? (uint32_t*)nullptr : gt.tiles_touched, gt.keys[0],
                        per_tile_depth_order(a) ? (uint32_t*)nullptr : gt.order[0], a.num_groups > 1 ? a.group_ids : (const int32_t*)nullptr, a.num_groups,
-                       block_sum_offsets(a) ? gt.block_sum : (uint32_t*)nullptr);
+                       block_sum_offsets(a) ? gt.block_sum : (uint32_t*)nullptr, block_sum_offsets(a) ? gt.emit_rect : (uint2*)nullptr);
     OGS_LAUNCH_CHECK(a.debug, s);
     return OGS_OK;
 }
@@ -737,9 +818,9 @@ int launch_duplicate(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomT
     const uint32_t* order = depth_order ? gt.order[0] : nullptr;
     const uint32_t* n_visible = depth_order ? gt.visible() : nullptr;
     switch (rec_vec4(a.C)) {
-        case 3: OGS_LAUNCH(duplicate_kernel<3>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, gt.tiles_touched, base, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
-        case 4: OGS_LAUNCH(duplicate_kernel<4>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, gt.tiles_touched, base, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
-        case 5: OGS_LAUNCH(duplicate_kernel<5>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, gt.tiles_touched, base, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
+        case 3: OGS_LAUNCH(duplicate_kernel<3>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, gt.emit_rect, base, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
+        case 4: OGS_LAUNCH(duplicate_kernel<4>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, gt.emit_rect, base, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
+        case 5: OGS_LAUNCH(duplicate_kernel<5>, dim3(grid), dim3(kBlock), 0, s, a.P, n_visible, a.W, a.H, gs.rec, order, gt.offsets, gt.emit_rect, base, tile_keys, vals, capacity, grp, drop_unreachable, zero_ranges, n_zero); break;
         default: set_error("unsupported record size"); return OGS_ERR_UNSUPPORTED;
     }
     OGS_LAUNCH_CHECK(a.debug, s);

@@ -33,6 +33,9 @@ BACKWARD_CHANNELS = (3, 6, 9)          # the gradient record holds C + 7 <= 16 s
 TINY_MAX_P = 256
 # diagnostics (scripts/diag_repeat.py): when set to a list, every backward appends its raw gradient-record buffer
 _DEBUG_KEEP_BWD_TMP = None
+# diagnostics / tests: when set to a list, every streaming pass appends (num_rendered, pairs its render phase expanded) -- the
+# second comes from a blocking read-back (ogs_raster_read_num_emitted); default-mode passes expand fewer pairs than they report
+_DEBUG_EMITTED = None
 # Capacity hint of the sync-free render phase: (P, W, H) -> num_rendered of the most recent passes at that size.
 # The cameras of a training run take turns, so one pass's count does not predict the next one's: the
 # capacity is 1.25x the MAXIMUM over the last _HINT_WINDOW passes -- after one sweep over the views it covers all of
@@ -281,6 +284,10 @@ def _streaming_render(a: OgsRasterFwdArgs, dev, lib, debug: bool, raw: Optional[
             point_list, bin_tmp, sorted_rec, quad_list = alloc_render(D)
             check(lib.ogs_raster_forward_render(C.byref(a), D, stream), "ogs_raster_forward_render")
     _hint_record(key, D)
+    if _DEBUG_EMITTED is not None:
+        n = C.c_uint32(0)
+        check(lib.ogs_raster_read_num_emitted(C.byref(a), stream, C.byref(n)), "ogs_raster_read_num_emitted")
+        _DEBUG_EMITTED.append((D, int(n.value)))
     return geom, image, point_list, sorted_rec, quad_list, D
 
 
