@@ -251,6 +251,15 @@ int ogs_raster_forward_tiny(const OgsRasterFwdArgs* args, void* stream);
  * passes through global memory); 0 for any other level. */
 size_t ogs_raster_tile_sort_capacity(int32_t level);
 
+/* The counting sort by tile of a default streaming pass (test hooks; no effect on results).  The emitted pairs are cut into B
+ * chunks, each a multiple of ogs_raster_tile_count_trip() pairs long.  ogs_raster_tile_count_debug returns the B a pass with a
+ * list capacity D (the num_rendered, or the capacity, given to the render phase) and `tiles` tiles takes, 0 when it takes the
+ * radix sort instead, after setting two process-wide hooks: force_blocks > 0 forces B (still cut to what the scratch has room
+ * for: (B + 1) * tiles <= D), 0 hands the choice back; reverse != 0 places each chunk back to front (ties then arrive at the per-tile
+ * depth sort in descending id order), 0 front to back.  A negative value leaves that hook as it is. */
+int ogs_raster_tile_count_debug(int64_t D, int64_t tiles, int32_t force_blocks, int32_t reverse);
+size_t ogs_raster_tile_count_trip(void);
+
 /* Re-blend of a KEPT pass (new capability; no reference counterpart -- the reference re-runs preprocess, both sorts and the
  * duplication on every call).  From stage 1 on the reference trains `_ins_feat` alone (train.py:431-436: every other Gaussian
  * parameter is detached) and renders without the random footprint rescale (train.py:346-350: rescale only in stage 2), so for a

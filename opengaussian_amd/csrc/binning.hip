@@ -4,9 +4,12 @@
 //
 // Sort strategy (DESIGN.md "binning"): the reference sorts D=(Gaussian,tile) duplicates on a 64-bit
 // key (tile<<32 | depth bits) -- 6 byte-digit passes over D.  Here duplicates are emitted in Gaussian-index
-// order, a STABLE sort on the tile id alone (ceil(log2 T / 8) = 2 passes over D at 1080p) groups them
-// with every tile's list in id order, and one launch then sorts each tile's short list by depth in LDS
-// (tile_depth_sort_kernel): bit-identical order -- depth ascending inside a tile, ties by Gaussian index.
+// order, grouped by tile id alone, and one launch then sorts each tile's short list by (depth, Gaussian index) in LDS
+// (tile_depth_sort_kernel): bit-identical order -- depth ascending inside a tile, ties by Gaussian index, whatever
+// order the list arrived in.  The grouping is ONE counting pass on the whole tile id for the default streaming pass
+// (tile_count_kernel .. tile_place_kernel: the keys are read twice, only the values move, once), and a stable
+// radix sort (ceil(log2 T / 8) = 2 passes over D at 1080p) for full_binning, grids past the LDS histogram and lists
+// too short for the count table.
 // Grouped passes (up to 2^31 virtual tiles of a few entries) and the small path instead sort the P
 // Gaussians by depth once and emit the duplicates in that order.
 #include <stdlib.h>
@@ -521,10 +524,173 @@ __global__ __launch_bounds__(kBlock) void tile_ranges_kernel(const uint32_t* __r
     }
 }
 
+// ---- counting sort by tile ("tile count" path) ----------------------------------------------------------------------------
+// The default streaming pass (capi.hip::render_impl) needs no stable tile sort: tile_depth_sort_kernel orders ties by id itself,
+// so the pairs only have to reach their tile's segment, in any order.  That is one counting pass on the whole tile id:
+//   tile_count_kernel        the emitted keys [0, n) are cut into B contiguous chunks; workgroup b counts its chunk's keys per
+//                            tile in an LDS histogram of `tiles` words and writes row b of the (B + 1) x tiles table (coalesced);
+//   tile_count_scan_kernel   per tile: every cnt[b][t] -> its exclusive prefix over b, the column's total -> row B;
+//   tile_place_kernel        workgroup b: exclusive scan of the totals in LDS (the tiles' range starts: 32 KB from L2 and a
+//                            thousand-thread scan cost less than a launch of its own), cursors = start + its table row; it
+//                            re-reads its chunk, position of a kept pair = LDS atomicAdd on its tile's cursor, one 4-byte
+//                            store of the value.  No key is written.  Workgroup 0 also writes ranges[t] = (start, end),
+//                            (0, 0) for an empty tile (what tile_ranges_kernel leaves), and the grand total to `kept`.
+// No global atomic, no look-back, no waiting between workgroups.  A dropped pair (kDropKey) fails the one `key < tiles` test, as
+// would a key outside the grid, so no LDS word outside the histogram is ever addressed.
+// chunk length = ceil(n / B) rounded up to the trip (kCountTrip keys: one 16-byte load per thread), from the device's n.
+constexpr int kCountBlock = 1024;              // threads: the per-workgroup work on the `tiles` words (clear, row, scan) is 4x shorter
+constexpr int kCountItems = 4;
+constexpr int kCountTrip = kCountBlock * kCountItems;
+constexpr int kCountScanCols = 64, kCountScanGroups = 16;         // column scan: 64 tiles x 16 groups of rows per workgroup
+
+__device__ __forceinline__ void tile_count_chunk(const uint32_t* __restrict__ n_dev, int64_t n_cap, int nchunks, int64_t& begin,
+                                                 int64_t& end) {
+    const int64_t n = n_dev ? min((int64_t)*n_dev, n_cap) : n_cap;
+    const int64_t per = (n + nchunks - 1) / nchunks;
+    const int64_t chunk = (per + kCountTrip - 1) / kCountTrip * kCountTrip;
+    begin = min(n, (int64_t)blockIdx.x * chunk);
+    end = min(n, begin + chunk);
+}
+
+__global__ __launch_bounds__(kCountBlock) void tile_count_kernel(const uint32_t* __restrict__ keys, int64_t n_cap,
+                                                                 const uint32_t* __restrict__ n_dev, int tiles,
+                                                                 uint32_t* __restrict__ table /*[gridDim.x + 1][tiles]*/) {
+    extern __shared__ uint32_t count_lds[];                       // [tiles]
+    int64_t begin, end;
+    tile_count_chunk(n_dev, n_cap, (int)gridDim.x, begin, end);
+    for (int t = threadIdx.x; t < tiles; t += kCountBlock) count_lds[t] = 0u;
+    __syncthreads();
+    for (int64_t i0 = begin + (int64_t)threadIdx.x * kCountItems; i0 < end; i0 += kCountTrip) {
+        uint32_t k[kCountItems];
+        if (i0 + kCountItems <= end) {                            // begin is a multiple of the trip: 16-byte aligned
+            const uint4 v = *reinterpret_cast<const uint4*>(keys + i0);
+            k[0] = v.x; k[1] = v.y; k[2] = v.z; k[3] = v.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kCountItems; ++j) k[j] = i0 + j < end ? keys[i0 + j] : kDropKey;
+        }
+#pragma unroll
+        for (int j = 0; j < kCountItems; ++j)
+            if (k[j] < (uint32_t)tiles) atomicAdd(&count_lds[k[j]], 1u);
+    }
+    __syncthreads();
+    uint32_t* row = table + (size_t)blockIdx.x * tiles;
+    for (int t = threadIdx.x; t < tiles; t += kCountBlock) row[t] = count_lds[t];
+}
+
+// Thread (g, c) owns tile blockIdx.x * 64 + c and the rows [g R, (g + 1) R), R = ceil(B / 16): it sums them, the 16 sums of a
+// column are scanned through LDS, and a second walk over the same rows (L2-resident) leaves the exclusive prefixes.  A wave
+// reads 64 consecutive words of a row per step.  Row `nrows` of the table receives the totals.
+__global__ __launch_bounds__(kCountScanCols * kCountScanGroups) void tile_count_scan_kernel(uint32_t* __restrict__ table, int nrows,
+                                                                                            int tiles) {
+    __shared__ uint32_t part[kCountScanGroups][kCountScanCols];
+    const int c = threadIdx.x & (kCountScanCols - 1), g = threadIdx.x / kCountScanCols;
+    const int t = blockIdx.x * kCountScanCols + c;
+    const int per = (nrows + kCountScanGroups - 1) / kCountScanGroups;
+    const int r0 = min(nrows, g * per), r1 = min(nrows, r0 + per);
+    uint32_t sum = 0;
+    if (t < tiles) {
+#pragma unroll 8
+        for (int r = r0; r < r1; ++r) sum += table[(size_t)r * tiles + t];
+    }
+    part[g][c] = sum;
+    __syncthreads();
+    uint32_t run = 0, total = 0;
+#pragma unroll
+    for (int j = 0; j < kCountScanGroups; ++j) {
+        const uint32_t v = part[j][c];
+        if (j < g) run += v;
+        total += v;
+    }
+    if (t >= tiles) return;
+    if (g == 0) table[(size_t)nrows * tiles + t] = total;
+#pragma unroll 8
+    for (int r = r0; r < r1; ++r) {
+        uint32_t* p = table + (size_t)r * tiles + t;
+        const uint32_t v = *p;
+        *p = run;
+        run += v;
+    }
+}
+
+// reverse (tests only): the chunk is walked back to front, so that equal-depth pairs reach their tile in descending id order.
+// out_cap: size of `out`; a position is below the kept total <= n <= out_cap by construction, the test only keeps a table that
+// something else damaged from turning into a stray store.
+__global__ __launch_bounds__(kCountBlock) void tile_place_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                                 int64_t n_cap, const uint32_t* __restrict__ n_dev, int tiles,
+                                                                 const uint32_t* __restrict__ table, uint2* __restrict__ ranges,
+                                                                 uint32_t* __restrict__ kept, uint32_t* __restrict__ out,
+                                                                 uint32_t out_cap, bool reverse) {
+    extern __shared__ uint32_t count_lds[];                       // [tiles] totals -> range starts -> cursors
+    __shared__ uint32_t wave_sums[kCountBlock / kWave];
+    int64_t begin, end;
+    tile_count_chunk(n_dev, n_cap, (int)gridDim.x, begin, end);
+    if (begin >= end && blockIdx.x != 0) return;                  // block-uniform; workgroup 0 writes the ranges whatever n is
+    const uint32_t* totals = table + (size_t)gridDim.x * tiles;
+    const uint32_t* row = table + (size_t)blockIdx.x * tiles;
+    for (int t = threadIdx.x; t < tiles; t += kCountBlock) count_lds[t] = totals[t];
+    __syncthreads();
+    // a thread scans `per` consecutive tiles; per is odd, so the lanes of a wave walk different LDS banks
+    const int per = ((tiles + kCountBlock - 1) / kCountBlock) | 1;
+    const int t0 = min(tiles, (int)threadIdx.x * per), t1 = min(tiles, t0 + per);
+    uint32_t sum = 0;
+    for (int t = t0; t < t1; ++t) sum += count_lds[t];
+    const uint32_t inc = wave_inclusive_scan(sum);
+    if (lane_id() == kWave - 1) wave_sums[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    uint32_t run = inc - sum, total = 0;
+#pragma unroll
+    for (int w = 0; w < kCountBlock / kWave; ++w) {
+        const uint32_t v = wave_sums[w];
+        if (w < (int)(threadIdx.x >> 6)) run += v;
+        total += v;
+    }
+    for (int t = t0; t < t1; ++t) {
+        const uint32_t cnt = count_lds[t];
+        count_lds[t] = run;
+        run += cnt;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        for (int t = threadIdx.x; t < tiles; t += kCountBlock) {
+            const uint32_t cnt = totals[t], start = count_lds[t];
+            ranges[t] = cnt ? make_uint2(start, start + cnt) : make_uint2(0u, 0u);
+        }
+        if (threadIdx.x == 0) *kept = total;
+    }
+    for (int t = threadIdx.x; t < tiles; t += kCountBlock) count_lds[t] += row[t];
+    __syncthreads();
+    for (int64_t j0 = (int64_t)threadIdx.x * kCountItems; j0 < end - begin; j0 += kCountTrip) {
+        uint32_t k[kCountItems], v[kCountItems];
+        if (!reverse && begin + j0 + kCountItems <= end) {
+            const uint4 kk = *reinterpret_cast<const uint4*>(keys + begin + j0);
+            const uint4 vv = *reinterpret_cast<const uint4*>(vals + begin + j0);
+            k[0] = kk.x; k[1] = kk.y; k[2] = kk.z; k[3] = kk.w;
+            v[0] = vv.x; v[1] = vv.y; v[2] = vv.z; v[3] = vv.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kCountItems; ++j) {
+                const int64_t i = reverse ? end - 1 - (j0 + j) : begin + j0 + j;
+                const bool in = j0 + j < end - begin;
+                k[j] = in ? keys[i] : kDropKey;
+                v[j] = in ? vals[i] : 0u;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kCountItems; ++j) {
+            if (k[j] < (uint32_t)tiles) {
+                const uint32_t pos = atomicAdd(&count_lds[k[j]], 1u);
+                if (pos < out_cap) out[pos] = v[j];
+            }
+        }
+    }
+}
+
 // ---- per-tile depth order ----------------------------------------------------------------------------------------------
-// After the stable tile sort a tile's segment of the point list holds its Gaussians in id order (duplicate_kernel emits the
-// pairs in Gaussian-index order).  The segment is permuted in place into (depth key, Gaussian id) order: stable LSD passes on
-// the 32-bit key, so ties keep the id order.  The keys are gathered from the compact per-Gaussian key array preprocess wrote
+// A tile's segment of the point list holds its Gaussians in id order after the stable radix tile sort (duplicate_kernel emits
+// the pairs in Gaussian-index order), in no particular order after the counting sort by tile.  Either way the segment is permuted
+// in place into (depth key, Gaussian id) order: stable LSD passes on the 32-bit key, then a look at the ties ("Ties", below),
+// which re-sorts the few lists whose equal keys did not come out in id order.  The keys are gathered from the compact per-Gaussian key array preprocess wrote
 // (4 B per Gaussian), by the id in the value; the reach flag (bit 31) travels with the value.  Only the bits that differ inside
 // the tile are sorted on: [lowest, highest differing bit] in ceil(span / 8) passes of <= 8 bits.
 // A workgroup takes four tiles (tile_order[4b .. 4b+3]):
@@ -599,7 +765,8 @@ __device__ __forceinline__ void wave_rank(LdsWord* hist, LdsMask* masks, const u
 // Item i of this lane: entry e = first + 64 i of list[0, m), and its key.  All loads first, then all key gathers, with no
 // lane-dependent branch in between: every item's load is in flight at once (a guarded load + gather per item made the compiler
 // wait for each one in turn).  Lanes past the end load the last entry again: a copy of a valid key changes no AND / OR, and the
-// ranking leaves those lanes out.
+// ranking leaves those lanes out.  BY_ID (the id passes of a long list): the sort word is the id itself, nothing is gathered.
+template <bool BY_ID = false>
 __device__ __forceinline__ void load_items(const uint32_t* __restrict__ list, const uint32_t* __restrict__ depth_keys,
                                            uint32_t (&key)[kTileSortItems], uint32_t (&val)[kTileSortItems], int ipl, int first,
                                            int m) {
@@ -611,8 +778,35 @@ __device__ __forceinline__ void load_items(const uint32_t* __restrict__ list, co
 #pragma unroll
     for (int i = 0; i < kTileSortItems; ++i) {
         if (i >= ipl) continue;
-        key[i] = depth_keys[val[i] & kGidMask];
+        key[i] = BY_ID ? val[i] & kGidMask : depth_keys[val[i] & kGidMask];
     }
+}
+
+// AND ^ OR over the wave of the first ipl sort words of every lane (`keep` masks them): the bits that differ in the list
+__device__ __forceinline__ void wave_and_or(const uint32_t (&w)[kTileSortItems], int ipl, uint32_t keep, uint32_t& k_and,
+                                            uint32_t& k_or) {
+    k_and = 0xFFFFFFFFu; k_or = 0u;
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        if (i >= ipl) continue;
+        k_and &= w[i] & keep;
+        k_or |= w[i] & keep;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        k_and &= (uint32_t)__shfl_xor((int)k_and, d, kWave);
+        k_or |= (uint32_t)__shfl_xor((int)k_or, d, kWave);
+    }
+}
+
+// Ties.  The list may arrive in any order (the counting sort by tile is not stable), so after the key passes equal keys need not
+// be in id order.  Every list path then holds the sorted list where entry e can see entry e + 1 and asks one question per entry:
+// same key as the next one AND a larger id?  No such pair anywhere (nearly every tile: ties are a few hundred pairs per frame)
+// and the list is final.  Otherwise the list is sorted by id first -- the same LSD passes, on the differing bits of
+// val & kGidMask -- and the key passes run again: stable, so equal keys now keep the id order.  Linear in the list whatever the
+// input; a list of ONE key skips the key passes on both sides.
+__device__ __forceinline__ bool tie_out_of_order(uint32_t k0, uint32_t v0, uint32_t k1, uint32_t v1) {
+    return k0 == k1 && (v0 & kGidMask) > (v1 & kGidMask);
 }
 
 // Four-wave ranking of one chunk of m entries (caller: a workgroup barrier since the key / value space was last read).
@@ -640,31 +834,14 @@ __device__ __forceinline__ uint32_t tile_sort_rank(TileSortLds& sm, const uint32
     return run_len;
 }
 
-// One wave sorts a list of 2 .. kWaveSortCap entries in its quarter of the key / value space.
-__device__ __forceinline__ void wave_sort_list(TileSortLds& sm, uint32_t* __restrict__ seg, int n,
-                                               const uint32_t* __restrict__ depth_keys) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    LdsWord* wk = lds_words(sm.kv + wave * 2 * kWaveSortCap);
-    LdsWord* wv = wk + kWaveSortCap;
-    LdsWord* hist = lds_words(sm.hist[wave]);
-    LdsMask* masks = wave_masks(sm, wave);
-    uint32_t key[kTileSortItems], val[kTileSortItems], rank[kTileSortItems];
-    const int ipl = (n + kWave - 1) / kWave;
-    load_items(seg, depth_keys, key, val, ipl, lane, n);
-    uint32_t k_and = 0xFFFFFFFFu, k_or = 0u;
-#pragma unroll
-    for (int i = 0; i < kTileSortItems; ++i) {
-        if (i >= ipl) continue;
-        k_and &= key[i];
-        k_or |= key[i];
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        k_and &= (uint32_t)__shfl_xor((int)k_and, d, kWave);
-        k_or |= (uint32_t)__shfl_xor((int)k_or, d, kWave);
-    }
-    const uint32_t diff = (uint32_t)__builtin_amdgcn_readfirstlane((int)(k_and ^ k_or));
-    if (diff == 0u) return;                                      // one key for the whole list: id order is the answer
+// The wave's LSD passes over the bits `diff` of the sort words `sel` (the keys, or the values for the id passes: their ids lie
+// below the reach flag, and diff never holds that bit), key / value pairs moved through the wave's quarter of the LDS space.
+// The sorted list is left there; reload_last: and in the registers again, entry i * 64 + lane in item i.
+__device__ __forceinline__ void wave_lsd_passes(LdsWord* hist, LdsMask* masks, LdsWord* wk, LdsWord* wv,
+                                                const uint32_t (&sel)[kTileSortItems], uint32_t (&key)[kTileSortItems],
+                                                uint32_t (&val)[kTileSortItems], uint32_t (&rank)[kTileSortItems], int ipl,
+                                                int n, uint32_t diff, bool reload_last) {
+    const int lane = threadIdx.x & (kWave - 1);
     const int lo = __builtin_ctz(diff), hi = 31 - __builtin_clz(diff);
     const int npass = (hi - lo + 8) / 8;
     const int per = (hi - lo + npass) / npass;                   // ceil(span / npass) <= 8
@@ -672,7 +849,7 @@ __device__ __forceinline__ void wave_sort_list(TileSortLds& sm, uint32_t* __rest
         const int shift = lo + p * per, bits = min(per, hi + 1 - shift);
         const uint32_t mask = (1u << bits) - 1u;
         wave_rank_clear(hist, masks);
-        wave_rank(hist, masks, key, rank, ipl, 0, n, shift, mask);
+        wave_rank(hist, masks, sel, rank, ipl, 0, n, shift, mask);
         // digit starts: lane l scans digits 4l .. 4l + 3
         uint32_t c[4], sum = 0;
 #pragma unroll
@@ -685,7 +862,7 @@ __device__ __forceinline__ void wave_sort_list(TileSortLds& sm, uint32_t* __rest
 #pragma unroll
         for (int i = 0; i < kTileSortItems; ++i) {
             if (i >= ipl) continue;
-            rank[i] += hist[(key[i] >> shift) & mask];
+            rank[i] += hist[(sel[i] >> shift) & mask];
         }
 #pragma unroll
         for (int i = 0; i < kTileSortItems; ++i) {
@@ -696,7 +873,7 @@ __device__ __forceinline__ void wave_sort_list(TileSortLds& sm, uint32_t* __rest
             }
         }
         __builtin_amdgcn_wave_barrier();
-        if (p + 1 < npass) {
+        if (p + 1 < npass || reload_last) {
 #pragma unroll
             for (int i = 0; i < kTileSortItems; ++i) {
                 if (i >= ipl) continue;
@@ -707,86 +884,131 @@ __device__ __forceinline__ void wave_sort_list(TileSortLds& sm, uint32_t* __rest
             __builtin_amdgcn_wave_barrier();
         }
     }
+}
+
+// One wave sorts a list of 2 .. kWaveSortCap entries in its quarter of the key / value space.
+__device__ __forceinline__ void wave_sort_list(TileSortLds& sm, uint32_t* __restrict__ seg, int n,
+                                               const uint32_t* __restrict__ depth_keys) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    LdsWord* wk = lds_words(sm.kv + wave * 2 * kWaveSortCap);
+    LdsWord* wv = wk + kWaveSortCap;
+    LdsWord* hist = lds_words(sm.hist[wave]);
+    LdsMask* masks = wave_masks(sm, wave);
+    uint32_t key[kTileSortItems], val[kTileSortItems], rank[kTileSortItems];
+    const int ipl = (n + kWave - 1) / kWave;
+    load_items(seg, depth_keys, key, val, ipl, lane, n);
+    uint32_t k_and, k_or;
+    wave_and_or(key, ipl, 0xFFFFFFFFu, k_and, k_or);
+    const uint32_t kdiff = (uint32_t)__builtin_amdgcn_readfirstlane((int)(k_and ^ k_or));
+    if (kdiff != 0u) {
+        wave_lsd_passes(hist, masks, wk, wv, key, key, val, rank, ipl, n, kdiff, false);
+    } else {                                                     // one key for the whole list: only the id order is open
+#pragma unroll
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl) continue;
+            if (i * kWave + lane < n) { wk[i * kWave + lane] = key[i]; wv[i * kWave + lane] = val[i]; }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        if (i >= ipl) continue;
+        const int e = min(i * kWave + lane, n - 2);              // n >= 2; lanes past the end repeat the last pair
+        if (wk[e] == wk[e + 1]) bad |= (wv[e] & kGidMask) > (wv[e + 1] & kGidMask);       // (the values: rarely read)
+    }
+    if (__ballot(bad) != 0ull) {                                 // wave-uniform
+#pragma unroll
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl) continue;
+            const int e = min(i * kWave + lane, n - 1);
+            key[i] = wk[e];
+            val[i] = wv[e];
+        }
+        __builtin_amdgcn_wave_barrier();
+        wave_and_or(val, ipl, kGidMask, k_and, k_or);
+        const uint32_t gdiff = (uint32_t)__builtin_amdgcn_readfirstlane((int)(k_and ^ k_or));      // != 0: the ids of a tile differ
+        if (gdiff != 0u) wave_lsd_passes(hist, masks, wk, wv, val, key, val, rank, ipl, n, gdiff, kdiff != 0u);
+        if (kdiff != 0u) wave_lsd_passes(hist, masks, wk, wv, key, key, val, rank, ipl, n, kdiff, false);
+    } else if (kdiff == 0u) {
+        return;                                                  // already in id order: nothing moved
+    }
     for (int j = lane; j < n; j += kWave) seg[j] = wv[j];
 }
 
-// The whole workgroup sorts one list of more than kWaveSortCap entries.
-__device__ __forceinline__ void block_sort_list(TileSortLds& sm, uint32_t* __restrict__ seg, uint32_t* __restrict__ alt, int n,
-                                                const uint32_t* __restrict__ depth_keys) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool in_lds = n <= kTileSortCap;
-    uint32_t key[kTileSortItems], val[kTileSortItems], rank[kTileSortItems];
-    __syncthreads();                                             // the previous list's use of the LDS is over
-    if (tid < 2) sm.red[tid] = tid == 0 ? 0xFFFFFFFFu : 0u;
-    uint32_t k_and = 0xFFFFFFFFu, k_or = 0u;
-    const int ipl0 = (min(n, kTileSortCap) + kBlock - 1) / kBlock, chunk0 = ipl0 * kWave;
-    if (in_lds) {
-        load_items(seg, depth_keys, key, val, ipl0, wave * chunk0 + lane, n);
-#pragma unroll
-        for (int i = 0; i < kTileSortItems; ++i) {
-            if (i >= ipl0) continue;
-            k_and &= key[i];
-            k_or |= key[i];
-        }
-    } else {
-        for (int j = tid; j < n; j += kBlock) {
-            const uint32_t k = depth_keys[seg[j] & kGidMask];
-            k_and &= k;
-            k_or |= k;
-        }
-    }
+// AND / OR over the workgroup of one word pair per thread, through sm.red; returns AND ^ OR, the OR comes back in all_or
+__device__ __forceinline__ uint32_t block_and_or(TileSortLds& sm, uint32_t k_and, uint32_t k_or, uint32_t& all_or) {
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         k_and &= (uint32_t)__shfl_xor((int)k_and, d, kWave);
         k_or |= (uint32_t)__shfl_xor((int)k_or, d, kWave);
     }
+    __syncthreads();                                             // the last reduction has been read
+    if (tid < 2) sm.red[tid] = tid == 0 ? 0xFFFFFFFFu : 0u;
     __syncthreads();
-    if (lane == 0) { atomicAnd(&sm.red[0], k_and); atomicOr(&sm.red[1], k_or); }
+    if ((tid & (kWave - 1)) == 0) { atomicAnd(&sm.red[0], k_and); atomicOr(&sm.red[1], k_or); }
     __syncthreads();
-    const uint32_t diff = sm.red[0] ^ sm.red[1];
-    if (diff == 0u) return;                                      // block-uniform: one key for the whole list
+    all_or = sm.red[1];
+    return sm.red[0] ^ all_or;
+}
+
+// The workgroup's LSD passes over the bits `diff` of the sort words `sel` (keys, or values for the id passes) of a list of
+// n <= kTileSortCap entries held in registers, entry wave * chunk + 64 i + lane in item i.  The sorted list is left in the
+// key / value space (a barrier behind it); reload_last: and in the registers again.
+__device__ __forceinline__ void block_lsd_passes(TileSortLds& sm, const uint32_t (&sel)[kTileSortItems],
+                                                 uint32_t (&key)[kTileSortItems], uint32_t (&val)[kTileSortItems],
+                                                 uint32_t (&rank)[kTileSortItems], int ipl, int chunk, int n, uint32_t diff,
+                                                 bool reload_last) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lo = __builtin_ctz(diff), hi = 31 - __builtin_clz(diff);
     const int npass = (hi - lo + 8) / 8;
     const int per = (hi - lo + npass) / npass;
     uint32_t* const sk = sm.kv;
     uint32_t* const sv = sm.kv + kTileSortCap;
-
-    if (in_lds) {
-        for (int p = 0; p < npass; ++p) {
-            const int shift = lo + p * per, bits = min(per, hi + 1 - shift);
-            const uint32_t mask = (1u << bits) - 1u;
-            tile_sort_rank(sm, key, rank, ipl0, chunk0, n, shift, mask);
+    for (int p = 0; p < npass; ++p) {
+        const int shift = lo + p * per, bits = min(per, hi + 1 - shift);
+        const uint32_t mask = (1u << bits) - 1u;
+        tile_sort_rank(sm, sel, rank, ipl, chunk, n, shift, mask);
 #pragma unroll
-            for (int i = 0; i < kTileSortItems; ++i) {
-                if (i >= ipl0) continue;
-                const uint32_t d = (key[i] >> shift) & mask;
-                rank[i] += sm.dig_start[d] + sm.hist[wave][d];
-            }
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl) continue;
+            const uint32_t d = (sel[i] >> shift) & mask;
+            rank[i] += sm.dig_start[d] + sm.hist[wave][d];
+        }
 #pragma unroll
-            for (int i = 0; i < kTileSortItems; ++i) {
-                if (i >= ipl0) continue;
-                if (wave * chunk0 + i * kWave + lane < n) {
-                    sk[rank[i]] = key[i];
-                    sv[rank[i]] = val[i];
-                }
-            }
-            __syncthreads();
-            if (p + 1 < npass) {
-#pragma unroll
-                for (int i = 0; i < kTileSortItems; ++i) {
-                    if (i >= ipl0) continue;
-                    const int e = min(wave * chunk0 + i * kWave + lane, n - 1);
-                    key[i] = sk[e];
-                    val[i] = sv[e];
-                }
-                __syncthreads();                                 // read before the next pass' masks overwrite the space
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl) continue;
+            if (wave * chunk + i * kWave + lane < n) {
+                sk[rank[i]] = key[i];
+                sv[rank[i]] = val[i];
             }
         }
-        for (int j = tid; j < n; j += kBlock) seg[j] = sv[j];
-        return;
+        __syncthreads();
+        if (p + 1 < npass || reload_last) {
+#pragma unroll
+            for (int i = 0; i < kTileSortItems; ++i) {
+                if (i >= ipl) continue;
+                const int e = min(wave * chunk + i * kWave + lane, n - 1);
+                key[i] = sk[e];
+                val[i] = sv[e];
+            }
+            __syncthreads();                                     // read before the next pass' masks overwrite the space
+        }
     }
+}
 
-    // long list: every pass streams the list through the chunk ranking, global memory in and out
+// Long list (more than kTileSortCap entries): the LSD passes over the bits `diff` of the sort words stream the list through the
+// chunk ranking, global memory in and out, ping-pong between seg and alt; the sorted list ends in seg, complete for the whole
+// workgroup.  BY_ID: the sort word of a value is its id, otherwise the depth key gathered by it.
+template <bool BY_ID>
+__device__ __forceinline__ void long_lsd_passes(TileSortLds& sm, uint32_t* __restrict__ seg, uint32_t* __restrict__ alt, int n,
+                                                const uint32_t* __restrict__ depth_keys, uint32_t diff) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t key[kTileSortItems], val[kTileSortItems], rank[kTileSortItems];
+    const int lo = __builtin_ctz(diff), hi = 31 - __builtin_clz(diff);
+    const int npass = (hi - lo + 8) / 8;
+    const int per = (hi - lo + npass) / npass;
     for (int p = 0; p < npass; ++p) {
         const int shift = lo + p * per, bits = min(per, hi + 1 - shift);
         const uint32_t mask = (1u << bits) - 1u;
@@ -794,7 +1016,10 @@ __device__ __forceinline__ void block_sort_list(TileSortLds& sm, uint32_t* __res
         uint32_t* __restrict__ dst = (p & 1) ? seg : alt;
         sm.base[tid] = 0u;
         __syncthreads();
-        for (int j = tid; j < n; j += kBlock) atomicAdd(&sm.base[(depth_keys[src[j] & kGidMask] >> shift) & mask], 1u);
+        for (int j = tid; j < n; j += kBlock) {
+            const uint32_t v = src[j] & kGidMask;
+            atomicAdd(&sm.base[((BY_ID ? v : depth_keys[v]) >> shift) & mask], 1u);
+        }
         __syncthreads();
         uint32_t total;
         const uint32_t start = block_exclusive_scan(sm.base[tid], total, sm.scan_sums);
@@ -802,7 +1027,7 @@ __device__ __forceinline__ void block_sort_list(TileSortLds& sm, uint32_t* __res
         for (int c0 = 0; c0 < n; c0 += kTileSortCap) {
             const int m = min(kTileSortCap, n - c0);
             const int ipl = (m + kBlock - 1) / kBlock, chunk = ipl * kWave;
-            load_items(src + c0, depth_keys, key, val, ipl, wave * chunk + lane, m);
+            load_items<BY_ID>(src + c0, depth_keys, key, val, ipl, wave * chunk + lane, m);
             const uint32_t cnt = tile_sort_rank(sm, key, rank, ipl, chunk, m, shift, mask);
 #pragma unroll
             for (int i = 0; i < kTileSortItems; ++i) {
@@ -819,8 +1044,92 @@ __device__ __forceinline__ void block_sort_list(TileSortLds& sm, uint32_t* __res
     }
     if (npass & 1) {
         for (int j = tid; j < n; j += kBlock) seg[j] = alt[j];
+        __syncthreads();
     }
 }
+
+// The whole workgroup sorts one list of more than kWaveSortCap entries.
+__device__ __forceinline__ void block_sort_list(TileSortLds& sm, uint32_t* __restrict__ seg, uint32_t* __restrict__ alt, int n,
+                                                const uint32_t* __restrict__ depth_keys) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t any;
+    __syncthreads();                                             // the previous list's use of the LDS is over
+    if (n <= kTileSortCap) {
+        uint32_t key[kTileSortItems], val[kTileSortItems], rank[kTileSortItems];
+        uint32_t* const sk = sm.kv;
+        uint32_t* const sv = sm.kv + kTileSortCap;
+        const int ipl = (n + kBlock - 1) / kBlock, chunk = ipl * kWave;
+        load_items(seg, depth_keys, key, val, ipl, wave * chunk + lane, n);
+        uint32_t k_and = 0xFFFFFFFFu, k_or = 0u;
+#pragma unroll
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl) continue;
+            k_and &= key[i];
+            k_or |= key[i];
+        }
+        const uint32_t kdiff = block_and_or(sm, k_and, k_or, any);           // block-uniform, as everything decided from it
+        if (kdiff != 0u) {
+            block_lsd_passes(sm, key, key, val, rank, ipl, chunk, n, kdiff, false);
+        } else {                                                 // one key for the whole list: only the id order is open
+#pragma unroll
+            for (int i = 0; i < kTileSortItems; ++i) {
+                if (i >= ipl) continue;
+                const int e = wave * chunk + i * kWave + lane;
+                if (e < n) { sk[e] = key[i]; sv[e] = val[i]; }
+            }
+            __syncthreads();
+        }
+        bool bad = false;
+#pragma unroll
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl) continue;
+            const int e = min(wave * chunk + i * kWave + lane, n - 2);
+            if (sk[e] == sk[e + 1]) bad |= (sv[e] & kGidMask) > (sv[e + 1] & kGidMask);
+        }
+        block_and_or(sm, 0xFFFFFFFFu, bad ? 1u : 0u, any);
+        if (any != 0u) {
+            k_and = 0xFFFFFFFFu; k_or = 0u;
+#pragma unroll
+            for (int i = 0; i < kTileSortItems; ++i) {
+                if (i >= ipl) continue;
+                const int e = min(wave * chunk + i * kWave + lane, n - 1);
+                key[i] = sk[e];
+                val[i] = sv[e];
+                k_and &= val[i] & kGidMask;
+                k_or |= val[i] & kGidMask;
+            }
+            const uint32_t gdiff = block_and_or(sm, k_and, k_or, any);       // (its barriers: the reads above are done)
+            if (gdiff != 0u) block_lsd_passes(sm, val, key, val, rank, ipl, chunk, n, gdiff, kdiff != 0u);
+            if (kdiff != 0u) block_lsd_passes(sm, key, key, val, rank, ipl, chunk, n, kdiff, false);
+        } else if (kdiff == 0u) {
+            return;                                              // already in id order: nothing moved
+        }
+        for (int j = tid; j < n; j += kBlock) seg[j] = sv[j];
+        return;
+    }
+
+    uint32_t k_and = 0xFFFFFFFFu, k_or = 0u;
+    for (int j = tid; j < n; j += kBlock) {
+        const uint32_t k = depth_keys[seg[j] & kGidMask];
+        k_and &= k;
+        k_or |= k;
+    }
+    const uint32_t kdiff = block_and_or(sm, k_and, k_or, any);
+    if (kdiff != 0u) long_lsd_passes<false>(sm, seg, alt, n, depth_keys, kdiff);
+    bool bad = false;
+    k_and = 0xFFFFFFFFu; k_or = 0u;
+    for (int j = tid; j < n; j += kBlock) {
+        const uint32_t v0 = seg[j], v1 = seg[min(j + 1, n - 1)];
+        bad |= tie_out_of_order(depth_keys[v0 & kGidMask], v0, depth_keys[v1 & kGidMask], v1);
+        k_and &= v0 & kGidMask;
+        k_or |= v0 & kGidMask;
+    }
+    const uint32_t gdiff = block_and_or(sm, k_and, k_or | (bad ? 0x80000000u : 0u), any) & kGidMask;     // bit 31: the flag
+    if ((any & 0x80000000u) == 0u || gdiff == 0u) return;
+    long_lsd_passes<true>(sm, seg, alt, n, depth_keys, gdiff);
+    if (kdiff != 0u) long_lsd_passes<false>(sm, seg, alt, n, depth_keys, kdiff);
+}
+
 
 __global__ __launch_bounds__(kBlock) void tile_depth_sort_kernel(const uint2* __restrict__ ranges, int tiles,
                                                                  const uint32_t* __restrict__ tile_order,
@@ -1047,6 +1356,43 @@ int launch_tile_ranges(const uint32_t* tile_keys_sorted, int64_t D, uint2* range
     if (D <= 0) return OGS_OK;
     const int grid = (int)((D + (int64_t)kBlock * kRangeItems - 1) / ((int64_t)kBlock * kRangeItems));
     OGS_LAUNCH(tile_ranges_kernel, dim3(grid), dim3(kBlock), 0, s, tile_keys_sorted, D, n_dev, ranges);
+    OGS_LAUNCH_CHECK(debug, s);
+    return OGS_OK;
+}
+
+// test hooks (ogs_raster_tile_count_debug): a forced chunk count, a reversed walk in tile_place_kernel
+static int g_tile_count_force = 0;
+static bool g_tile_place_reverse = false;
+void tile_count_debug(int force_blocks, int reverse) {
+    if (force_blocks >= 0) g_tile_count_force = force_blocks;
+    if (reverse >= 0) g_tile_place_reverse = reverse != 0;
+}
+int tile_count_trip() { return kCountTrip; }
+
+// B, the number of chunks (= workgroups of tile_count_kernel and tile_place_kernel), or 0: the pass takes the radix sort.
+// The table of (B + 1) x tiles words (B rows of counts, one of totals) lives in a D-word key buffer; one chunk per trip of
+// keys at the most.
+int tile_count_blocks(int64_t D, int64_t tiles) {
+    if (tiles < 1 || tiles > kTileCountMaxTiles || D < 2 * tiles) return 0;
+    const int64_t trips = (D + kCountTrip - 1) / kCountTrip;
+    int64_t B = g_tile_count_force > 0 ? g_tile_count_force : (trips < kTileCountBlocks ? trips : kTileCountBlocks);
+    if (B > D / tiles - 1) B = D / tiles - 1;
+    return (int)B;
+}
+
+int launch_tile_count_binning(const uint32_t* keys, const uint32_t* vals, int64_t D, const uint32_t* n_dev, int B, int64_t tiles,
+                              uint32_t* table, uint2* ranges, uint32_t* kept, uint32_t* point_list, hipStream_t s, int debug) {
+    if (B < 1 || tiles < 1 || tiles > kTileCountMaxTiles || ((int64_t)B + 1) * tiles > D) {
+        set_error("tile_count_binning: B=%d tiles=%lld D=%lld", B, (long long)tiles, (long long)D); return OGS_ERR_INVALID_ARG;
+    }
+    const size_t lds = (size_t)tiles * sizeof(uint32_t);
+    OGS_LAUNCH(tile_count_kernel, dim3(B), dim3(kCountBlock), lds, s, keys, D, n_dev, (int)tiles, table);
+    OGS_LAUNCH_CHECK(debug, s);
+    const int cols = (int)((tiles + kCountScanCols - 1) / kCountScanCols);
+    OGS_LAUNCH(tile_count_scan_kernel, dim3(cols), dim3(kCountScanCols * kCountScanGroups), 0, s, table, B, (int)tiles);
+    OGS_LAUNCH_CHECK(debug, s);
+    OGS_LAUNCH(tile_place_kernel, dim3(B), dim3(kCountBlock), lds, s, keys, vals, D, n_dev, (int)tiles, (const uint32_t*)table,
+               ranges, kept, point_list, (uint32_t)D, g_tile_place_reverse);
     OGS_LAUNCH_CHECK(debug, s);
     return OGS_OK;
 }

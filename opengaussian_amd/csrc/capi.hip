@@ -185,7 +185,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 408; }
+int ogs_version(void) { return 409; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 
@@ -414,39 +414,54 @@ static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipS
         // in the order the full list has them.  args.full_binning != 0 keeps the reference's full list (the dropped pairs stay,
         // flagged in bit 31 of the value, and pack skips them): what ogs_raster_export_binning hands to the parity tests.
         const bool cull = a->full_binning == 0;
-        const bool zero_in_dup = tiles <= (int64_t)a->P;          // one thread per range to clear
-        rc = launch_duplicate(*a, gs, gt, bt.tile_keys[0], vbuf[0], (uint32_t)D, cull, !per_tile, s,
-                              zero_in_dup ? is.ranges : nullptr, zero_in_dup ? (int)tiles : 0);
-        if (rc != OGS_OK) return rc;
-        const bool sweep = radix_onesweep_enabled(D);
-        int shifts[4], nbits[4];
-        for (int p = 0; p < passes; ++p) {
-            shifts[p] = p * per;
-            nbits[p] = (p == passes - 1) ? (bits == 0 ? 1 : bits - shifts[p]) : per;
-        }
-        if (passes == 2 && (bits & 1)) {
-            // odd digit total: the SMALLER digit goes first -- the first pass ranks every pair, the second only those that survive
-            // the drop (13 bits: 6 + 7 instead of 7 + 6, a few us on the scatters)
-            nbits[0] = bits / 2; shifts[1] = nbits[0]; nbits[1] = bits - nbits[0];
-        }
-        if (sweep) {
-            rc = radix_sort_begin(bt.tile_keys[0], D, n_dev, passes, shifts, nbits, bt.sort_tmp, s, a->debug, cull);
+        // The default streaming pass groups the pairs by ONE counting pass on the tile id (binning.hip, "tile count" path): the
+        // per-tile depth sort orders ties by id itself, so nothing before it has to be stable.  duplicate writes its values to
+        // bt.vals, the count table borrows bt.tile_keys[1], the values land in point_list, every range is written (no clear).
+        // Decided from the arguments alone (and the test hook's forced chunk count): 0 chunks = the radix sort below, which
+        // full_binning, grouped passes, the small path, grids past the LDS histogram and lists shorter than two grids keep.
+        const int count_blocks = block_sum_offsets(*a) ? tile_count_blocks(D, tiles) : 0;
+        if (count_blocks > 0) {
+            rc = launch_duplicate(*a, gs, gt, bt.tile_keys[0], bt.vals, (uint32_t)D, true, false, s);
+            if (rc != OGS_OK) return rc;
+            rc = launch_tile_count_binning(bt.tile_keys[0], bt.vals, D, n_dev, count_blocks, tiles, bt.tile_keys[1], is.ranges, bt.kept,
+                                           a->point_list, s, a->debug);
+            if (rc != OGS_OK) return rc;
+        } else {
+            const bool zero_in_dup = tiles <= (int64_t)a->P;          // one thread per range to clear
+            rc = launch_duplicate(*a, gs, gt, bt.tile_keys[0], vbuf[0], (uint32_t)D, cull, !per_tile, s,
+                                  zero_in_dup ? is.ranges : nullptr, zero_in_dup ? (int)tiles : 0);
+            if (rc != OGS_OK) return rc;
+            const bool sweep = radix_onesweep_enabled(D);
+            int shifts[4], nbits[4];
+            for (int p = 0; p < passes; ++p) {
+                shifts[p] = p * per;
+                nbits[p] = (p == passes - 1) ? (bits == 0 ? 1 : bits - shifts[p]) : per;
+            }
+            if (passes == 2 && (bits & 1)) {
+                // odd digit total: the SMALLER digit goes first -- the first pass ranks every pair, the second only those that survive
+                // the drop (13 bits: 6 + 7 instead of 7 + 6, a few us on the scatters)
+                nbits[0] = bits / 2; shifts[1] = nbits[0]; nbits[1] = bits - nbits[0];
+            }
+            if (sweep) {
+                rc = radix_sort_begin(bt.tile_keys[0], D, n_dev, passes, shifts, nbits, bt.sort_tmp, s, a->debug, cull);
+                if (rc != OGS_OK) return rc;
+            }
+            for (int p = 0; p < passes; ++p) {
+                const int in = p & 1, out = in ^ 1;
+                const bool drop = cull && p == 0;
+                // launches stay sized for D (the host does not know the kept count); workgroups past it find nothing to do
+                const uint32_t* n_pass = (cull && p > 0) ? bt.kept : n_dev;
+                rc = sweep ? radix_sort_pass(p, passes, bt.tile_keys[in], vbuf[in], bt.tile_keys[out], vbuf[out], D, shifts[p], nbits[p], bt.sort_tmp, s, a->debug, n_pass, drop, drop ? bt.kept : nullptr)
+                           : radix_pass(bt.tile_keys[in], vbuf[in], bt.tile_keys[out], vbuf[out], D, shifts[p], nbits[p], bt.sort_tmp, s, a->debug, n_pass, drop, drop ? bt.kept : nullptr);
+                if (rc != OGS_OK) return rc;
+            }
+            rc = launch_tile_ranges(bt.tile_keys[passes & 1], D, is.ranges, tiles, s, a->debug, cull ? bt.kept : n_dev, zero_in_dup);
             if (rc != OGS_OK) return rc;
         }
-        for (int p = 0; p < passes; ++p) {
-            const int in = p & 1, out = in ^ 1;
-            const bool drop = cull && p == 0;
-            // launches stay sized for D (the host does not know the kept count); workgroups past it find nothing to do
-            const uint32_t* n_pass = (cull && p > 0) ? bt.kept : n_dev;
-            rc = sweep ? radix_sort_pass(p, passes, bt.tile_keys[in], vbuf[in], bt.tile_keys[out], vbuf[out], D, shifts[p], nbits[p], bt.sort_tmp, s, a->debug, n_pass, drop, drop ? bt.kept : nullptr)
-                       : radix_pass(bt.tile_keys[in], vbuf[in], bt.tile_keys[out], vbuf[out], D, shifts[p], nbits[p], bt.sort_tmp, s, a->debug, n_pass, drop, drop ? bt.kept : nullptr);
-            if (rc != OGS_OK) return rc;
-        }
-        rc = launch_tile_ranges(bt.tile_keys[passes & 1], D, is.ranges, tiles, s, a->debug, cull ? bt.kept : n_dev, zero_in_dup);
-        if (rc != OGS_OK) return rc;
         if (per_tile) {
-            // each tile's list (id order after the stable tile sort) into depth order; heaviest tiles first, the same workgroup
-            // order pack then uses.  Long lists pass through bt.vals, which the tile sort's last pass left free
+            // each tile's list (id order after the stable radix sort, any order after the counting sort) into (depth, id) order;
+            // heaviest tiles first, the same workgroup order pack then uses.  Long lists pass through bt.vals, which the tile
+            // sort's last pass / tile_place_kernel left free
             const uint32_t* order = launch_tile_order(is, tiles, a->P, s, a->debug);
             order_ready = true;
             rc = launch_tile_depth_sort(is.ranges, tiles, order, a->point_list, gt.keys[0], bt.vals, s, a->debug);
@@ -524,6 +539,16 @@ size_t ogs_raster_tiny_max_points(void) { return (size_t)kTinyMaxP; }
 size_t ogs_raster_tile_sort_capacity(int32_t level) {
     return level == 0 ? (size_t)kWaveSortCap : level == 1 ? (size_t)kTileSortCap : 0;
 }
+
+// Tests: the chunk count B the counting sort by tile takes for a list capacity D and a grid of `tiles` (0: such a pass takes the
+// radix sort), after setting the hooks -- force_blocks > 0 forces B (still cut to what the table has room for), 0 gives the
+// choice back to the library, reverse != 0 makes tile_place_kernel walk its chunks back to front; a negative value leaves a
+// hook as it is.  Process-wide: a test restores (0, 0) when it is done.
+int ogs_raster_tile_count_debug(int64_t D, int64_t tiles, int32_t force_blocks, int32_t reverse) {
+    tile_count_debug(force_blocks, reverse);
+    return tile_count_blocks(D, tiles);
+}
+size_t ogs_raster_tile_count_trip(void) { return (size_t)tile_count_trip(); }
 
 static int forward_tiny_impl(const OgsRasterFwdArgs* a_in, void* stream_, bool raw, const float* raw_rest) {
     int rc = validate_fwd(a_in);

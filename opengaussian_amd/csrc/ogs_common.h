@@ -396,9 +396,20 @@ int launch_duplicate(const OgsRasterFwdArgs& a, const GeomState& gs, const GeomT
                      uint2* zero_ranges = nullptr, int n_zero = 0);
 int launch_tile_ranges(const uint32_t* tile_keys_sorted, int64_t D, uint2* ranges, int64_t tiles, hipStream_t s,
                        int debug, const uint32_t* n_dev = nullptr, bool already_zeroed = false);
+// Counting sort by tile (binning.hip, "tile count" path): what replaces the radix tile sort and launch_tile_ranges on a default
+// streaming pass (block_sum_offsets) whose grid fits the LDS histogram.  keys / vals: what duplicate_kernel wrote, n_dev of them
+// (at most D); table: (B + 1) * tiles <= D words of scratch; out: ranges (every tile written, (0, 0) when empty), kept, and point_list
+// with every tile's values in its range, in no particular order -- launch_tile_depth_sort orders ties by id itself.
+constexpr int kTileCountMaxTiles = 12288;      // 48 KB of LDS counters / cursors per workgroup
+constexpr int kTileCountBlocks = 128;          // chunks (workgroups of 1024 threads; DESIGN 3h has the sweep), unless the list or the table is too short for as many
+int tile_count_blocks(int64_t D, int64_t tiles);           // B for this pass; 0: the radix path
+int tile_count_trip();
+void tile_count_debug(int force_blocks, int reverse);      // test hooks; a negative argument leaves its setting as it is
+int launch_tile_count_binning(const uint32_t* keys, const uint32_t* vals, int64_t D, const uint32_t* n_dev, int B, int64_t tiles,
+                              uint32_t* table, uint2* ranges, uint32_t* kept, uint32_t* point_list, hipStream_t s, int debug);
 // Ungrouped streaming passes with P > kSmallMaxP bin without a global depth sort: the geometry phase scans tiles_touched in
-// Gaussian-index order, duplicate walks the Gaussians in that order, and after the tile sort every tile's list (in id order)
-// is sorted by depth on its own (launch_tile_depth_sort).  Grouped passes and the small path keep the depth order of the P
+// Gaussian-index order, duplicate walks the Gaussians in that order, and after the pairs are grouped by tile every tile's list
+// is sorted by (depth, id) on its own (launch_tile_depth_sort: whatever order the list arrives in).  Grouped passes and the small path keep the depth order of the P
 // Gaussians.  Decided from the arguments alone, so that the geometry and the render phase of a pass agree.
 inline bool per_tile_depth_order(const OgsRasterFwdArgs& a) { return a.num_groups <= 1 && a.P > kSmallMaxP; }
 // The default-mode passes among those need no scan over the P Gaussians either: preprocess_kernel and duplicate_kernel cut the
@@ -411,7 +422,7 @@ inline bool block_sum_offsets(const OgsRasterFwdArgs& a) { return per_tile_depth
 // Every tile's segment of point_list into (depth key, id) order in place, keys gathered by id from depth_keys (the 32-bit keys
 // preprocess wrote); workgroup b takes tiles tile_order[4b .. 4b+3] (b.. when NULL).  Lists up to kWaveSortCap entries are sorted by
 // one wave, up to kTileSortCap by the workgroup in LDS; longer ones run their passes through the same positions of `scratch`
-// (D entries, free after the tile sort).
+// (D entries, free after the tile sort).  Equal keys come out in id order whether or not they arrived so.
 constexpr int kTileSortItems = 16;
 constexpr int kTileSortCap = kBlock * kTileSortItems;       // 4096 entries: 32 KB of keys + values, 4 workgroups per CU
 constexpr int kWaveSortCap = kTileSortCap / (kBlock / kWave);   // 1024: lists one wave sorts alone (a quarter of that space)

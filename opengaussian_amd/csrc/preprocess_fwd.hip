@@ -442,8 +442,9 @@ __global__ __launch_bounds__(kSmallMaxP) void small_geometry_kernel(
     if (idx == 0) { num_rendered[0] = total; num_rendered[1] = (uint32_t)P; }     // word 1: entries of the depth order (GeomTmp::visible)
 }
 
-// Emit one (tile id, Gaussian id) pair per touched tile.  Gaussians are visited in INDEX order (order == NULL: the stable
-// tile sort leaves every tile's list in id order, tile_depth_sort_kernel then sorts each list by depth) or, on the grouped and
+// Emit one (tile id, Gaussian id) pair per touched tile.  Gaussians are visited in INDEX order (order == NULL: the pairs are
+// grouped by tile -- a counting pass on the default streaming path, which keeps no order inside a tile, or the stable radix sort,
+// which keeps the id order -- and tile_depth_sort_kernel then sorts each list by (depth, id)) or, on the grouped and
 // small paths, in DEPTH order, so that the stable sort by tile id alone gives the final order.  Either way the result is the
 // reference's (tile<<32 | depth_bits) order with ties broken by Gaussian index (DESIGN.md "binning").
 template <int NV>
@@ -457,8 +458,8 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
                                                            uint32_t* __restrict__ vals, uint32_t capacity,
                                                            const int32_t* __restrict__ group_ids, bool drop_unreachable,
                                                            uint2* __restrict__ zero_ranges, int n_zero) {
-    // drop_unreachable: a pair that cannot reach a pixel of its tile gets the key kDropKey, which the first pass of the tile
-    // sort leaves out (binning.hip) -- the sorted list then holds the reachable pairs only.  Otherwise the pair keeps its tile
+    // drop_unreachable: a pair that cannot reach a pixel of its tile gets the key kDropKey, which the counting pass by tile, or
+    // the first pass of the radix tile sort, leaves out (binning.hip) -- the sorted list then holds the reachable pairs only.  Otherwise the pair keeps its tile
     // key and only its reach flag (bit 31 of the value) tells pack to skip it: the reference's full list (args.full_binning).
     // group_ids != nullptr (grouped pass): the key is the VIRTUAL tile group * tiles + tile
     // capacity: size of tile_keys / vals.  In the deferred render phase it is a cached estimate and the true
