@@ -54,6 +54,34 @@ int ogs_knn_neighbors(int64_t n, const float* points, int32_t K, int32_t exclude
                       size_t tmp_bytes, void* stream);
 
 /*
+ * The K nearest neighbours BETWEEN TWO point sets (csrc/knn_query.hip): an index of the n REFERENCE rows, built once, and any
+ * number of queries against it.  For query row q take every reference row j in [0, n), order by the pair (d2(q, j), j)
+ * ascending -- d2 as above with dx = x_q - x_j, ties on the distance go to the smaller reference row -- and store the first K:
+ * idx [m, K] int32 (reference rows in the caller's reference order), d2 [m, K] fp32, in the caller's query order.  Slots past the
+ * end of the list (n < K) hold idx = -1, d2 = +inf.  There is no exclude_self: the two sets are unrelated.  The result is unique,
+ * so two calls give the same bytes, and it does not depend on where the search of a query starts.
+ *
+ * index: ogs_knn_index_bytes(n) opaque device bytes that ogs_knn_index_build fills and ogs_knn_query only reads: the reference
+ * coordinates sorted by Morton key in boxes of ogs_knn_box_points() points (NaN-padded to whole boxes), the sorted row numbers,
+ * the bounds and the first key of every box, and the bounding box that made the keys.  It is a COPY: writing to `points` after
+ * the build does not change later queries.  Valid for the n it was built with, at any address it is copied to as a whole.
+ * tmp: ogs_knn_index_build_tmp_bytes(n) / ogs_knn_query_tmp_bytes(n, m) bytes of device scratch, free again after the call.
+ *
+ * 1 <= K <= ogs_knn_max_k(), m * K < 2^31, n and m <= INT32_MAX - ogs_knn_box_points().  n == 0 fills idx / d2 with -1 / +inf
+ * (index, queries and tmp are not looked at), m == 0 does nothing, a build with n == 0 does nothing; all three return 0.  Bad
+ * sizes, NULL pointers and an index or tmp that is too small return OGS_ERR_INVALID_ARG.  The size queries return 0 for a size
+ * that needs no buffer or is out of range.  Non-finite coordinates on either side give undefined values, never a wild address.
+ * No read-back, no float atomics, no workgroup waits on another.
+ */
+size_t ogs_knn_index_bytes(int64_t n);
+size_t ogs_knn_index_build_tmp_bytes(int64_t n);
+int ogs_knn_index_build(int64_t n, const float* points, void* index, size_t index_bytes, void* tmp, size_t tmp_bytes,
+                        void* stream);
+size_t ogs_knn_query_tmp_bytes(int64_t n, int64_t m);
+int ogs_knn_query(int64_t n, const void* index, int64_t m, const float* queries, int32_t K, int32_t* idx, float* d2, void* tmp,
+                  size_t tmp_bytes, void* stream);
+
+/*
  * Fixed-degree gather-sum: out[i, c] = the chain acc = fmaf(w[i, k], X[idx[i, k], c], acc) from +0, k ascending, over the slots
  * with 0 <= idx[i, k] < R; other slots are skipped and their w is not read as a value.  idx, w [n, K]; X [R, D] finite;
  * out [n, D], one writer per element, no atomics.  Any D >= 1.  Its adjoint is ogs_knn_aggregate_t (gradient with respect to

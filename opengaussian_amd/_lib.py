@@ -198,6 +198,11 @@ SIGNATURES = {
     "ogs_knn_max_k": (C.c_size_t, []),
     "ogs_knn_neighbors_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "ogs_knn_neighbors": (C.c_int, [C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ogs_knn_index_bytes": (C.c_size_t, [C.c_int64]),
+    "ogs_knn_index_build_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "ogs_knn_index_build": (C.c_int, [C.c_int64, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "ogs_knn_query_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "ogs_knn_query": (C.c_int, [C.c_int64, _vp, C.c_int64, _vp, C.c_int32, _vp, _vp, _vp, C.c_size_t, _vp]),
     "ogs_knn_aggregate": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "ogs_knn_transpose_chunk": (C.c_size_t, []),
     "ogs_knn_transpose_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64]),

@@ -185,7 +185,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 409; }
+int ogs_version(void) { return 410; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 

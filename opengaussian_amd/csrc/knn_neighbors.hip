@@ -17,57 +17,37 @@
 //      A cloud that cannot be pruned (all points coincident: every bound and every K-th value is 0) visits every box: one brute
 //      pass of n^2 pairs, still correct.
 //   The order (d2, id) is total, so the result is unique and does not depend on the order of visits.
+//   Steps 1-4 are knn_sort_into_boxes (defined here, declared in knn_boxes.h) and the kernel of step 5 is knn_search_kernel
+//   (knn_boxes.h): knn_query.hip runs both on two point sets.
 //
 // ogs_knn_aggregate: out[i, c] = sum_k w[i, k] * X[idx[i, k], c] as one fmaf chain per element, k ascending, one thread per
 // output element (per four columns where D and the bases allow 16-byte accesses); no [n, K, D] buffer, no atomics.
 //
 // This file is compiled with -ffp-contract=off: d2 = (dx*dx + dy*dy) + dz*dz, exactly so (the fmaf of the aggregate is explicit).
-#include "ogs_common.h"
+#include "knn_boxes.h"
 #include "../../include/ogs_knn.h"
-
-#include <limits.h>
 
 namespace ogs {
 namespace {
 
-constexpr int kKnnBox = kWave;                          // points per box = queries per wave = candidates per staging round
-constexpr int kKnnMaxK = 32;
-constexpr int kBoundBlocks = 256;                       // workgroups (and partial records) of the bounding-box pass
-constexpr int kNoId = INT_MAX;                          // id of an empty list slot and of a padding point: above every real id
-static_assert(kBoundBlocks <= kBlock, "one thread folds one partial record");
-
 struct NeighborsTmp {
-    float* partial;                                     // [kBoundBlocks][6] min xyz, max xyz
-    uint32_t* keys[2];                                  // [n] Morton keys, ping-pong
-    uint32_t* vals[2];                                  // [n] point ids, ping-pong; vals[0] holds the sorted order at the end
-    float *sx, *sy, *sz;                                // [nbox * kKnnBox] sorted coordinates, NaN past n
-    int32_t* sid;                                       // [nbox * kKnnBox] sorted ids (clamped to [0, n)), kNoId past n
-    float* box;                                         // [6][nbox] min xyz, max xyz of every box
-    void* sort_tmp;
+    KnnSortScratch sort;
+    KnnBoxes boxes;                                     // without first_key / frame: the search starts at the own box
     size_t bytes;
     static NeighborsTmp carve(void* p, int64_t n) {
         Carver c(p);
         NeighborsTmp t{};
         const size_t nbox = (size_t)((n + kKnnBox - 1) / kKnnBox), npad = nbox * kKnnBox;
-        t.partial = c.take<float>((size_t)kBoundBlocks * 6);
-        for (int i = 0; i < 2; ++i) { t.keys[i] = c.take<uint32_t>((size_t)n); t.vals[i] = c.take<uint32_t>((size_t)n); }
-        t.sx = c.take<float>(npad); t.sy = c.take<float>(npad); t.sz = c.take<float>(npad);
-        t.sid = c.take<int32_t>(npad);
-        t.box = c.take<float>(6 * nbox);
-        t.sort_tmp = c.take<char>(sort_tmp_bytes(n));
+        t.sort.partial = c.take<float>((size_t)kBoundBlocks * 6);
+        for (int i = 0; i < 2; ++i) { t.sort.keys[i] = c.take<uint32_t>((size_t)n); t.sort.vals[i] = c.take<uint32_t>((size_t)n); }
+        t.boxes.sx = c.take<float>(npad); t.boxes.sy = c.take<float>(npad); t.boxes.sz = c.take<float>(npad);
+        t.boxes.sid = c.take<int32_t>(npad);
+        t.boxes.box = c.take<float>(6 * nbox);
+        t.sort.sort_tmp = c.take<char>(sort_tmp_bytes(n));
         t.bytes = c.off;
         return t;
     }
 };
-
-__device__ __forceinline__ float wave_min_f(float v) {
-    for (int m = kWave / 2; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, kWave));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-    for (int m = kWave / 2; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, kWave));
-    return v;
-}
 
 // min / max of six values over the workgroup; every thread returns with the result.  fminf / fmaxf drop NaNs.
 __device__ __forceinline__ void block_bounds(float (&lo)[3], float (&hi)[3], float (*sh)[6]) {
@@ -104,23 +84,10 @@ __global__ __launch_bounds__(kBlock) void knn_bounds_kernel(int n, const float* 
     }
 }
 
-__device__ __forceinline__ uint32_t spread10(uint32_t v) {       // abcdefghij -> a00b00c00...j
-    v &= 1023u;
-    v = (v | (v << 16)) & 0x030000FFu;
-    v = (v | (v << 8)) & 0x0300F00Fu;
-    v = (v | (v << 4)) & 0x030C30C3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-
-// cell of a coordinate: always in [0, 1023] -- a NaN or an infinity anywhere in the chain ends as 0 or 1023
-__device__ __forceinline__ uint32_t knn_cell(float v, float lo, float scale) {
-    const float t = (v - lo) * scale;
-    return (uint32_t)(int)fminf(fmaxf(t, 0.f), 1023.f);            // fmaxf(NaN, 0) = 0
-}
-
+// frame (may be nullptr): the folded bounds, min xyz then max xyz, written by the first workgroup
 __global__ __launch_bounds__(kBlock) void knn_keys_kernel(int n, const float* __restrict__ pts, const float* __restrict__ partial,
-                                                          int nparts, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+                                                          int nparts, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                          float* __restrict__ frame) {
     __shared__ float sh[kBlock / kWave][6];
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     if ((int)threadIdx.x < nparts) {
@@ -128,24 +95,25 @@ __global__ __launch_bounds__(kBlock) void knn_keys_kernel(int n, const float* __
         for (int a = 0; a < 3; ++a) { lo[a] = partial[threadIdx.x * 6 + a]; hi[a] = partial[threadIdx.x * 6 + 3 + a]; }
     }
     block_bounds(lo, hi, sh);
+    if (frame && blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { frame[a] = lo[a]; frame[3 + a] = hi[a]; }
+    }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    uint32_t key = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float ext = hi[a] - lo[a];
-        const float scale = ext > 0.f && ext < INFINITY ? 1024.f / ext : 0.f;      // a zero extent: every point in cell 0
-        key |= spread10(knn_cell(pts[(size_t)i * 3 + a], lo[a], scale)) << a;
-    }
-    keys[i] = key;
+    const float p[3] = {pts[(size_t)i * 3], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2]};
+    keys[i] = knn_morton(p, lo, hi);
     vals[i] = (uint32_t)i;
 }
 
-// one wave per box: gather its points into sorted order and fold their bounds
+// one wave per box: gather its points into sorted order and fold their bounds; first_key (may be nullptr) takes the sorted key
+// of the box's first point
 __global__ __launch_bounds__(kBlock) void knn_gather_kernel(int n, int nbox, const float* __restrict__ pts,
-                                                            const uint32_t* __restrict__ order, float* __restrict__ sx,
+                                                            const uint32_t* __restrict__ order,
+                                                            const uint32_t* __restrict__ sorted_keys, float* __restrict__ sx,
                                                             float* __restrict__ sy, float* __restrict__ sz,
-                                                            int32_t* __restrict__ sid, float* __restrict__ box) {
+                                                            int32_t* __restrict__ sid, float* __restrict__ box,
+                                                            uint32_t* __restrict__ first_key) {
     const int lane = threadIdx.x & (kWave - 1);
     const int b = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
     if (b >= nbox) return;
@@ -161,120 +129,8 @@ __global__ __launch_bounds__(kBlock) void knn_gather_kernel(int n, int nbox, con
     if (lane == 0) {
 #pragma unroll
         for (int a = 0; a < 6; ++a) box[(size_t)a * nbox + b] = v[a];
+        if (first_key) first_key[b] = sorted_keys[(size_t)b * kKnnBox];      // b * kKnnBox < n: the box has a point
     }
-}
-
-// (d, j) before (bd, bi) in the order (d2, id)
-__device__ __forceinline__ bool knn_before(float d, int j, float bd, int bi) {
-    return d < bd || (d == bd && j < bi);
-}
-
-// offset o of the outward walk: 0, +1, -1, +2, -2, ...
-__device__ __forceinline__ int knn_delta(int o) { return (o & 1) ? (o + 1) >> 1 : -(o >> 1); }
-
-template <int KT>
-__global__ __launch_bounds__(kKnnBox) void knn_search_kernel(int n, int nbox, int K, int exclude_self,
-                                                             const float* __restrict__ sx, const float* __restrict__ sy,
-                                                             const float* __restrict__ sz, const int32_t* __restrict__ sid,
-                                                             const float* __restrict__ box, int32_t* __restrict__ idx_out,
-                                                             float* __restrict__ d2_out) {
-    __shared__ __attribute__((aligned(16))) float cx[kKnnBox], cy[kKnnBox], cz[kKnnBox];
-    __shared__ __attribute__((aligned(16))) int cid[kKnnBox];
-    const int lane = threadIdx.x, b = blockIdx.x;                  // gridDim.x == nbox
-    const size_t p = (size_t)b * kKnnBox + lane;
-    const float qx = sx[p], qy = sy[p], qz = sz[p];                // NaN in a padding lane: nothing is ever inserted there
-    const int qid = sid[p];
-    const bool valid = qid != kNoId;
-    const int self = exclude_self ? qid : -1;
-    float qlo[3], qhi[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { qlo[a] = box[(size_t)a * nbox + b]; qhi[a] = box[(size_t)(3 + a) * nbox + b]; }
-
-    float bd[KT];
-    int bi[KT];
-#pragma unroll
-    for (int k = 0; k < KT; ++k) { bd[k] = INFINITY; bi[k] = kNoId; }
-
-    float T = INFINITY;                                            // largest K-th d2 among the wave's queries
-    const int reach = max(b, nbox - 1 - b);                        // |delta| of the farthest box
-    for (int o0 = 0; o0 <= 2 * reach; o0 += kKnnBox) {
-        // ---- 64 candidate boxes, one per lane: the lower bound of d2 between the two boxes --------------------------------
-        const int c = b + knn_delta(o0 + lane);
-        const bool inside = c >= 0 && c < nbox;
-        float lb = 0.f;
-        if (inside) {
-            float g[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float clo = box[(size_t)a * nbox + c], chi = box[(size_t)(3 + a) * nbox + c];
-                g[a] = fmaxf(fmaxf(clo - qhi[a], qlo[a] - chi), 0.f);
-            }
-            lb = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
-        }
-        unsigned long long todo = __ballot(inside && !(lb > T));    // (a NaN bound is visited)
-        while (todo) {
-            const int l = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const float lbl = __shfl(lb, l, kWave);
-            if (lbl > T) continue;                                 // T has fallen since the ballot (wave-uniform)
-            const int cb = b + knn_delta(o0 + l);                  // in [0, nbox): lane l was `inside`
-            // ---- stage the box, then every query against its 64 points -----------------------------------------------------
-            const size_t cp = (size_t)cb * kKnnBox + lane;
-            const float lx = sx[cp], ly = sy[cp], lz = sz[cp];
-            const int lid = sid[cp];
-            __syncthreads();                                       // the previous box has been consumed
-            cx[lane] = lx; cy[lane] = ly; cz[lane] = lz; cid[lane] = lid;
-            __syncthreads();
-#pragma unroll 2
-            for (int v = 0; v < kKnnBox; v += 4) {
-                const float4 x4 = *reinterpret_cast<const float4*>(cx + v);
-                const float4 y4 = *reinterpret_cast<const float4*>(cy + v);
-                const float4 z4 = *reinterpret_cast<const float4*>(cz + v);
-                const int4 i4 = *reinterpret_cast<const int4*>(cid + v);
-                const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, ys[4] = {y4.x, y4.y, y4.z, y4.w}, zs[4] = {z4.x, z4.y, z4.z, z4.w};
-                const int js[4] = {i4.x, i4.y, i4.z, i4.w};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float dx = qx - xs[u], dy = qy - ys[u], dz = qz - zs[u];
-                    const float d = (dx * dx + dy * dy) + dz * dz;  // NaN for a padding point: before nothing
-                    const int j = js[u];
-                    if (knn_before(d, j, bd[KT - 1], bi[KT - 1]) && j != self) {
-                        // slot k takes the candidate where it goes before slot k but not before slot k - 1, and the old
-                        // slot k - 1 where it goes before both; static indices only
-#pragma unroll
-                        for (int k = KT - 1; k >= 1; --k) {
-                            const bool here = knn_before(d, j, bd[k], bi[k]), above = knn_before(d, j, bd[k - 1], bi[k - 1]);
-                            bd[k] = here ? (above ? bd[k - 1] : d) : bd[k];
-                            bi[k] = here ? (above ? bi[k - 1] : j) : bi[k];
-                        }
-                        if (knn_before(d, j, bd[0], bi[0])) { bd[0] = d; bi[0] = j; }
-                    }
-                }
-            }
-            float kth = bd[KT - 1];
-#pragma unroll
-            for (int k = 0; k < KT - 1; ++k) kth = k == K - 1 ? bd[k] : kth;
-            T = wave_max_f(valid ? kth : -INFINITY);
-        }
-    }
-    if (!valid) return;
-    const size_t o = (size_t)qid * (size_t)K;                      // qid in [0, n): clamped by the gather
-#pragma unroll
-    for (int k = 0; k < KT; ++k) {
-        if (k < K) {
-            const bool filled = bi[k] != kNoId;
-            idx_out[o + k] = filled ? bi[k] : -1;
-            d2_out[o + k] = filled ? bd[k] : INFINITY;
-        }
-    }
-}
-
-template <int KT>
-int launch_search(int n, int nbox, int K, int exclude_self, const NeighborsTmp& t, int32_t* idx, float* d2, hipStream_t s) {
-    OGS_LAUNCH(knn_search_kernel<KT>, dim3((unsigned)nbox), dim3(kKnnBox), 0, s, n, nbox, K, exclude_self, t.sx, t.sy, t.sz,
-               t.sid, t.box, idx, d2);
-    OGS_LAUNCH_CHECK(0, s);
-    return OGS_OK;
 }
 
 // ---- the gather-sum ---------------------------------------------------------------------------------------------------------
@@ -313,6 +169,28 @@ __global__ __launch_bounds__(kBlock) void knn_aggregate_kernel(int64_t total, in
 }
 
 }  // namespace
+
+int knn_sort_into_boxes(int n, const float* pts, const KnnSortScratch& t, const KnnBoxes& out, hipStream_t s) {
+    const int nbox = (n + kKnnBox - 1) / kKnnBox;
+    const int nparts = min(kBoundBlocks, (n + kBlock - 1) / kBlock);
+    OGS_LAUNCH(knn_bounds_kernel, dim3((unsigned)nparts), dim3(kBlock), 0, s, n, pts, t.partial);
+    OGS_LAUNCH_CHECK(0, s);
+    OGS_LAUNCH(knn_keys_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n, pts, t.partial, nparts,
+               t.keys[0], t.vals[0], out.frame);
+    OGS_LAUNCH_CHECK(0, s);
+    const int shifts[4] = {0, 8, 16, 24}, nbits[4] = {8, 8, 8, 6};  // 30 key bits; an even number of passes ends in [0]
+    for (int pass = 0; pass < 4; ++pass) {
+        const int in = pass & 1, o = in ^ 1;
+        const int rc = radix_pass(t.keys[in], t.vals[in], t.keys[o], t.vals[o], n, shifts[pass], nbits[pass], t.sort_tmp, s, 0);
+        if (rc != OGS_OK) return rc;
+    }
+    const int wpb = kBlock / kWave;
+    OGS_LAUNCH(knn_gather_kernel, dim3((unsigned)((nbox + wpb - 1) / wpb)), dim3(kBlock), 0, s, n, nbox, pts, t.vals[0], t.keys[0],
+               out.sx, out.sy, out.sz, out.sid, out.box, out.first_key);
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
+}
+
 }  // namespace ogs
 
 using namespace ogs;
@@ -342,27 +220,9 @@ int ogs_knn_neighbors(int64_t n, const float* points, int32_t K, int32_t exclude
     }
     hipStream_t s = static_cast<hipStream_t>(stream_);
     const int ni = (int)n, nbox = (ni + kKnnBox - 1) / kKnnBox;
-    const int nparts = min(kBoundBlocks, (ni + kBlock - 1) / kBlock);
-    OGS_LAUNCH(knn_bounds_kernel, dim3((unsigned)nparts), dim3(kBlock), 0, s, ni, points, t.partial);
-    OGS_LAUNCH_CHECK(0, s);
-    OGS_LAUNCH(knn_keys_kernel, dim3((unsigned)((ni + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ni, points, t.partial, nparts,
-               t.keys[0], t.vals[0]);
-    OGS_LAUNCH_CHECK(0, s);
-    const int shifts[4] = {0, 8, 16, 24}, nbits[4] = {8, 8, 8, 6};  // 30 key bits; an even number of passes ends in [0]
-    for (int pass = 0; pass < 4; ++pass) {
-        const int in = pass & 1, out = in ^ 1;
-        const int rc = radix_pass(t.keys[in], t.vals[in], t.keys[out], t.vals[out], n, shifts[pass], nbits[pass], t.sort_tmp, s, 0);
-        if (rc != OGS_OK) return rc;
-    }
-    const int wpb = kBlock / kWave;
-    OGS_LAUNCH(knn_gather_kernel, dim3((unsigned)((nbox + wpb - 1) / wpb)), dim3(kBlock), 0, s, ni, nbox, points, t.vals[0], t.sx,
-               t.sy, t.sz, t.sid, t.box);
-    OGS_LAUNCH_CHECK(0, s);
-    const int ex = exclude_self ? 1 : 0;
-    if (K <= 4) return launch_search<4>(ni, nbox, K, ex, t, idx, d2, s);
-    if (K <= 8) return launch_search<8>(ni, nbox, K, ex, t, idx, d2, s);
-    if (K <= 16) return launch_search<16>(ni, nbox, K, ex, t, idx, d2, s);
-    return launch_search<32>(ni, nbox, K, ex, t, idx, d2, s);
+    const int rc = knn_sort_into_boxes(ni, points, t.sort, t.boxes, s);
+    if (rc != OGS_OK) return rc;
+    return knn_launch_search(nbox, nbox, K, exclude_self ? 1 : 0, t.boxes, nullptr, t.boxes, idx, d2, s);
 }
 
 int ogs_knn_aggregate(int64_t n, int32_t K, int64_t R, int32_t D, const int32_t* idx, const float* w, const float* X, float* out,

@@ -7,6 +7,9 @@
                   K smallest and of their squares.
 ``neighbors``     the k <= 32 nearest neighbours themselves, indices and distances, by a sorted box search that scales to
                   millions of rows; ``distCUDA2`` takes it for large clouds.
+``Index`` /       the same search BETWEEN TWO point sets: an index of a reference set, built once, and the k <= 32 nearest
+``query``         reference rows of every row of any other set, wherever it lies; ``query.transfer_labels`` /
+                  ``transfer_features`` carry per-point results across on it.
 ``aggregate``     the fixed-degree gather-sum over such an index table (the step of a diffusion over the kNN graph).
 ``reverse_edges`` the reverse-edge lists of an index table: per target row, the slots that point at it.
 ``gather_sum``    ``aggregate`` with a backward: the gradient of the table through the reverse lists, that of the weights as
@@ -176,6 +179,60 @@ def neighbors(points: torch.Tensor, k: int, exclude_self: bool = True):
     check(L.ogs_knn_neighbors(n, ptr(pts), k, int(bool(exclude_self)), ptr(idx), ptr(d2), ptr(tmp), nbytes, _stream()),
           "ogs_knn_neighbors")
     return idx, d2
+
+
+def _points_arg(points, name):
+    _need_gpu(points, name)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{name} must be [n, 3], got {tuple(points.shape)}")
+    return points.detach().to(torch.float32).contiguous()
+
+
+class Index:
+    """The search index of one REFERENCE point set (``ogs_knn_index_build``), built once and queried any number of times with
+    other point sets: the reference's coordinates sorted by Morton key in boxes of 64 points, their row numbers, the bounds and
+    the first key of every box -- about 16.5 bytes per point, a copy, so ``points`` may change or go afterwards.  ``.n`` rows on
+    ``.device``.  Nothing is read back from the device."""
+
+    def __init__(self, points: torch.Tensor):
+        pts = _points_arg(points, "points")
+        self.n, self.device = pts.shape[0], pts.device
+        L = _lib.lib()
+        self._bytes = int(L.ogs_knn_index_bytes(self.n))
+        self._buf = _tmp(self._bytes, self.device)
+        nbytes = int(L.ogs_knn_index_build_tmp_bytes(self.n))
+        tmp = _tmp(nbytes, self.device)
+        check(L.ogs_knn_index_build(self.n, ptr(pts), ptr(self._buf), self._bytes, ptr(tmp), nbytes, _stream()),
+              "ogs_knn_index_build")
+
+    def query(self, queries: torch.Tensor, k: int):
+        """The k nearest reference rows of every query row: (idx int32 [m, k], d2 fp32 [m, k]), exact (``ogs_knn_query``: the
+        queries are grouped by a Morton sort of their own, every group of 64 starts at the reference box its centre falls
+        into, and the search of ``neighbors`` runs from there).
+
+        Row q lists the reference rows j by ascending (d2, j): d2 is the fp32 ``(dx*dx + dy*dy) + dz*dz`` with
+        ``dx = x_q - x_j``, equal distances go to the smaller reference row, so the result is unique and two calls give the
+        same bytes.  Slots past the end of the list (fewer than k reference rows) hold idx = -1, d2 = +inf.
+        1 <= k <= 32 and m * k < 2^31.  The queries may lie anywhere, also wholly outside the reference's bounding box."""
+        q = _points_arg(queries, "queries")
+        if q.device != self.device:
+            raise ValueError(f"queries live on {q.device}, the index on {self.device}")
+        m, k = q.shape[0], int(k)
+        idx = torch.empty((m, k), dtype=torch.int32, device=self.device)
+        d2 = torch.empty((m, k), dtype=torch.float32, device=self.device)
+        L = _lib.lib()
+        nbytes = int(L.ogs_knn_query_tmp_bytes(self.n, m))
+        tmp = _tmp(nbytes, self.device)
+        check(L.ogs_knn_query(self.n, ptr(self._buf), m, ptr(q), k, ptr(idx), ptr(d2), ptr(tmp), nbytes, _stream()),
+              "ogs_knn_query")
+        return idx, d2
+
+
+def query(points: torch.Tensor, queries: torch.Tensor, k: int):
+    """``Index(points).query(queries, k)``: the k nearest rows of ``points`` [n, 3] for every row of ``queries`` [m, 3], in one
+    shot.  Keep the ``Index`` instead when the same reference set is asked more than once."""
+    _points_arg(queries, "queries")                                 # both sets are checked before anything is built
+    return Index(points).query(queries, k)
 
 
 @torch.no_grad()

@@ -24,6 +24,8 @@
 ``diffuse`` /               the same graph inside a training loss: the diffusion with a backward (``knn.gather_sum`` per step) and
 ``neighbor_smoothness``     the loss sum w |F_i - F_j|^2 fused forward and backward; gradients through the reverse-edge lists
                             (``knn.reverse_edges``), no float atomics
+``transfer_labels`` /       per-point results across a CHANGE of the point set (densified, pruned, another checkpoint, a scan): labels by
+``transfer_features``       nearest-neighbour vote, feature rows by weighted mean, over exact kNN between the two sets (``knn.Index``)
 ``build_codebook``          lifted features -> leaves: wide k-means (``kmeans.wide_lloyd``, D up to 1024) into the ``leaf_ind`` /
                             ``leaf_lang_feat`` / ``occu_count`` the text queries above take -- no trained instance features needed
 ``click_features`` /        the reference's own click route (scripts/render_by_click.py:35-66,138-166), batched over clicks, in
@@ -893,6 +895,12 @@ def neighbor_weights(d2, idx, valid=None, bandwidth=None):
     ``valid`` (bool [R], indexed by idx), ``valid[idx]`` holds.  ``h_i`` is the mean d2 of the row's counting slots (a row
     whose counting slots are all at distance 0 weighs them equally), or ``bandwidth`` (a number or [n]) where given.  Rows
     without a counting slot stay all-zero.  Plain torch where the table lives, computed in fp64."""
+    w, total = _raw_neighbor_weights(d2, idx, valid, bandwidth)
+    return (w / torch.where(total > 0, total, torch.ones_like(total))).to(torch.float32)
+
+
+def _raw_neighbor_weights(d2, idx, valid, bandwidth):
+    """(w fp64 [n, K] before the division, their row sums fp64 [n, 1]) of ``neighbor_weights``"""
     if d2.shape != idx.shape or d2.dim() != 2:
         raise ValueError(f"d2 and idx must be [n, K] alike, got {tuple(d2.shape)} and {tuple(idx.shape)}")
     ok = (idx >= 0) & torch.isfinite(d2)
@@ -905,8 +913,108 @@ def neighbor_weights(d2, idx, valid=None, bandwidth=None):
         h = torch.as_tensor(bandwidth, dtype=torch.float64, device=d2.device).expand(d2.shape[0])
     arg = torch.where(h[:, None] > 0, d / (2.0 * torch.where(h > 0, h, torch.ones_like(h)))[:, None], torch.zeros_like(d))
     w = torch.where(ok, torch.exp(-arg), torch.zeros_like(d))
-    total = w.sum(dim=1, keepdim=True)
-    return (w / torch.where(total > 0, total, torch.ones_like(total))).to(torch.float32)
+    return w, w.sum(dim=1, keepdim=True)
+
+
+LABEL_TABLE_BYTES = 256 << 20          # budget of the [rows, num_labels] fp32 table of one chunk of transfer_labels
+
+
+def _cross_lists(src_xyz, dst_xyz, k, max_dist, index):
+    """(idx, d2) of the k nearest source rows of every destination row, idx = -1 on the slots farther than max_dist"""
+    if src_xyz.dim() != 2 or src_xyz.shape[1] != 3 or dst_xyz.dim() != 2 or dst_xyz.shape[1] != 3:
+        raise ValueError(f"src_xyz and dst_xyz must be [n, 3] and [m, 3], got {tuple(src_xyz.shape)} and {tuple(dst_xyz.shape)}")
+    if int(k) < 1:
+        raise ValueError(f"k must be at least 1, got {k}")
+    if max_dist is not None and not float(max_dist) >= 0:
+        raise ValueError(f"max_dist must be a distance >= 0 or None, got {max_dist}")
+    if index is None:
+        index = _knn.Index(src_xyz)
+    elif index.n != src_xyz.shape[0]:
+        raise ValueError(f"index was built on {index.n} rows, src_xyz has {src_xyz.shape[0]}")
+    idx, d2 = index.query(dst_xyz, int(k))
+    if max_dist is not None:
+        idx = torch.where(d2 <= float(max_dist) ** 2, idx, torch.full_like(idx, -1))
+    return idx, d2
+
+
+def transfer_labels(src_xyz, src_labels, dst_xyz, k=1, num_labels=None, max_dist=None, ignore=None, index=None):
+    """Labels of one point set carried onto another by exact nearest neighbours (``knn.Index.query``), int64 [m]: every row of
+    ``dst_xyz`` [m, 3] takes a label from its ``k`` nearest rows of ``src_xyz`` [n, 3] with labels ``src_labels`` [n].
+
+    ``k = 1``: the label of the nearest source row.  ``k > 1``: the label with the largest sum of ``neighbor_weights`` over the
+    k neighbours, the LOWEST label where two sums are equal.  A neighbour counts when it lies within ``max_dist`` (None: any
+    distance; ``d2 <= max_dist ** 2`` on the fp32 d2), its row is not marked in ``ignore`` (bool [n]) and its label lies in
+    ``[0, num_labels)``; a row without a counting neighbour gets -1.  ``num_labels=None`` takes ``src_labels.max() + 1``, the
+    one value this function reads back.  ``index``: a ``knn.Index`` of ``src_xyz`` to search instead of building one.
+
+    The sums of a chunk of rows live in a [rows, num_labels] fp32 table of at most ``LABEL_TABLE_BYTES``, filled slot by slot
+    (one writer per element and slot: the same bytes every run).  The ScanNet use: ``classify_points`` on a densified model,
+    this onto the GT vertices, then ``segmentation_metrics`` -- no ``--frozen_init_pts`` needed."""
+    if src_labels.dim() != 1 or src_labels.shape[0] != src_xyz.shape[0]:
+        raise ValueError(f"src_labels must be [{src_xyz.shape[0]}], got {tuple(src_labels.shape)}")
+    if ignore is not None and ignore.shape != src_labels.shape:
+        raise ValueError(f"ignore must be [{src_xyz.shape[0]}] like src_labels, got {tuple(ignore.shape)}")
+    if num_labels is not None and int(num_labels) < 1:
+        raise ValueError(f"num_labels must be at least 1, got {num_labels}")
+    idx, d2 = _cross_lists(src_xyz, dst_xyz, k, max_dist, index)
+    dev, m, k = idx.device, idx.shape[0], idx.shape[1]
+    lab = src_labels.detach().to(dev).to(torch.int64)
+    if num_labels is None:
+        num_labels = int(lab.max()) + 1 if lab.numel() else 1
+    num_labels = max(int(num_labels), 1)
+    good = (lab >= 0) & (lab < num_labels)
+    if ignore is not None:
+        good &= ~ignore.to(dev).to(torch.bool)
+    if lab.numel() == 0:                                            # no source row: every list is empty
+        return torch.full((m,), -1, dtype=torch.int64, device=dev)
+    slot_lab = lab[idx.clamp_min(0).to(torch.int64)]                # [m, k]; looked at only where the slot counts
+    counts = (idx >= 0) & good[idx.clamp_min(0).to(torch.int64)]
+    none = torch.full((m,), -1, dtype=torch.int64, device=dev)
+    if k == 1:
+        return torch.where(counts[:, 0], slot_lab[:, 0], none)
+    w = neighbor_weights(d2, torch.where(counts, idx, torch.full_like(idx, -1)))
+    out = torch.empty(m, dtype=torch.int64, device=dev)
+    rows = max(1, LABEL_TABLE_BYTES // (4 * num_labels))
+    every_label = torch.arange(num_labels, device=dev)
+    for r0 in range(0, m, rows):
+        r1 = min(m, r0 + rows)
+        table = torch.zeros((r1 - r0, num_labels), dtype=torch.float32, device=dev)
+        row = torch.arange(r1 - r0, device=dev)
+        for s in range(k):                                          # one slot at a time: no two writers of an element
+            col = torch.where(counts[r0:r1, s], slot_lab[r0:r1, s], torch.zeros_like(row))
+            table[row, col] += w[r0:r1, s]                          # a slot that does not count weighs 0
+        best = table.max(dim=1, keepdim=True).values
+        out[r0:r1] = torch.where(table == best, every_label, num_labels).min(dim=1).values
+    return torch.where(counts.any(dim=1), out, none)
+
+
+def transfer_features(src_xyz, src_feat, dst_xyz, k=8, max_dist=None, valid=None, bandwidth=None, index=None):
+    """Per-point rows of one point set carried onto another: ``(feat fp32 [m, D], weight fp32 [m])``, every row of ``dst_xyz``
+    [m, 3] the ``neighbor_weights`` mean of ``src_feat`` [n, D] over its ``k`` exact nearest rows of ``src_xyz`` [n, 3]
+    (``knn.Index.query``, then one ``knn.aggregate`` launch with R = n; no [m, k, D] buffer).
+
+    A neighbour counts when it lies within ``max_dist`` (None: any distance) and, with ``valid`` (bool [n]), ``valid`` holds for
+    its row; ``bandwidth`` as in ``neighbor_weights``.  ``weight`` is the sum of the weights BEFORE the rows are normalised: 0
+    where no neighbour counts, and the feature row is then all zero.  When ``src_feat`` requires grad the sum is
+    ``knn.gather_sum`` over ``knn.reverse_edges(idx, num_rows=n)``: differentiable in the features, gradients without float
+    atomics.  ``index``: a ``knn.Index`` of ``src_xyz`` to search instead of building one.  Use: lifted features, codebook
+    rows or ``_ins_feat`` across ``densify_and_prune``, onto another checkpoint, or onto a scan for display."""
+    if src_feat.dim() != 2 or src_feat.shape[0] != src_xyz.shape[0] or src_feat.shape[1] < 1:
+        raise ValueError(f"src_feat must be [{src_xyz.shape[0]}, D], got {tuple(src_feat.shape)}")
+    if valid is not None and valid.shape != (src_xyz.shape[0],):
+        raise ValueError(f"valid must be [{src_xyz.shape[0]}], got {tuple(valid.shape)}")
+    idx, d2 = _cross_lists(src_xyz, dst_xyz, k, max_dist, index)
+    n, m = src_feat.shape[0], idx.shape[0]
+    if n == 0:
+        return (torch.zeros((m, src_feat.shape[1]), dtype=torch.float32, device=idx.device),
+                torch.zeros(m, dtype=torch.float32, device=idx.device))
+    w, total = _raw_neighbor_weights(d2, idx, None if valid is None else valid.to(idx.device), bandwidth)
+    w = (w / torch.where(total > 0, total, torch.ones_like(total))).to(torch.float32)
+    if src_feat.requires_grad:
+        feat = _knn.gather_sum(src_feat, idx, w)                    # reverse_edges(idx, num_rows=n), built in the backward
+    else:
+        feat = _knn.aggregate(src_feat, idx, w)
+    return feat, total[:, 0].to(torch.float32)
 
 
 def diffuse_features(X, idx, w, steps=1, rate=1.0, fixed=None):
