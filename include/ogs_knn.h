@@ -155,6 +155,37 @@ int ogs_knn_smoothness_bwd(int64_t n, int32_t K, int32_t D, const int32_t* idx, 
                            const int32_t* slots, const float* scale, float* gF, float* gw, void* tmp, size_t tmp_bytes,
                            void* stream);
 
+/*
+ * ---- which rows hang together (csrc/knn_components.hip) ---------------------------------------------------------------------------
+ * Connected components of the graph an index table idx [n, K] spans (with d2 [n, K] as ogs_knn_neighbors writes them), under an
+ * optional distance threshold and an optional same-label rule; a lock-free union-find, "hook the larger root under the smaller".
+ *
+ * Row i is ACTIVE when labels == NULL or labels[i] >= 0.  Slot (i, k) with j = idx[i, k] is an EDGE between i and j when all of
+ *   0 <= j < n;
+ *   both rows are active;
+ *   labels == NULL or labels[i] == labels[j];
+ *   d2 == NULL, or max_d2 == NULL, or d2[i, k] <= *max_d2 -- the fp32 compare as written: a NaN on either side gives no edge,
+ *   equality gives an edge (max_d2 is a DEVICE scalar)
+ * hold.  Edges are UNDIRECTED: i listing j connects them whether or not j lists i.  A self slot (j == i) is a no-op.  The
+ * components are those of that graph over the active rows, numbered 0 .. C - 1 by ascending smallest member row:
+ *   comp [n]   the number of the row's component, -1 for an inactive row
+ *   count [1]  C
+ *   sizes [n]  sizes[c] = the member count for c < C, 0 for C <= c < n
+ *   first [n]  (may be NULL) first[c] = the smallest member row for c < C, -1 beyond
+ * Every output element is written by every call.  The result is unique: two calls give the same bytes, and a permutation of the
+ * slots within a row changes nothing.
+ *
+ * 1 <= K, n * K < 2^31; n == 0 writes count[0] = 0 and returns 0 (nothing else is looked at).  Bad sizes, NULL required pointers
+ * (idx, comp, sizes, count, tmp) and a tmp below ogs_knn_components_tmp_bytes(n) bytes return OGS_ERR_INVALID_ARG; the size query
+ * returns 0 for a size that needs no buffer or is out of range.  No read-back, no float atomics (the only read-modify-write is the
+ * integer compare-and-swap of the hook; the sizes are the lengths of the components' sorted member lists), no workgroup waits on another.  No content of idx, d2 or labels makes a wild address: a slot outside [0, n) is skipped before it
+ * indexes anything.  Every walk and retry loop of the union-find is bounded by a count taken from n; a thread that reaches the bound
+ * sets the sticky status word (ogs_check_async_status() then returns OGS_ERR_DEVICE) and leaves its loop.
+ */
+size_t ogs_knn_components_tmp_bytes(int64_t n);
+int ogs_knn_components(int64_t n, int32_t K, const int32_t* idx, const float* d2, const float* max_d2, const int32_t* labels,
+                       int32_t* comp, int32_t* sizes, int32_t* first, int32_t* count, void* tmp, size_t tmp_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

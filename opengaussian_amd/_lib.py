@@ -216,6 +216,8 @@ SIGNATURES = {
     "ogs_knn_smoothness_bwd_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "ogs_knn_smoothness_bwd": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          C.c_size_t, _vp]),
+    "ogs_knn_components_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "ogs_knn_components": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "ogs_kmeans_wide_row_tile": (C.c_size_t, []),
     "ogs_kmeans_wide_centre_tile": (C.c_size_t, []),
     "ogs_kmeans_wide_dim_step": (C.c_size_t, []),

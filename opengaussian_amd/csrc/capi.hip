@@ -81,10 +81,11 @@ int take_async_status() {
 int check_async_status(const char* where) {
     const int st = take_async_status();
     if (st == 0) return OGS_OK;
-    set_error("%s: a kernel of an earlier launch reported status 0x%x%s%s -- the results of the passes since the last check "
+    set_error("%s: a kernel of an earlier launch reported status 0x%x%s%s%s -- the results of the passes since the last check "
               "are not valid", where, st,
               (st & (int)kAsyncRadixSpin) ? " (one-launch radix pass: a look-back wait exceeded its bound)" : "",
-              (st & (int)kAsyncSplitOverflow) ? " (query split: the scatter met more rows than its capacity)" : "");
+              (st & (int)kAsyncSplitOverflow) ? " (query split: the scatter met more rows than its capacity)" : "",
+              (st & (int)kAsyncComponentsWalk) ? " (knn components: a union-find walk exceeded the bound n sets for it)" : "");
     return OGS_ERR_DEVICE;
 }
 

@@ -46,9 +46,11 @@ void set_error(const char* fmt, ...);
 // (and clears) the word wherever it already synchronises with the stream: after the num_rendered read-back of a forward,
 // at the entry of the next forward / backward, in the self-test hooks; ogs_check_async_status() turns it into
 // OGS_ERR_DEVICE.  Producers: the bounded look-back spin of radix_onesweep_kernel (binning.hip), and the scatter of the query
-// split (query.hip) when a row's position lies at or beyond the capacity it was given.
+// split (query.hip) when a row's position lies at or beyond the capacity it was given, and the walks and retry loops of the
+// union-find (knn_components.hip) when one passes the bound that n sets for it.
 constexpr uint32_t kAsyncRadixSpin = 1u;
 constexpr uint32_t kAsyncSplitOverflow = 2u;
+constexpr uint32_t kAsyncComponentsWalk = 4u;
 uint32_t* async_status_word();                   // device-usable pointer (nullptr + set_error when the allocation fails)
 int take_async_status();                         // read and clear; 0 = nothing happened (also when never allocated)
 int check_async_status(const char* where);       // OGS_OK, or OGS_ERR_DEVICE with the message set

@@ -12,6 +12,8 @@
                   ``transfer_features`` carry per-point results across on it.
 ``aggregate``     the fixed-degree gather-sum over such an index table (the step of a diffusion over the kNN graph).
 ``reverse_edges`` the reverse-edge lists of an index table: per target row, the slots that point at it.
+``components``    the connected components of an index table under a distance threshold and a same-label rule: a lock-free
+                  union-find, numbered by smallest member, the same bytes every run.
 ``gather_sum``    ``aggregate`` with a backward: the gradient of the table through the reverse lists, that of the weights as
                   per-edge dots; no float atomics, so the gradients are the same bytes every run.
 
@@ -297,6 +299,59 @@ def reverse_edges(idx: torch.Tensor, num_rows=None):
     tmp = _tmp(nbytes, idx.device)
     check(L.ogs_knn_transpose(n, K, R, ptr(ic), ptr(begin), ptr(slots), ptr(tmp), nbytes, _stream()), "ogs_knn_transpose")
     return begin, slots
+
+
+@torch.no_grad()
+def components(idx: torch.Tensor, d2=None, max_d2=None, labels=None):
+    """Connected components of the graph an index table spans (``ogs_knn_components``): ``(comp, count, sizes, first)``, int32
+    [n], [1], [n], [n], all on the device.
+
+    idx int32 [n, K] as ``neighbors`` returns it.  Row i is active unless ``labels`` [n] holds a negative value for it.  Slot
+    (i, k) with j = idx[i, k] joins i and j when ``0 <= j < n``, both rows are active, ``labels`` (where given) are equal, and --
+    with both ``d2`` fp32 [n, K] and ``max_d2`` given -- ``d2[i, k] <= max_d2`` in fp32 (a NaN on either side joins nothing).
+    ``max_d2`` is a SQUARED distance, a float or a 0-dim / one-element device tensor.  Edges are undirected: one row listing
+    the other is enough.  Components are numbered by ascending smallest member row: ``comp[i]`` is the row's component (-1:
+    inactive), ``count[0]`` their number C, ``sizes[c]`` / ``first[c]`` the member count and smallest member of c < C (0 / -1
+    beyond).  The result is unique -- the same bytes every run, whatever the order of the slots within a row -- and nothing is
+    read back: ``count`` stays on the device.
+
+    This is NOT DBSCAN: a table with K <= 32 columns does not hold every neighbour within a radius, so two rows closer than
+    ``max_d2`` whose lists are full of nearer rows are joined only through those."""
+    _need_gpu(idx, "idx")
+    if idx.dim() != 2 or idx.shape[1] < 1:
+        raise ValueError(f"idx must be [n, K] with K >= 1, got {tuple(idx.shape)}")
+    n, K = idx.shape
+    dev = idx.device
+    ic = idx.to(torch.int32).contiguous()
+    dc = mc = lc = None
+    if d2 is not None:
+        _need_gpu(d2, "d2")
+        if d2.shape != idx.shape:
+            raise ValueError(f"d2 must be [{n}, {K}] like idx, got {tuple(d2.shape)}")
+        dc = d2.detach().to(torch.float32).contiguous()
+    if max_d2 is not None:
+        if isinstance(max_d2, torch.Tensor):
+            _need_gpu(max_d2, "max_d2")
+            if max_d2.numel() != 1:
+                raise ValueError(f"max_d2 must be a number or a one-element tensor, got {tuple(max_d2.shape)}")
+            mc = max_d2.detach().to(torch.float32).reshape(1).contiguous()
+        else:
+            mc = torch.full((1,), float(max_d2), dtype=torch.float32, device=dev)
+    if labels is not None:
+        _need_gpu(labels, "labels")
+        if labels.shape != (n,):
+            raise ValueError(f"labels must be [{n}], got {tuple(labels.shape)}")
+        lc = labels.detach().to(torch.int32).contiguous()
+    comp = torch.empty(n, dtype=torch.int32, device=dev)
+    sizes = torch.empty(n, dtype=torch.int32, device=dev)
+    first = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    nbytes = int(L.ogs_knn_components_tmp_bytes(n))
+    tmp = _tmp(nbytes, dev)
+    check(L.ogs_knn_components(n, K, ptr(ic), ptr(dc), ptr(mc), ptr(lc), ptr(comp), ptr(sizes), ptr(first), ptr(count), ptr(tmp),
+                               nbytes, _stream()), "ogs_knn_components")
+    return comp, count, sizes, first
 
 
 class LazyReverse:

@@ -26,6 +26,8 @@
                             (``knn.reverse_edges``), no float atomics
 ``transfer_labels`` /       per-point results across a CHANGE of the point set (densified, pruned, another checkpoint, a scan): labels by
 ``transfer_features``       nearest-neighbour vote, feature rows by weighted mean, over exact kNN between the two sets (``knn.Index``)
+``segment_instances`` /     which points hang together: the connected pieces of every class as instances, and the keep-mask of every
+``component_filter``        group's connected bulk (``knn.components``: a lock-free union-find over the kNN table, one call for all)
 ``build_codebook``          lifted features -> leaves: wide k-means (``kmeans.wide_lloyd``, D up to 1024) into the ``leaf_ind`` /
                             ``leaf_lang_feat`` / ``occu_count`` the text queries above take -- no trained instance features needed
 ``click_features`` /        the reference's own click route (scripts/render_by_click.py:35-66,138-166), batched over clicks, in
@@ -1218,3 +1220,120 @@ def select_leaves_by_masks(views, pc, pipe, bg, iteration, prompt_images, num_pr
     leaf's weight, one pixel's worth of weight) are conveniences, not tuned values."""
     table = lift_labels(views, pc, pipe, bg, iteration, prompt_images, num_prompts, rows=leaf_ind, num_rows=num_leaves)
     return leaves_from_votes(table, min_share=min_share, min_weight=min_weight)
+
+
+# ---- which points hang together -------------------------------------------------------------------------------------------------
+def _max_d2_of(max_dist, dev):
+    """max_dist squared as ONE fp32 multiply, on the device (None stays None)"""
+    if max_dist is None:
+        return None
+    if isinstance(max_dist, torch.Tensor):
+        m = max_dist.detach().to(dev).to(torch.float32).reshape(1)
+    else:
+        if not float(max_dist) >= 0:
+            raise ValueError(f"max_dist must be a distance >= 0 or None, got {max_dist}")
+        m = torch.full((1,), float(max_dist), dtype=torch.float32, device=dev)
+    return m * m
+
+
+def _neighbour_table(xyz, k, neighbors):
+    """(idx, d2) of ``knn.neighbors(xyz, k)``, or the pair handed in"""
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"points must be [n, 3], got {tuple(xyz.shape)}")
+    if neighbors is None:
+        if int(k) < 1:
+            raise ValueError(f"k must be at least 1, got {k}")
+        return _knn.neighbors(xyz, int(k))
+    idx, d2 = neighbors
+    if idx.dim() != 2 or idx.shape[0] != xyz.shape[0] or d2.shape != idx.shape:
+        raise ValueError(f"neighbors must be (idx, d2), both [{xyz.shape[0]}, K], got {tuple(idx.shape)} and {tuple(d2.shape)}")
+    return idx, d2
+
+
+@torch.no_grad()
+def segment_instances(xyz, labels, k=16, max_dist=None, min_size=1, ignore=None, neighbors=None):
+    """Per-point classes -> instances: the spatially connected pieces of every class, ``(instance, num_instances,
+    instance_label, instance_size)``.
+
+    One ``knn.neighbors(xyz, k)`` call (or ``neighbors = (idx, d2)`` of an earlier one) and one ``knn.components`` call under the
+    same-label rule: two points are joined when one lists the other among its k nearest, both carry the same label >= 0 and --
+    with ``max_dist`` -- they lie within it (``d2 <= max_dist * max_dist``, the square one fp32 multiply).  Rows with a negative
+    label, and rows whose label is named in ``ignore`` (a label value or a collection of them; a bool tensor [n] marks ROWS
+    instead), belong to no instance.  Components with fewer than ``min_size`` members are dropped and the rest renumbered in
+    order, so instances are numbered by ascending smallest member row.
+
+    ``instance`` int32 [n] (-1: none), ``num_instances`` an int -- the one value this function reads back --,
+    ``instance_label`` [num] in the dtype of ``labels`` and ``instance_size`` int32 [num].  Not DBSCAN: a table of k <= 32
+    neighbours does not hold every point within ``max_dist`` (``knn.components``)."""
+    _need_gpu(xyz, "xyz")
+    _need_gpu(labels, "labels")
+    n, dev = xyz.shape[0] if xyz.dim() else -1, xyz.device
+    if labels.dim() != 1 or labels.shape[0] != n:
+        raise ValueError(f"labels must be [{n}], got {tuple(labels.shape)}")
+    if int(min_size) < 1:
+        raise ValueError(f"min_size must be at least 1, got {min_size}")
+    idx, d2 = _neighbour_table(xyz, k, neighbors)
+    lab = labels.detach().to(dev)
+    active = lab >= 0
+    if ignore is not None:
+        if isinstance(ignore, torch.Tensor) and ignore.dtype is torch.bool:
+            if ignore.shape != lab.shape:
+                raise ValueError(f"a bool ignore marks rows and must be [{n}], got {tuple(ignore.shape)}")
+            active &= ~ignore.to(dev)
+        else:
+            active &= ~torch.isin(lab, torch.as_tensor(ignore, device=dev).to(lab.dtype).reshape(-1))
+    lab32 = torch.where(active, lab, torch.full_like(lab, -1)).to(torch.int32)
+    comp, _, sizes, first = _knn.components(idx, d2, _max_d2_of(max_dist, dev), lab32)
+    keep = sizes >= int(min_size)                                   # sizes past the count are 0
+    new_id = torch.cumsum(keep, dim=0, dtype=torch.int32) - 1
+    num = int(keep.sum())                                           # the one read-back
+    at = comp.clamp_min(0).to(torch.int64)
+    instance = torch.where((comp >= 0) & keep[at], new_id[at], torch.full_like(comp, -1))
+    kept = torch.argsort((~keep).to(torch.uint8), stable=True)[:num]            # the kept components, ascending
+    return instance, num, lab[first[kept].to(torch.int64)], sizes[kept]
+
+
+@torch.no_grad()
+def component_filter(points, group=None, num_groups=1, k=16, max_dist=None, min_share=None):
+    """Keep-mask bool [n] that keeps the connected bulk of every group and drops what floats beside it -- the counterpart of
+    ``knn.outlier_mask``, which removes SPARSE points but keeps a dense floater.
+
+    ``group`` [n] integer ids (None: one group of all rows); rows with an id outside ``[0, num_groups)`` are not kept.  All
+    groups go through one ``knn.neighbors(points, k)`` and one ``knn.components`` call with the group as the label: two rows are
+    joined when one lists the other, both lie in the same group and -- with ``max_dist`` -- within that distance.
+    ``min_share=None`` keeps the largest component of every group (equal sizes: the one whose smallest row comes first);
+    otherwise every component with ``size >= min_share * rows of its group`` (compared in fp64) is kept.  The per-group
+    reduction runs over per-component tensors in torch; nothing is read back.  Use: ``render_queries(..., pre_mask=
+    component_filter(xyz, leaf_group, num_groups))``."""
+    _need_gpu(points, "points")
+    n, dev, G = points.shape[0] if points.dim() else -1, points.device, int(num_groups)
+    if G < 1:
+        raise ValueError(f"num_groups must be at least 1, got {num_groups}")
+    if min_share is not None and not 0.0 <= float(min_share) <= 1.0:
+        raise ValueError(f"min_share must lie in [0, 1] or be None, got {min_share}")
+    if group is None:
+        if G != 1:
+            raise ValueError("group=None means one group")
+        lab = torch.zeros(n if n > 0 else 0, dtype=torch.int32, device=dev)
+    else:
+        _need_gpu(group, "group")
+        if group.shape != (n,):
+            raise ValueError(f"group must be [{n}], got {tuple(group.shape)}")
+        lab = torch.where((group < 0) | (group >= G), -1, group).to(torch.int32)
+    idx, d2 = _neighbour_table(points, k, None)
+    comp, _, sizes, first = _knn.components(idx, d2, _max_d2_of(max_dist, dev), lab)
+    # per component c (tensors of n entries, the ones past the count hold first = -1): its group, slot G for none
+    real = first >= 0
+    cgroup = torch.where(real, lab[first.clamp_min(0).to(torch.int64)], torch.full_like(first, G)).to(torch.int64)
+    size64 = sizes.to(torch.int64)
+    if min_share is None:
+        gmax = torch.zeros(G + 1, dtype=torch.int64, device=dev).scatter_reduce(0, cgroup, size64, "amax", include_self=True)
+        best = real & (size64 == gmax[cgroup])
+        c = torch.arange(n, dtype=torch.int64, device=dev)
+        gbest = torch.full((G + 1,), n, dtype=torch.int64, device=dev).scatter_reduce(0, cgroup, torch.where(best, c, n), "amin",
+                                                                                      include_self=True)
+        keep_comp = real & (c == gbest[cgroup])
+    else:
+        gsize = torch.zeros(G + 1, dtype=torch.int64, device=dev).index_add_(0, cgroup, size64)
+        keep_comp = real & (size64.to(torch.float64) >= float(min_share) * gsize[cgroup].to(torch.float64))
+    return (comp >= 0) & keep_comp[comp.clamp_min(0).to(torch.int64)]
