@@ -260,6 +260,15 @@ size_t ogs_raster_tile_sort_capacity(int32_t level);
 int ogs_raster_tile_count_debug(int64_t D, int64_t tiles, int32_t force_blocks, int32_t reverse);
 size_t ogs_raster_tile_count_trip(void);
 
+/* The placement of that counting sort (test hooks; no effect on results).  Its grid is (place chunks) x (tile slices): a place
+ * chunk is G consecutive chunks of the B above, a slice ceil(tiles / S) consecutive tiles, and a workgroup may stage its pairs in
+ * up to stage_words words of LDS to write each tile's run in slot order; a workgroup with more pairs than that stores them one by
+ * one.  group / slices / stage_words > 0 force G, S and the staging words (cut to what LDS has room for), 0 hands that choice back
+ * to the library, a negative value leaves it as it is.  Process-wide.  chosen[0..2] (may be NULL) receives the place chunks
+ * ceil(B / G), the slices and the staging words a pass with list capacity D and `tiles` tiles takes under the hooks as they
+ * stand; all 0 when it takes the radix sort.  Returns OGS_OK. */
+int ogs_raster_tile_place_debug(int64_t D, int64_t tiles, int32_t group, int32_t slices, int32_t stage_words, int32_t* chosen);
+
 /* Re-blend of a KEPT pass (new capability; no reference counterpart -- the reference re-runs preprocess, both sorts and the
  * duplication on every call).  From stage 1 on the reference trains `_ins_feat` alone (train.py:431-436: every other Gaussian
  * parameter is detached) and renders without the random footprint rescale (train.py:346-350: rescale only in stage 2), so for a

@@ -15,6 +15,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
+
 #include "ogs_common.h"
 
 namespace ogs {
@@ -530,11 +532,13 @@ __global__ __launch_bounds__(kBlock) void tile_ranges_kernel(const uint32_t* __r
 //   tile_count_kernel        the emitted keys [0, n) are cut into B contiguous chunks; workgroup b counts its chunk's keys per
 //                            tile in an LDS histogram of `tiles` words and writes row b of the (B + 1) x tiles table (coalesced);
 //   tile_count_scan_kernel   per tile: every cnt[b][t] -> its exclusive prefix over b, the column's total -> row B;
-//   tile_place_kernel        workgroup b: exclusive scan of the totals in LDS (the tiles' range starts: 32 KB from L2 and a
-//                            thousand-thread scan cost less than a launch of its own), cursors = start + its table row; it
-//                            re-reads its chunk, position of a kept pair = LDS atomicAdd on its tile's cursor, one 4-byte
-//                            store of the value.  No key is written.  Workgroup 0 also writes ranges[t] = (start, end),
-//                            (0, 0) for an empty tile (what tile_ranges_kernel leaves), and the grand total to `kept`.
+//   tile_place_kernel        workgroup (p, s), G consecutive chunks x a slice of the tiles: exclusive scan of the totals in LDS
+//                            (the tiles' range starts: 32 KB from L2 and a thousand-thread scan cost less than a launch of its
+//                            own), cursors from its table rows; it re-reads its chunks, position of a kept pair of its slice =
+//                            LDS atomicAdd on its tile's cursor.  Staged (long lists): the position is a slot of an LDS buffer,
+//                            written out afterwards with consecutive lanes on consecutive list slots; otherwise one 4-byte
+//                            store of the value per pair.  No key is written.  The workgroups p = 0 also write ranges[t] =
+//                            (start, end), (0, 0) for an empty tile (what tile_ranges_kernel leaves), one the total to `kept`.
 // No global atomic, no look-back, no waiting between workgroups.  A dropped pair (kDropKey) fails the one `key < tiles` test, as
 // would a key outside the grid, so no LDS word outside the histogram is ever addressed.
 // chunk length = ceil(n / B) rounded up to the trip (kCountTrip keys: one 16-byte load per thread), from the device's n.
@@ -542,14 +546,22 @@ constexpr int kCountBlock = 1024;              // threads: the per-workgroup wor
 constexpr int kCountItems = 4;
 constexpr int kCountTrip = kCountBlock * kCountItems;
 constexpr int kCountScanCols = 64, kCountScanGroups = 16;         // column scan: 64 tiles x 16 groups of rows per workgroup
+constexpr int kPlaceUnroll = 2;                // trips whose loads tile_place_kernel issues before its first LDS atomic
+constexpr int kPlaceEntryBytes = 6;            // a staged entry: the value and its 16-bit tile index inside the slice
 
-__device__ __forceinline__ void tile_count_chunk(const uint32_t* __restrict__ n_dev, int64_t n_cap, int nchunks, int64_t& begin,
-                                                 int64_t& end) {
+// [begin, end) of `group` consecutive chunks from chunk p * group on, out of nchunks (the last of them may be short or empty)
+__device__ __forceinline__ void tile_chunk_span(const uint32_t* __restrict__ n_dev, int64_t n_cap, int nchunks, int p, int group,
+                                                int64_t& begin, int64_t& end) {
     const int64_t n = n_dev ? min((int64_t)*n_dev, n_cap) : n_cap;
     const int64_t per = (n + nchunks - 1) / nchunks;
     const int64_t chunk = (per + kCountTrip - 1) / kCountTrip * kCountTrip;
-    begin = min(n, (int64_t)blockIdx.x * chunk);
-    end = min(n, begin + chunk);
+    begin = min(n, (int64_t)p * group * chunk);
+    end = min(n, begin + (int64_t)group * chunk);
+}
+
+__device__ __forceinline__ void tile_count_chunk(const uint32_t* __restrict__ n_dev, int64_t n_cap, int nchunks, int64_t& begin,
+                                                 int64_t& end) {
+    tile_chunk_span(n_dev, n_cap, nchunks, (int)blockIdx.x, 1, begin, end);
 }
 
 __global__ __launch_bounds__(kCountBlock) void tile_count_kernel(const uint32_t* __restrict__ keys, int64_t n_cap,
@@ -613,76 +625,155 @@ __global__ __launch_bounds__(kCountScanCols * kCountScanGroups) void tile_count_
     }
 }
 
+// The walk of tile_place_kernel over its keys [begin, end): a pair whose key lies in the slice [ulo, ulo + unt) takes the next
+// slot of its tile's LDS cursor -- kStaged: a slot of the staging buffer, where the value and the tile's index inside the slice
+// go; otherwise the global slot, where the value goes.  The values are loaded beside the keys, 16 bytes per thread, whatever the
+// slice keeps of them: a load that waits for the key test cost 3-5 us at S = 2 and 4.
+template <bool kStaged>
+__device__ __forceinline__ void tile_place_walk(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t begin,
+                                                int64_t end, bool reverse, uint32_t ulo, uint32_t unt, uint32_t* cur,
+                                                uint32_t* stage, uint16_t* stile, uint32_t stage_words, uint32_t* __restrict__ out,
+                                                uint32_t out_cap) {
+    const int64_t len = end - begin;
+    for (int64_t i0 = (int64_t)threadIdx.x * kCountItems; i0 < len; i0 += (int64_t)kPlaceUnroll * kCountTrip) {
+        uint32_t k[kPlaceUnroll][kCountItems], v[kPlaceUnroll][kCountItems];
+#pragma unroll
+        for (int u = 0; u < kPlaceUnroll; ++u) {
+            const int64_t iu = i0 + (int64_t)u * kCountTrip;
+            if (!reverse && begin + iu + kCountItems <= end) {        // begin is a multiple of the trip: 16-byte aligned
+                const uint4 kk = *reinterpret_cast<const uint4*>(keys + begin + iu);
+                const uint4 vv = *reinterpret_cast<const uint4*>(vals + begin + iu);
+                k[u][0] = kk.x - ulo; k[u][1] = kk.y - ulo; k[u][2] = kk.z - ulo; k[u][3] = kk.w - ulo;
+                v[u][0] = vv.x; v[u][1] = vv.y; v[u][2] = vv.z; v[u][3] = vv.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < kCountItems; ++j) {
+                    const int64_t i = reverse ? end - 1 - (iu + j) : begin + iu + j;
+                    const bool in = iu + j < len;
+                    k[u][j] = in ? keys[i] - ulo : kDropKey;
+                    v[u][j] = in ? vals[i] : 0u;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kPlaceUnroll; ++u) {
+#pragma unroll
+            for (int j = 0; j < kCountItems; ++j) {
+                if (k[u][j] < unt) {
+                    const uint32_t pos = atomicAdd(&cur[k[u][j]], 1u);
+                    if (kStaged) {
+                        if (pos < stage_words) {
+                            stage[pos] = v[u][j];
+                            stile[pos] = (uint16_t)k[u][j];
+                        }
+                    } else if (pos < out_cap) {
+                        out[pos] = v[u][j];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Workgroup (p, s) = (blockIdx.x, blockIdx.y) places the pairs of place chunk p -- the count chunks [p G, min((p + 1) G, B)), one
+// contiguous stretch of the keys -- that fall into tile slice s: the ceil(tiles / S) tiles from s ceil(tiles / S) on (the last
+// slices may be short or empty).  The table's rows are exclusive prefixes over b with the totals in row B, so the workgroup's
+// first slot of tile t is start[t] + table[p G][t] and its pair count table[min((p + 1) G, B)][t] - table[p G][t]; start[t] is
+// the sum of the totals in front of the slice plus a scan inside it.
+//   staged   (stage_words > 0 and the workgroup's pair count, known before a key is read, fits): the LDS cursor of a tile starts
+//            at the tile's run start inside the staging buffer; the value and the tile's 16-bit index j inside the slice go to
+//            entry atomicAdd(&cur[j], 1).  After the walk thread i takes staged entry i and stores its value at delta[j] + i
+//            (delta = first global slot - run start): consecutive lanes write consecutive list slots.  (Finding j by bisection
+//            over the run ends instead of keeping it cost 3-5 us: DESIGN 3i.)
+//   direct   (otherwise): the cursor is the global slot, the value is stored from the walk, one 4-byte store per pair.
+// LDS: cur[ceil(tiles / S)], and with stage_words > 0 also delta[ceil(tiles / S)], stage[stage_words] and the 16-bit
+// stile[stage_words].
+// The workgroups p = 0 write ranges[t] of their slice ((0, 0) for an empty tile), workgroup (0, S - 1) -- whose slice, empty or
+// not, ends at the last tile -- writes the grand total to `kept`; neither duty depends on the chunk holding a key.
 // reverse (tests only): the chunk is walked back to front, so that equal-depth pairs reach their tile in descending id order.
 // out_cap: size of `out`; a position is below the kept total <= n <= out_cap by construction, the test only keeps a table that
-// something else damaged from turning into a stray store.
+// something else damaged from turning into a stray store (as does `pos < stage_words` for the staging buffer).
 __global__ __launch_bounds__(kCountBlock) void tile_place_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                                  int64_t n_cap, const uint32_t* __restrict__ n_dev, int tiles,
+                                                                 int nrows, int group, uint32_t stage_words,
                                                                  const uint32_t* __restrict__ table, uint2* __restrict__ ranges,
                                                                  uint32_t* __restrict__ kept, uint32_t* __restrict__ out,
                                                                  uint32_t out_cap, bool reverse) {
-    extern __shared__ uint32_t count_lds[];                       // [tiles] totals -> range starts -> cursors
-    __shared__ uint32_t wave_sums[kCountBlock / kWave];
+    extern __shared__ uint32_t count_lds[];
+    __shared__ uint32_t wave_sums[3][kCountBlock / kWave];
+    const int p = blockIdx.x, slices = gridDim.y;
+    const int per_slice = (tiles + slices - 1) / slices;
+    const int t_lo = min(tiles, (int)blockIdx.y * per_slice), nt = min(tiles, t_lo + per_slice) - t_lo;
     int64_t begin, end;
-    tile_count_chunk(n_dev, n_cap, (int)gridDim.x, begin, end);
-    if (begin >= end && blockIdx.x != 0) return;                  // block-uniform; workgroup 0 writes the ranges whatever n is
-    const uint32_t* totals = table + (size_t)gridDim.x * tiles;
-    const uint32_t* row = table + (size_t)blockIdx.x * tiles;
-    for (int t = threadIdx.x; t < tiles; t += kCountBlock) count_lds[t] = totals[t];
+    tile_chunk_span(n_dev, n_cap, nrows, p, group, begin, end);
+    if (begin >= end && p != 0) return;                           // block-uniform; the workgroups p = 0 write the ranges whatever n is
+    const bool may_stage = stage_words > 0;
+    uint32_t* cur = count_lds;                                    // totals -> run starts / global slots -> cursors
+    uint32_t* delta = cur + per_slice;                            // pair counts -> first global slot - run start
+    uint32_t* stage = delta + per_slice;
+    const uint32_t* totals = table + (size_t)nrows * tiles;
+    const uint32_t* row = table + (size_t)p * group * tiles + t_lo;
+    const uint32_t* row_end = table + (size_t)min(nrows, (p + 1) * group) * tiles + t_lo;
+    uint32_t front = 0;                                           // this thread's share of the totals in front of the slice
+    for (int t = threadIdx.x; t < t_lo; t += kCountBlock) front += totals[t];
+    for (int j = threadIdx.x; j < nt; j += kCountBlock) {
+        cur[j] = totals[t_lo + j];
+        if (may_stage) delta[j] = row_end[j] - row[j];
+    }
     __syncthreads();
     // a thread scans `per` consecutive tiles; per is odd, so the lanes of a wave walk different LDS banks
-    const int per = ((tiles + kCountBlock - 1) / kCountBlock) | 1;
-    const int t0 = min(tiles, (int)threadIdx.x * per), t1 = min(tiles, t0 + per);
-    uint32_t sum = 0;
-    for (int t = t0; t < t1; ++t) sum += count_lds[t];
-    const uint32_t inc = wave_inclusive_scan(sum);
-    if (lane_id() == kWave - 1) wave_sums[threadIdx.x >> 6] = inc;
+    const int per = ((nt + kCountBlock - 1) / kCountBlock) | 1;
+    const int j0 = min(nt, (int)threadIdx.x * per), j1 = min(nt, j0 + per);
+    uint32_t sum = 0, mine = 0;
+    for (int j = j0; j < j1; ++j) {
+        sum += cur[j];
+        if (may_stage) mine += delta[j];
+    }
+    const uint32_t inc = wave_inclusive_scan(sum), inc_mine = wave_inclusive_scan(mine), inc_front = wave_inclusive_scan(front);
+    if (lane_id() == kWave - 1) {
+        wave_sums[0][threadIdx.x >> 6] = inc;
+        wave_sums[1][threadIdx.x >> 6] = inc_mine;
+        wave_sums[2][threadIdx.x >> 6] = inc_front;
+    }
     __syncthreads();
-    uint32_t run = inc - sum, total = 0;
+    uint32_t run = inc - sum, run_mine = inc_mine - mine, total = 0, need = 0;
 #pragma unroll
     for (int w = 0; w < kCountBlock / kWave; ++w) {
-        const uint32_t v = wave_sums[w];
-        if (w < (int)(threadIdx.x >> 6)) run += v;
-        total += v;
+        const uint32_t a = wave_sums[0][w], b = wave_sums[1][w];
+        if (w < (int)(threadIdx.x >> 6)) { run += a; run_mine += b; }
+        total += a + wave_sums[2][w];
+        run += wave_sums[2][w];
+        need += b;
     }
-    for (int t = t0; t < t1; ++t) {
-        const uint32_t cnt = count_lds[t];
-        count_lds[t] = run;
-        run += cnt;
-    }
-    __syncthreads();
-    if (blockIdx.x == 0) {
-        for (int t = threadIdx.x; t < tiles; t += kCountBlock) {
-            const uint32_t cnt = totals[t], start = count_lds[t];
-            ranges[t] = cnt ? make_uint2(start, start + cnt) : make_uint2(0u, 0u);
-        }
-        if (threadIdx.x == 0) *kept = total;
-    }
-    for (int t = threadIdx.x; t < tiles; t += kCountBlock) count_lds[t] += row[t];
-    __syncthreads();
-    for (int64_t j0 = (int64_t)threadIdx.x * kCountItems; j0 < end - begin; j0 += kCountTrip) {
-        uint32_t k[kCountItems], v[kCountItems];
-        if (!reverse && begin + j0 + kCountItems <= end) {
-            const uint4 kk = *reinterpret_cast<const uint4*>(keys + begin + j0);
-            const uint4 vv = *reinterpret_cast<const uint4*>(vals + begin + j0);
-            k[0] = kk.x; k[1] = kk.y; k[2] = kk.z; k[3] = kk.w;
-            v[0] = vv.x; v[1] = vv.y; v[2] = vv.z; v[3] = vv.w;
+    const bool staged = may_stage && need <= stage_words;         // block-uniform: every pair of the workgroup has a staging slot
+    for (int j = j0; j < j1; ++j) {
+        const uint32_t cnt = cur[j], c = may_stage ? delta[j] : 0u;
+        if (p == 0) ranges[t_lo + j] = cnt ? make_uint2(run, run + cnt) : make_uint2(0u, 0u);
+        if (staged) {
+            cur[j] = run_mine;
+            delta[j] = run - run_mine;
         } else {
-#pragma unroll
-            for (int j = 0; j < kCountItems; ++j) {
-                const int64_t i = reverse ? end - 1 - (j0 + j) : begin + j0 + j;
-                const bool in = j0 + j < end - begin;
-                k[j] = in ? keys[i] : kDropKey;
-                v[j] = in ? vals[i] : 0u;
-            }
+            cur[j] = run;
         }
-#pragma unroll
-        for (int j = 0; j < kCountItems; ++j) {
-            if (k[j] < (uint32_t)tiles) {
-                const uint32_t pos = atomicAdd(&count_lds[k[j]], 1u);
-                if (pos < out_cap) out[pos] = v[j];
-            }
-        }
+        run += cnt;
+        run_mine += c;
+    }
+    if (p == 0 && blockIdx.y == gridDim.y - 1 && threadIdx.x == 0) *kept = total;
+    if (begin >= end || nt == 0 || (may_stage && need == 0)) return;   // block-uniform: nothing of this chunk lies in this slice
+    __syncthreads();
+    for (int j = threadIdx.x; j < nt; j += kCountBlock) (staged ? delta : cur)[j] += row[j];
+    __syncthreads();
+    const uint32_t ulo = (uint32_t)t_lo, unt = (uint32_t)nt;      // key - ulo < unt: inside the slice (a dropped pair never is)
+    uint16_t* stile = reinterpret_cast<uint16_t*>(stage + stage_words);
+    if (!staged) {
+        tile_place_walk<false>(keys, vals, begin, end, reverse, ulo, unt, cur, stage, stile, stage_words, out, out_cap);
+        return;
+    }
+    tile_place_walk<true>(keys, vals, begin, end, reverse, ulo, unt, cur, stage, stile, stage_words, out, out_cap);
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < need; i += kCountBlock) {   // consecutive lanes, consecutive slots of a run
+        const uint32_t pos = delta[min((int)stile[i], nt - 1)] + i;
+        if (pos < out_cap) out[pos] = stage[i];
     }
 }
 
@@ -1369,7 +1460,7 @@ void tile_count_debug(int force_blocks, int reverse) {
 }
 int tile_count_trip() { return kCountTrip; }
 
-// B, the number of chunks (= workgroups of tile_count_kernel and tile_place_kernel), or 0: the pass takes the radix sort.
+// B, the number of chunks (= workgroups of tile_count_kernel), or 0: the pass takes the radix sort.
 // The table of (B + 1) x tiles words (B rows of counts, one of totals) lives in a D-word key buffer; one chunk per trip of
 // keys at the most.
 int tile_count_blocks(int64_t D, int64_t tiles) {
@@ -1378,6 +1469,49 @@ int tile_count_blocks(int64_t D, int64_t tiles) {
     int64_t B = g_tile_count_force > 0 ? g_tile_count_force : (trips < kTileCountBlocks ? trips : kTileCountBlocks);
     if (B > D / tiles - 1) B = D / tiles - 1;
     return (int)B;
+}
+
+// test hooks (ogs_raster_tile_place_debug): forced G (count chunks per place chunk), S (tile slices) and staging words; 0: the rule
+static int g_tile_place_group = 0, g_tile_place_slices = 0, g_tile_place_stage = 0;
+void tile_place_debug(int group, int slices, int stage_words) {
+    if (group >= 0) g_tile_place_group = group;
+    if (slices >= 0) g_tile_place_slices = slices;
+    if (stage_words >= 0) g_tile_place_stage = stage_words;
+}
+
+constexpr size_t kPlaceLdsBytes = 160 * 1024 - 256;               // dynamic: what one workgroup may declare less the kernel's static words
+constexpr int kPlaceMaxSlices = 1024;                             // what the hook may force
+constexpr int kPlaceGrid = 256, kPlaceOwnSlices = 4;              // the rule: workgroups to fill the chip with, slices at the most
+constexpr int kPlaceStageTrips = 2;                               // and the trips a chunk has room for before it stages
+
+// The grid of tile_place_kernel for a pass of B count chunks: ceil(B / G) place chunks x S slices, and its staging words
+// (0: every workgroup stores straight from the walk).  From what the host knows -- the capacity D, the grid, B -- and the hooks.
+// DESIGN 3i has the sweep behind the rule.
+TilePlacePlan tile_place_plan(int64_t D, int64_t tiles, int B) {
+    TilePlacePlan pl = {0, 0, 0, 0};
+    if (B < 1 || tiles < 1) return pl;
+    // The rule: a pass whose chunks have room for kPlaceStageTrips trips or more (the streaming workloads from 2.6 M pairs up, at
+    // B = 128) stages, with G = 1 and as many slices, kPlaceOwnSlices at the most, as make the grid the size of the chip.  The
+    // kernel's time is one workgroup's chain of trips: longer place chunks (G > 1) lose more than their longer runs save, a second
+    // slice halves the staged entries per workgroup.  Shorter chunks (one trip each below kTileCountBlocks chunks; 0.44 M pairs
+    // over 2500 tiles at B = 128) keep the direct path, G = S = 1, where the sweep found nothing to gain.
+    const bool rule = D >= (int64_t)kPlaceStageTrips * kCountTrip * B;
+    int G = 1, S = 1;
+    if (rule) S = kPlaceGrid / B < 1 ? 1 : kPlaceGrid / B > kPlaceOwnSlices ? kPlaceOwnSlices : kPlaceGrid / B;
+    if (g_tile_place_group > 0) G = g_tile_place_group;
+    if (g_tile_place_slices > 0) S = g_tile_place_slices < kPlaceMaxSlices ? g_tile_place_slices : kPlaceMaxSlices;
+    if (G > B) G = B;
+    const int64_t per_slice = (tiles + S - 1) / S;
+    const int64_t room = ((int64_t)kPlaceLdsBytes - 8 * per_slice) / kPlaceEntryBytes;     // > 0: tiles <= kTileCountMaxTiles
+    // no more words than a place chunk has pairs: G chunks of ceil(D / B) pairs rounded up to the trip
+    const int64_t span = G * (((D + B - 1) / B + kCountTrip - 1) / kCountTrip * kCountTrip);
+    int64_t W = g_tile_place_stage > 0 ? g_tile_place_stage : (rule || G > 1 || S > 1) ? span : 0;
+    if (W > room) W = room;
+    pl.group = G;
+    pl.chunks = (B + G - 1) / G;
+    pl.slices = S;
+    pl.stage_words = (uint32_t)W;
+    return pl;
 }
 
 int launch_tile_count_binning(const uint32_t* keys, const uint32_t* vals, int64_t D, const uint32_t* n_dev, int B, int64_t tiles,
@@ -1391,8 +1525,22 @@ int launch_tile_count_binning(const uint32_t* keys, const uint32_t* vals, int64_
     const int cols = (int)((tiles + kCountScanCols - 1) / kCountScanCols);
     OGS_LAUNCH(tile_count_scan_kernel, dim3(cols), dim3(kCountScanCols * kCountScanGroups), 0, s, table, B, (int)tiles);
     OGS_LAUNCH_CHECK(debug, s);
-    OGS_LAUNCH(tile_place_kernel, dim3(B), dim3(kCountBlock), lds, s, keys, vals, D, n_dev, (int)tiles, (const uint32_t*)table,
-               ranges, kept, point_list, (uint32_t)D, g_tile_place_reverse);
+    const TilePlacePlan pl = tile_place_plan(D, tiles, B);
+    const size_t per_slice = (size_t)((tiles + pl.slices - 1) / pl.slices);
+    const size_t place_lds = pl.stage_words ? (8 * per_slice + (size_t)kPlaceEntryBytes * pl.stage_words + 15) / 16 * 16
+                                            : per_slice * sizeof(uint32_t);
+    if (place_lds > 48 * 1024) {                                  // the function's dynamic LDS limit is raised once per device
+        static std::atomic<bool> raised[64];
+        int dev = 0;
+        OGS_HIP_CHECK(hipGetDevice(&dev));
+        if (dev < 0 || dev >= 64 || !raised[dev].load(std::memory_order_relaxed)) {
+            OGS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_place_kernel),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPlaceLdsBytes));
+            if (dev >= 0 && dev < 64) raised[dev].store(true, std::memory_order_relaxed);
+        }
+    }
+    OGS_LAUNCH(tile_place_kernel, dim3(pl.chunks, pl.slices), dim3(kCountBlock), place_lds, s, keys, vals, D, n_dev, (int)tiles, B,
+               pl.group, pl.stage_words, (const uint32_t*)table, ranges, kept, point_list, (uint32_t)D, g_tile_place_reverse);
     OGS_LAUNCH_CHECK(debug, s);
     return OGS_OK;
 }

@@ -551,6 +551,19 @@ int ogs_raster_tile_count_debug(int64_t D, int64_t tiles, int32_t force_blocks, 
 }
 size_t ogs_raster_tile_count_trip(void) { return (size_t)tile_count_trip(); }
 
+// Tests: the grid of tile_place_kernel.  group / slices / stage_words > 0 force G (count chunks per place chunk), S (tile slices)
+// and the staging words per workgroup, 0 gives that choice back to the library, a negative value leaves it as it is; chosen[0..2]
+// receives (place chunks, slices, staging words) of a pass with list capacity D and `tiles` tiles under the hooks as they stand
+// (all 0 when such a pass takes the radix sort).  Process-wide: a test restores (0, 0, 0) when it is done.
+int ogs_raster_tile_place_debug(int64_t D, int64_t tiles, int32_t group, int32_t slices, int32_t stage_words, int32_t* chosen) {
+    tile_place_debug(group, slices, stage_words);
+    if (chosen) {
+        const TilePlacePlan pl = tile_place_plan(D, tiles, tile_count_blocks(D, tiles));
+        chosen[0] = pl.chunks; chosen[1] = pl.slices; chosen[2] = (int32_t)pl.stage_words;
+    }
+    return OGS_OK;
+}
+
 static int forward_tiny_impl(const OgsRasterFwdArgs* a_in, void* stream_, bool raw, const float* raw_rest) {
     int rc = validate_fwd(a_in);
     if (rc != OGS_OK) return rc;

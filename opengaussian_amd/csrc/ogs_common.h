@@ -407,6 +407,12 @@ constexpr int kTileCountBlocks = 128;          // chunks (workgroups of 1024 thr
 int tile_count_blocks(int64_t D, int64_t tiles);           // B for this pass; 0: the radix path
 int tile_count_trip();
 void tile_count_debug(int force_blocks, int reverse);      // test hooks; a negative argument leaves its setting as it is
+// tile_place_kernel's grid for a pass of B count chunks: `chunks` = ceil(B / group) place chunks of `group` count chunks each, times
+// `slices` slices of the tiles; stage_words of LDS per workgroup for the runs it writes out in slot order (0: none, every pair is
+// stored from the walk).  All zero when B < 1.
+struct TilePlacePlan { int group, chunks, slices; uint32_t stage_words; };
+TilePlacePlan tile_place_plan(int64_t D, int64_t tiles, int B);
+void tile_place_debug(int group, int slices, int stage_words);   // test hooks; > 0 forces, 0 hands back, < 0 leaves as it is
 int launch_tile_count_binning(const uint32_t* keys, const uint32_t* vals, int64_t D, const uint32_t* n_dev, int B, int64_t tiles,
                               uint32_t* table, uint2* ranges, uint32_t* kept, uint32_t* point_list, hipStream_t s, int debug);
 // Ungrouped streaming passes with P > kSmallMaxP bin without a global depth sort: the geometry phase scans tiles_touched in
