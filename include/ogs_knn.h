@@ -186,6 +186,50 @@ size_t ogs_knn_components_tmp_bytes(int64_t n);
 int ogs_knn_components(int64_t n, int32_t K, const int32_t* idx, const float* d2, const float* max_d2, const int32_t* labels,
                        int32_t* comp, int32_t* sizes, int32_t* first, int32_t* count, void* tmp, size_t tmp_bytes, void* stream);
 
+/*
+ * ---- every row within a radius (csrc/knn_radius.hip) -----------------------------------------------------------------------------
+ * The walk of ogs_knn_query with a FIXED threshold: boxes of the sorted reference set are skipped by the same exact lower bound,
+ * and nothing of variable length is ever stored -- memory is O(n + m) whatever the radius.  d2 as at the top of this file;
+ * radius2 / eps2 is a SQUARED distance in a DEVICE fp32 scalar and the pair test is d2(q, j) <= *radius2, the fp32 compare as
+ * written: equality counts, a NaN on either side counts nothing.  A NaN or negative threshold therefore selects nothing, +inf
+ * every row with finite coordinates.  No read-back, no float atomics, no workgroup waits on another; two calls give the same bytes.
+ *
+ * ogs_knn_radius_count: count [m] int32, count[q] = the number of reference rows j in [0, n) with d2(q, j) <= *radius2, in the
+ * caller's query order.  index is what ogs_knn_index_build made for the n reference rows; the queries may lie anywhere and are
+ * grouped by a Morton sort of their own, as in ogs_knn_query.  Labels are given for both sets or for neither (one without the
+ * other: OGS_ERR_INVALID_ARG): ref_labels [n], query_labels [m]; row j then counts only when ref_labels[j] == query_labels[q] >= 0,
+ * and a query with a negative label gets 0.  Label values are compared, never used as an index.  n == 0 writes zeros (index,
+ * queries, radius2 and tmp are not looked at), m == 0 does nothing.  n and m <= INT32_MAX - ogs_knn_box_points(); bad sizes, NULL
+ * pointers and a tmp below ogs_knn_radius_count_tmp_bytes(n, m) bytes return OGS_ERR_INVALID_ARG.
+ *
+ * ogs_knn_dbscan: exact DBSCAN of one point set against itself (the sort into boxes happens inside the call, in tmp).
+ *   Row i is ACTIVE when labels == NULL or labels[i] >= 0.
+ *   N(i) = the active rows j with labels[j] == labels[i] (where given) and d2(i, j) <= *eps2; i itself is one of them.
+ *   degree [n] (may be NULL)  |N(i)|, 0 for an inactive row
+ *   core [n] uint8            degree[i] >= min_pts
+ *   Clusters are the connected components of the graph on the CORE rows with an edge between two cores in each other's N.  A
+ *   non-core active row with a core in N(i) is a BORDER row: it joins the cluster of the core j with the smallest pair
+ *   (d2(i, j), j), that one only, and bridges nothing.  Clusters are numbered 0 .. C - 1 by ascending smallest CORE row.
+ *   cluster [n]  the row's cluster, -1 for every row that is neither core nor border
+ *   count [1]    C
+ *   sizes [n]    sizes[c] = the members of c, borders included, for c < C; 0 beyond
+ *   first [n]    (may be NULL) first[c] = the smallest core row of c for c < C; -1 beyond
+ * Every output element is written by every call.  The result is unique: two calls give the same bytes, and renumbering the rows
+ * gives the same partition as long as no border row has cores of two clusters at the same smallest d2.
+ * min_pts >= 1, n <= INT32_MAX - ogs_knn_box_points(); n == 0 writes count[0] = 0 and returns 0 (nothing else is looked at).  Bad
+ * sizes, NULL required pointers (points, eps2, cluster, core, sizes, count, tmp) and a tmp below ogs_knn_dbscan_tmp_bytes(n) bytes
+ * return OGS_ERR_INVALID_ARG before anything is launched.  No content of labels makes a wild address.  The union-find is the one
+ * of ogs_knn_components, bounded and reporting through the sticky status word in the same way.
+ */
+size_t ogs_knn_radius_count_tmp_bytes(int64_t n, int64_t m);
+int ogs_knn_radius_count(int64_t n, const void* index, int64_t m, const float* queries, const float* radius2,
+                         const int32_t* ref_labels, const int32_t* query_labels, int32_t* count,
+                         void* tmp, size_t tmp_bytes, void* stream);
+size_t ogs_knn_dbscan_tmp_bytes(int64_t n);
+int ogs_knn_dbscan(int64_t n, const float* points, const float* eps2, int32_t min_pts, const int32_t* labels,
+                   int32_t* cluster, uint8_t* core, int32_t* degree, int32_t* sizes, int32_t* first, int32_t* count,
+                   void* tmp, size_t tmp_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,10 @@ SIGNATURES = {
                                          C.c_size_t, _vp]),
     "ogs_knn_components_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "ogs_knn_components": (C.c_int, [C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ogs_knn_radius_count_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "ogs_knn_radius_count": (C.c_int, [C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "ogs_knn_dbscan_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "ogs_knn_dbscan": (C.c_int, [C.c_int64, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "ogs_kmeans_wide_row_tile": (C.c_size_t, []),
     "ogs_kmeans_wide_centre_tile": (C.c_size_t, []),
     "ogs_kmeans_wide_dim_step": (C.c_size_t, []),

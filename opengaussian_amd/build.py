@@ -36,6 +36,8 @@ EXTRA = {
     "knn_neighbors.hip": ["-ffp-contract=off"],
     # the same walk (csrc/knn_boxes.h) between two point sets: the same d2 bits and the same monotone bound
     "knn_query.hip": ["-ffp-contract=off"],
+    # the same walk with a fixed threshold (radius counts, DBSCAN): the same d2 bits and the same monotone bound
+    "knn_radius.hip": ["-ffp-contract=off"],
     # every fmaf of the reverse-list sums is written out: the summation orders include/ogs_knn.h states are what runs
     "knn_graph.hip": ["-ffp-contract=off"],
     # similarities as one fixed chain of fp32 multiplies and adds: the same bits from every build

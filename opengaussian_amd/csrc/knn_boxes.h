@@ -38,6 +38,38 @@ struct KnnBoxes {                                       // what a search reads o
 // n in [1, INT32_MAX - kKnnBox]; pts [n, 3]; everything else as the structs say.  No read-back, nothing waits on another workgroup.
 int knn_sort_into_boxes(int n, const float* pts, const KnnSortScratch& t, const KnnBoxes& out, hipStream_t s);
 
+// the persistent index of a point set (ogs_knn_index_build): what ogs_knn_query and ogs_knn_radius_count carve out of `index`
+struct IndexLayout {
+    KnnBoxes b;
+    size_t bytes;
+    static IndexLayout carve(void* p, int64_t n) {
+        Carver c(p);
+        IndexLayout t{};
+        const size_t nbox = (size_t)((n + kKnnBox - 1) / kKnnBox), npad = nbox * kKnnBox;
+        t.b.frame = c.take<float>(6);
+        t.b.sx = c.take<float>(npad); t.b.sy = c.take<float>(npad); t.b.sz = c.take<float>(npad);
+        t.b.sid = c.take<int32_t>(npad);
+        t.b.box = c.take<float>(6 * nbox);
+        t.b.first_key = c.take<uint32_t>(nbox);
+        t.bytes = c.off;
+        return t;
+    }
+};
+
+// the scratch of one knn_sort_into_boxes call over n points
+struct SortTmp {
+    KnnSortScratch sort;
+    size_t bytes;
+    static SortTmp carve(Carver& c, int64_t n) {
+        SortTmp t{};
+        t.sort.partial = c.take<float>((size_t)kBoundBlocks * 6);
+        for (int i = 0; i < 2; ++i) { t.sort.keys[i] = c.take<uint32_t>((size_t)n); t.sort.vals[i] = c.take<uint32_t>((size_t)n); }
+        t.sort.sort_tmp = c.take<char>(sort_tmp_bytes(n));
+        t.bytes = c.off;
+        return t;
+    }
+};
+
 __device__ __forceinline__ float wave_min_f(float v) {
     for (int m = kWave / 2; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, kWave));
     return v;
@@ -82,6 +114,7 @@ __device__ __forceinline__ bool knn_before(float d, int j, float bd, int bi) {
 // offset o of the outward walk: 0, +1, -1, +2, -2, ...
 __device__ __forceinline__ int knn_delta(int o) { return (o & 1) ? (o + 1) >> 1 : -(o >> 1); }
 
+#ifndef OGS_KNN_BOXES_NO_SEARCH     // knn_radius.hip walks the boxes with a kernel of its own and wants no copy of this one
 namespace {        // internal linkage: every file that includes this builds and registers its own copy of the kernel (no -fgpu-rdc)
 
 // The search: one single-wave workgroup per RUN of kKnnBox queries (gridDim.x runs), one query per lane.  The queries are the
@@ -216,5 +249,6 @@ int knn_launch_search(int nruns, int nbox, int K, int exclude_self, const KnnBox
 }
 
 }  // namespace
+#endif
 
 }  // namespace ogs

@@ -32,42 +32,18 @@
 // status word (ogs_common.h) and leaves the loop: a bug here ends as OGS_ERR_DEVICE from ogs_check_async_status(), not as a
 // hung card.
 //
+// The primitives (load_parent, store_parent, step_up, report_bound, unite) live in knn_union.h, shared with knn_radius.hip, which
+// unites inside a radius walk and ends in the same tail (knn_components_tail below: flatten .. sizes).
+//
 // Addresses: a slot value outside [0, n) is skipped before it indexes anything; every value read from parent[] is one the
 // kernels of this call wrote, in [0, n); dense[] values are clamped to [0, n - 1] before they become component numbers, and
 // the list bounds to [0, n] before they index the member array.
-#include "ogs_common.h"
-#include "../../include/ogs_knn.h"
+#include "knn_union.h"
 
 #include <limits.h>
 
 namespace ogs {
 namespace {
-
-struct ComponentsTmp {
-    int32_t* parent;                                    // [n]
-    uint32_t* flag;                                     // [n] 1 on the root rows
-    uint32_t* dense;                                    // [n] exclusive scan of flag
-    int32_t* begin;                                     // [n + 1] member list of component c: members[begin[c] : begin[c + 1]]
-    int32_t* members;                                   // [n]
-    void* scan_tmp;
-    void* lists_tmp;                                    // scratch of ogs_knn_transpose(n, 1, n)
-    size_t lists_bytes;
-    size_t bytes;
-    static ComponentsTmp carve(void* p, int64_t n) {
-        Carver c(p);
-        ComponentsTmp t{};
-        t.parent = c.take<int32_t>((size_t)n);
-        t.flag = c.take<uint32_t>((size_t)n);
-        t.dense = c.take<uint32_t>((size_t)n);
-        t.begin = c.take<int32_t>((size_t)n + 1);
-        t.members = c.take<int32_t>((size_t)n);
-        t.scan_tmp = c.take<char>(scan_tmp_bytes(n));
-        t.lists_bytes = ogs_knn_transpose_tmp_bytes(n, 1, n);
-        t.lists_tmp = c.take<char>(t.lists_bytes);
-        t.bytes = c.off;
-        return t;
-    }
-};
 
 struct EdgeRule {
     int64_t n;
@@ -86,16 +62,6 @@ struct EdgeRule {
         return j;
     }
 };
-
-__device__ __forceinline__ int load_parent(const int32_t* parent, int64_t x) {
-    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void store_parent(int32_t* parent, int64_t x, int v) {
-    __hip_atomic_store(parent + x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void report_bound(uint32_t* status_word) {
-    if (status_word) __hip_atomic_fetch_or(status_word, kAsyncComponentsWalk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // A row is owned by a group of L consecutive lanes, L the smallest power of two >= min(K, 64): lane l looks at the slots l,
 // l + L, ... (consecutive lanes read consecutive slots), the group folds its minima by xor-shuffles and lane 0 writes.
@@ -125,15 +91,6 @@ __global__ __launch_bounds__(kBlock) void components_init_kernel(EdgeRule r, int
     if (i < r.n && l == 0) parent[i] = p;
 }
 
-// One step towards the root of x with path halving: returns parent[x] as loaded (x itself: x looked like a root).
-__device__ __forceinline__ int step_up(int32_t* parent, int x) {
-    const int p = load_parent(parent, x);
-    if (p == x) return x;
-    const int g = load_parent(parent, p);
-    if (g != p) store_parent(parent, x, g);             // x was seen as a non-root, g is an ancestor of it: a hint, never a hook
-    return p;
-}
-
 __global__ __launch_bounds__(kBlock) void components_hook_kernel(EdgeRule r, int64_t E, int32_t* parent, uint32_t* status_word) {
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (e >= E) return;
@@ -142,35 +99,23 @@ __global__ __launch_bounds__(kBlock) void components_hook_kernel(EdgeRule r, int
     const bool use_d2 = r.d2 && r.max_d2;
     const int j = r.edge(e, i, r.labels ? r.labels[i] : 0, use_d2, use_d2 ? r.max_d2[0] : 0.f);
     if (j < 0) return;
-    int a = (int)i, b = j;
-    // every pass lowers a + b by at least one or ends the loop; a + b < 2 n at the start
-    const int64_t bound = 2 * r.n + 2;
-    for (int64_t it = 0; ; ++it) {
-        if (a == b) return;
-        if (it >= bound) { report_bound(status_word); return; }
-        if (a < b) { const int t = a; a = b; b = t; }   // a: the larger end
-        const int pa = step_up(parent, a);
-        if (pa != a) { a = pa; continue; }
-        const int pb = step_up(parent, b);
-        if (pb != b) { b = pb; continue; }
-        // both ends looked like roots: hook the larger under the smaller, if it still is one
-        int expected = a;
-        if (__hip_atomic_compare_exchange_strong(parent + a, &expected, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            return;
-        if (expected >= a) { report_bound(status_word); return; }       // cannot happen (invariant 1); never walk upwards
-        a = expected;                                   // what parent[a] holds now: a member of a's set below a
-    }
+    unite(parent, (int)i, j, 2 * r.n + 2, status_word);
 }
 
+// anchor (may be nullptr; knn_union.h): row i starts its walk at anchor[i] instead of at itself, is a node of the forest only when
+// that IS itself, and leaves its root in anchor[i] (-1 stays -1); labels is not read then
 __global__ __launch_bounds__(kBlock) void components_flatten_kernel(int64_t n, const int32_t* __restrict__ labels, int32_t* parent,
-                                                                    int32_t* __restrict__ comp, uint32_t* __restrict__ flag,
-                                                                    uint32_t* status_word) {
+                                                                    int32_t* __restrict__ anchor, int32_t* __restrict__ comp,
+                                                                    uint32_t* __restrict__ flag, uint32_t* status_word) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    if (labels && labels[i] < 0) { comp[i] = -1; flag[i] = 0u; return; }
-    // no hook runs in this launch: the roots are fixed, the walk strictly descends, halving is a hint for the other walkers
     int x = (int)i;
+    if (anchor) {
+        x = anchor[i];
+        if (x < 0 || (int64_t)x >= n) { comp[i] = -1; flag[i] = 0u; anchor[i] = -1; return; }
+    } else if (labels && labels[i] < 0) { comp[i] = -1; flag[i] = 0u; return; }
+    const bool node = x == (int)i;
+    // no hook runs in this launch: the roots are fixed, the walk strictly descends, halving is a hint for the other walkers
     for (int64_t it = 0; ; ++it) {
         if (it > n) { report_bound(status_word); break; }
         const int p = step_up(parent, x);
@@ -178,7 +123,8 @@ __global__ __launch_bounds__(kBlock) void components_flatten_kernel(int64_t n, c
         x = p;
     }
     comp[i] = x;
-    flag[i] = x == (int)i ? 1u : 0u;
+    flag[i] = node && x == (int)i ? 1u : 0u;
+    if (anchor) anchor[i] = x;
 }
 
 __global__ __launch_bounds__(kBlock) void components_number_kernel(int64_t n, const uint32_t* __restrict__ dense, int32_t* __restrict__ comp) {
@@ -189,20 +135,46 @@ __global__ __launch_bounds__(kBlock) void components_number_kernel(int64_t n, co
 }
 
 // sizes and first from the member lists of the components (the reverse lists of comp seen as an [n, 1] table: the rows of
-// component c, ascending): the list's length, and its first entry
+// component c, ascending): the list's length, and its first entry -- or, with root_of (may be nullptr), the root of that entry
 __global__ __launch_bounds__(kBlock) void components_sizes_kernel(int64_t n, const int32_t* __restrict__ begin, const int32_t* __restrict__ members,
-                                                                  int32_t* __restrict__ sizes, int32_t* __restrict__ first) {
+                                                                  const int32_t* __restrict__ root_of, int32_t* __restrict__ sizes,
+                                                                  int32_t* __restrict__ first) {
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= n) return;
     const int64_t b = min(max((int64_t)begin[c], (int64_t)0), n), e = min(max((int64_t)begin[c + 1], b), n);
     sizes[c] = (int32_t)(e - b);
-    if (first) first[c] = e > b ? members[b] : -1;
+    if (!first) return;
+    int f = e > b ? members[b] : -1;
+    if (root_of && f >= 0) f = (int64_t)f < n ? root_of[f] : -1;
+    first[c] = f;
 }
 
 bool components_sizes_ok(int64_t n, int32_t K) { return n >= 0 && K >= 1 && n * (int64_t)K < ((int64_t)1 << 31); }
 int64_t blocks_for(int64_t threads) { return (threads + kBlock - 1) / kBlock; }
 
 }  // namespace
+
+int knn_components_tail(int64_t n, const int32_t* labels, int32_t* anchor, int32_t* comp, int32_t* sizes, int32_t* first,
+                        int32_t* count, const ComponentsTmp& t, void* stream_) {
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    uint32_t* status_word = async_status_word();
+    if (!status_word) return OGS_ERR_HIP;
+    const dim3 rows((unsigned)blocks_for(n)), block(kBlock);
+    OGS_LAUNCH(components_flatten_kernel, rows, block, 0, s, n, labels, t.parent, anchor, comp, t.flag, status_word);
+    OGS_LAUNCH_CHECK(0, s);
+    int rc = exclusive_scan_u32(t.flag, nullptr, t.dense, n, reinterpret_cast<uint32_t*>(count), t.scan_tmp, s, 0);
+    if (rc != OGS_OK) return rc;
+    OGS_LAUNCH(components_number_kernel, rows, block, 0, s, n, (const uint32_t*)t.dense, comp);
+    OGS_LAUNCH_CHECK(0, s);
+    // the member lists: comp as an [n, 1] index table over n rows (-1 is an invalid slot there), a stable sort
+    rc = ogs_knn_transpose(n, 1, n, comp, t.begin, t.members, t.lists_tmp, t.lists_bytes, stream_);
+    if (rc != OGS_OK) return rc;
+    OGS_LAUNCH(components_sizes_kernel, rows, block, 0, s, n, (const int32_t*)t.begin, (const int32_t*)t.members,
+               (const int32_t*)anchor, sizes, first);
+    OGS_LAUNCH_CHECK(0, s);
+    return OGS_OK;
+}
+
 }  // namespace ogs
 
 using namespace ogs;
@@ -211,7 +183,8 @@ extern "C" {
 
 size_t ogs_knn_components_tmp_bytes(int64_t n) {
     if (n <= 0 || n >= ((int64_t)1 << 31)) return 0;
-    return ComponentsTmp::carve(nullptr, n).bytes;
+    Carver c(nullptr);
+    return ComponentsTmp::carve(c, n).bytes;
 }
 
 int ogs_knn_components(int64_t n, int32_t K, const int32_t* idx, const float* d2, const float* max_d2, const int32_t* labels,
@@ -227,7 +200,8 @@ int ogs_knn_components(int64_t n, int32_t K, const int32_t* idx, const float* d2
         return OGS_OK;
     }
     if (!idx || !comp || !sizes || !tmp) { set_error("knn_components: NULL pointer"); return OGS_ERR_INVALID_ARG; }
-    const ComponentsTmp t = ComponentsTmp::carve(tmp, n);
+    Carver c(tmp);
+    const ComponentsTmp t = ComponentsTmp::carve(c, n);
     if (tmp_bytes < t.bytes) {
         set_error("knn_components: tmp has %zu bytes, %zu needed (ogs_knn_components_tmp_bytes)", tmp_bytes, t.bytes);
         return OGS_ERR_INVALID_ARG;
@@ -236,24 +210,13 @@ int ogs_knn_components(int64_t n, int32_t K, const int32_t* idx, const float* d2
     if (!status_word) return OGS_ERR_HIP;
     const EdgeRule r{n, K, idx, d2, max_d2, labels};
     const int64_t E = n * (int64_t)K;
-    const dim3 rows((unsigned)blocks_for(n)), block(kBlock);
+    const dim3 block(kBlock);
     const int L = lanes_for_row(K);
     OGS_LAUNCH(components_init_kernel, dim3((unsigned)blocks_for(n * L)), block, 0, s, r, L, t.parent);
     OGS_LAUNCH_CHECK(0, s);
     OGS_LAUNCH(components_hook_kernel, dim3((unsigned)blocks_for(E)), block, 0, s, r, E, t.parent, status_word);
     OGS_LAUNCH_CHECK(0, s);
-    OGS_LAUNCH(components_flatten_kernel, rows, block, 0, s, n, labels, t.parent, comp, t.flag, status_word);
-    OGS_LAUNCH_CHECK(0, s);
-    int rc = exclusive_scan_u32(t.flag, nullptr, t.dense, n, reinterpret_cast<uint32_t*>(count), t.scan_tmp, s, 0);
-    if (rc != OGS_OK) return rc;
-    OGS_LAUNCH(components_number_kernel, rows, block, 0, s, n, (const uint32_t*)t.dense, comp);
-    OGS_LAUNCH_CHECK(0, s);
-    // the member lists: comp as an [n, 1] index table over n rows (-1 is an invalid slot there), a stable sort
-    rc = ogs_knn_transpose(n, 1, n, comp, t.begin, t.members, t.lists_tmp, t.lists_bytes, stream_);
-    if (rc != OGS_OK) return rc;
-    OGS_LAUNCH(components_sizes_kernel, rows, block, 0, s, n, (const int32_t*)t.begin, (const int32_t*)t.members, sizes, first);
-    OGS_LAUNCH_CHECK(0, s);
-    return OGS_OK;
+    return knn_components_tail(n, labels, nullptr, comp, sizes, first, count, t, stream_);
 }
 
 }  // extern "C"

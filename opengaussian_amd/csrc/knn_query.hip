@@ -26,36 +26,6 @@
 namespace ogs {
 namespace {
 
-struct IndexLayout {
-    KnnBoxes b;
-    size_t bytes;
-    static IndexLayout carve(void* p, int64_t n) {
-        Carver c(p);
-        IndexLayout t{};
-        const size_t nbox = (size_t)((n + kKnnBox - 1) / kKnnBox), npad = nbox * kKnnBox;
-        t.b.frame = c.take<float>(6);
-        t.b.sx = c.take<float>(npad); t.b.sy = c.take<float>(npad); t.b.sz = c.take<float>(npad);
-        t.b.sid = c.take<int32_t>(npad);
-        t.b.box = c.take<float>(6 * nbox);
-        t.b.first_key = c.take<uint32_t>(nbox);
-        t.bytes = c.off;
-        return t;
-    }
-};
-
-struct SortTmp {
-    KnnSortScratch sort;
-    size_t bytes;
-    static SortTmp carve(Carver& c, int64_t n) {
-        SortTmp t{};
-        t.sort.partial = c.take<float>((size_t)kBoundBlocks * 6);
-        for (int i = 0; i < 2; ++i) { t.sort.keys[i] = c.take<uint32_t>((size_t)n); t.sort.vals[i] = c.take<uint32_t>((size_t)n); }
-        t.sort.sort_tmp = c.take<char>(sort_tmp_bytes(n));
-        t.bytes = c.off;
-        return t;
-    }
-};
-
 struct QueryTmp {
     KnnSortScratch sort;
     KnnBoxes runs;                                      // the queries in runs of kKnnBox; no first_key, no frame

@@ -10,6 +10,10 @@
 ``Index`` /       the same search BETWEEN TWO point sets: an index of a reference set, built once, and the k <= 32 nearest
 ``query``         reference rows of every row of any other set, wherever it lies; ``query.transfer_labels`` /
                   ``transfer_features`` carry per-point results across on it.
+``radius_count``  how many rows lie within a radius of every row (``Index.radius_count`` for two sets): the same box walk with a
+                  fixed threshold, no neighbour list anywhere.
+``dbscan``        exact DBSCAN on that walk: core rows by ``min_pts``, clusters as the components of the core graph (the union
+                  made inside the second walk), border rows to their nearest core; memory O(n) whatever ``eps`` is.
 ``aggregate``     the fixed-degree gather-sum over such an index table (the step of a diffusion over the kNN graph).
 ``reverse_edges`` the reverse-edge lists of an index table: per target row, the slots that point at it.
 ``components``    the connected components of an index table under a distance threshold and a same-label rule: a lock-free
@@ -22,6 +26,8 @@ only where ``neighbors`` returns it).
 CPU tensors raise: there is no CPU path.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import torch
 
@@ -229,12 +235,113 @@ class Index:
               "ogs_knn_query")
         return idx, d2
 
+    def radius_count(self, queries: torch.Tensor, radius, labels=None, query_labels=None):
+        """How many reference rows lie within ``radius`` of every query row: int32 [m] (``ogs_knn_radius_count``: the walk of
+        ``query`` with a fixed threshold, so no list is kept and memory does not grow with the radius).
+
+        Row j counts for query q when ``d2(q, j) <= radius * radius`` in fp32 -- d2 as in ``query``, the square ONE fp32 multiply
+        made on the device, equality counts.  ``radius`` is a float >= 0 or a one-element device tensor (a NaN selects nothing,
+        +inf everything).  ``labels`` [n] / ``query_labels`` [m] go together: row j then counts only when both labels are equal
+        and >= 0.  Nothing is read back."""
+        q = _points_arg(queries, "queries")
+        if q.device != self.device:
+            raise ValueError(f"queries live on {q.device}, the index on {self.device}")
+        if (labels is None) != (query_labels is None):
+            raise ValueError("labels and query_labels are given together or not at all")
+        m = q.shape[0]
+        rl = _labels_arg(labels, self.n, "labels", self.device)
+        ql = _labels_arg(query_labels, m, "query_labels", self.device)
+        r2 = squared_on_device(radius, self.device, "radius")
+        count = torch.empty(m, dtype=torch.int32, device=self.device)
+        L = _lib.lib()
+        nbytes = int(L.ogs_knn_radius_count_tmp_bytes(self.n, m))
+        tmp = _tmp(nbytes, self.device)
+        check(L.ogs_knn_radius_count(self.n, ptr(self._buf), m, ptr(q), ptr(r2), ptr(rl), ptr(ql), ptr(count), ptr(tmp), nbytes,
+                                     _stream()), "ogs_knn_radius_count")
+        return count
+
+
+def squared_on_device(dist, dev, name="dist"):
+    """A distance squared as ONE fp32 multiply on the device, fp32 [1]: a float >= 0 or a one-element tensor"""
+    if isinstance(dist, torch.Tensor):
+        if dist.numel() != 1:
+            raise ValueError(f"{name} must be a number or a one-element tensor, got {tuple(dist.shape)}")
+        m = dist.detach().to(dev).to(torch.float32).reshape(1)
+    else:
+        if not float(dist) >= 0:
+            raise ValueError(f"{name} must be a distance >= 0, got {dist}")
+        m = torch.full((1,), float(dist), dtype=torch.float32, device=dev)
+    return m * m
+
+
+def _labels_arg(labels, n, name, dev):
+    if labels is None:
+        return None
+    _need_gpu(labels, name)
+    if labels.shape != (n,):
+        raise ValueError(f"{name} must be [{n}], got {tuple(labels.shape)}")
+    return labels.detach().to(dev).to(torch.int32).contiguous()
+
 
 def query(points: torch.Tensor, queries: torch.Tensor, k: int):
     """``Index(points).query(queries, k)``: the k nearest rows of ``points`` [n, 3] for every row of ``queries`` [m, 3], in one
     shot.  Keep the ``Index`` instead when the same reference set is asked more than once."""
     _points_arg(queries, "queries")                                 # both sets are checked before anything is built
     return Index(points).query(queries, k)
+
+
+def radius_count(points: torch.Tensor, radius, queries=None, labels=None, query_labels=None):
+    """``Index(points).radius_count(queries, radius, ...)`` in one shot; ``queries=None`` counts the set against itself (every
+    row then counts itself, and ``labels`` serves both sides)."""
+    if queries is None:
+        if query_labels is not None:
+            raise ValueError("query_labels needs queries")
+        queries, query_labels = points, labels
+    else:
+        _points_arg(queries, "queries")                             # both sets are checked before anything is built
+    return Index(points).radius_count(queries, radius, labels, query_labels)
+
+
+class Dbscan(NamedTuple):
+    cluster: torch.Tensor                               # int32 [n]: the row's cluster, -1 for noise and inactive rows
+    count: torch.Tensor                                 # int32 [1]: the number of clusters C, on the device
+    sizes: torch.Tensor                                 # int32 [n]: members of cluster c < C with its borders, 0 beyond
+    first: torch.Tensor                                 # int32 [n]: smallest CORE row of cluster c < C, -1 beyond
+    core: torch.Tensor                                  # bool [n]
+    degree: torch.Tensor                                # int32 [n]: rows within eps, the row itself included; 0 when inactive
+
+
+@torch.no_grad()
+def dbscan(points: torch.Tensor, eps, min_pts: int, labels=None) -> Dbscan:
+    """Exact DBSCAN of points [n, 3] (``ogs_knn_dbscan``): every pair within ``eps`` is seen, by two walks over the sorted boxes
+    of ``neighbors`` with a fixed threshold -- the first counts, the second unites -- so no neighbour list exists and memory is
+    O(n) whatever ``eps`` is.
+
+    Row i is active unless ``labels`` [n] holds a negative value for it.  N(i) is the set of active rows j with the same label
+    and ``d2(i, j) <= eps * eps`` in fp32 (d2 as in ``neighbors``, the square ONE fp32 multiply on the device; equality counts;
+    i itself is in N(i)).  ``degree = |N(i)|``, ``core = degree >= min_pts``.  Clusters are the connected components of the core
+    rows under "within each other's N"; a non-core row with a core in reach is a border row and joins the cluster of the core
+    with the smallest (d2, row) -- that one only, so a chain of border rows bridges nothing; every other row is noise (-1).
+    Clusters are numbered by ascending smallest core row.  ``eps``: a float >= 0 or a one-element device tensor.  The result is
+    unique, the same bytes every run; nothing is read back (``count`` stays on the device)."""
+    pts = _points_arg(points, "points")
+    n, dev = pts.shape[0], pts.device
+    if int(min_pts) < 1:
+        raise ValueError(f"min_pts must be at least 1, got {min_pts}")
+    lc = _labels_arg(labels, n, "labels", dev)
+    e2 = squared_on_device(eps, dev, "eps")
+    cluster = torch.empty(n, dtype=torch.int32, device=dev)
+    core = torch.empty(n, dtype=torch.uint8, device=dev)
+    degree = torch.empty(n, dtype=torch.int32, device=dev)
+    sizes = torch.empty(n, dtype=torch.int32, device=dev)
+    first = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    nbytes = int(L.ogs_knn_dbscan_tmp_bytes(n))
+    tmp = _tmp(nbytes, dev)
+    check(L.ogs_knn_dbscan(n, ptr(pts), ptr(e2), int(min_pts), ptr(lc), ptr(cluster), ptr(core), ptr(degree), ptr(sizes), ptr(first),
+                           ptr(count), ptr(tmp), nbytes, _stream()), "ogs_knn_dbscan")
+    return Dbscan(cluster, count, sizes, first, core.view(torch.bool), degree)
 
 
 @torch.no_grad()
@@ -315,8 +422,9 @@ def components(idx: torch.Tensor, d2=None, max_d2=None, labels=None):
     beyond).  The result is unique -- the same bytes every run, whatever the order of the slots within a row -- and nothing is
     read back: ``count`` stays on the device.
 
-    This is NOT DBSCAN: a table with K <= 32 columns does not hold every neighbour within a radius, so two rows closer than
-    ``max_d2`` whose lists are full of nearer rows are joined only through those."""
+    A table with K <= 32 columns does not hold every neighbour within a radius, so two rows closer than ``max_d2`` whose lists
+    are full of nearer rows are joined only through those, and there is no core-point rule: ``dbscan`` is the exact clustering
+    by radius."""
     _need_gpu(idx, "idx")
     if idx.dim() != 2 or idx.shape[1] < 1:
         raise ValueError(f"idx must be [n, K] with K >= 1, got {tuple(idx.shape)}")

@@ -1250,6 +1250,40 @@ def _neighbour_table(xyz, k, neighbors):
     return idx, d2
 
 
+def _instance_labels(xyz, labels, min_size, ignore):
+    """(lab, lab32) of the instance segmentations: the labels on the device, and as int32 with -1 on every row that belongs to no
+    instance (a negative label, or one that ``ignore`` names)"""
+    _need_gpu(xyz, "xyz")
+    _need_gpu(labels, "labels")
+    n, dev = xyz.shape[0] if xyz.dim() else -1, xyz.device
+    if labels.dim() != 1 or labels.shape[0] != n:
+        raise ValueError(f"labels must be [{n}], got {tuple(labels.shape)}")
+    if int(min_size) < 1:
+        raise ValueError(f"min_size must be at least 1, got {min_size}")
+    lab = labels.detach().to(dev)
+    active = lab >= 0
+    if ignore is not None:
+        if isinstance(ignore, torch.Tensor) and ignore.dtype is torch.bool:
+            if ignore.shape != lab.shape:
+                raise ValueError(f"a bool ignore marks rows and must be [{n}], got {tuple(ignore.shape)}")
+            active &= ~ignore.to(dev)
+        else:
+            active &= ~torch.isin(lab, torch.as_tensor(ignore, device=dev).to(lab.dtype).reshape(-1))
+    return lab, torch.where(active, lab, torch.full_like(lab, -1)).to(torch.int32)
+
+
+def _instances_of(comp, sizes, first, lab, min_size):
+    """The four values of the instance segmentations from numbered components: those with fewer than ``min_size`` members are
+    dropped, the rest renumbered in order"""
+    keep = sizes >= int(min_size)                                   # sizes past the count are 0
+    new_id = torch.cumsum(keep, dim=0, dtype=torch.int32) - 1
+    num = int(keep.sum())                                           # the one read-back
+    at = comp.clamp_min(0).to(torch.int64)
+    instance = torch.where((comp >= 0) & keep[at], new_id[at], torch.full_like(comp, -1))
+    kept = torch.argsort((~keep).to(torch.uint8), stable=True)[:num]            # the kept components, ascending
+    return instance, num, lab[first[kept].to(torch.int64)], sizes[kept]
+
+
 @torch.no_grad()
 def segment_instances(xyz, labels, k=16, max_dist=None, min_size=1, ignore=None, neighbors=None):
     """Per-point classes -> instances: the spatially connected pieces of every class, ``(instance, num_instances,
@@ -1263,34 +1297,29 @@ def segment_instances(xyz, labels, k=16, max_dist=None, min_size=1, ignore=None,
     order, so instances are numbered by ascending smallest member row.
 
     ``instance`` int32 [n] (-1: none), ``num_instances`` an int -- the one value this function reads back --,
-    ``instance_label`` [num] in the dtype of ``labels`` and ``instance_size`` int32 [num].  Not DBSCAN: a table of k <= 32
-    neighbours does not hold every point within ``max_dist`` (``knn.components``)."""
-    _need_gpu(xyz, "xyz")
-    _need_gpu(labels, "labels")
-    n, dev = xyz.shape[0] if xyz.dim() else -1, xyz.device
-    if labels.dim() != 1 or labels.shape[0] != n:
-        raise ValueError(f"labels must be [{n}], got {tuple(labels.shape)}")
-    if int(min_size) < 1:
-        raise ValueError(f"min_size must be at least 1, got {min_size}")
+    ``instance_label`` [num] in the dtype of ``labels`` and ``instance_size`` int32 [num].  A table of k <= 32 neighbours does
+    not hold every point within ``max_dist`` and has no core-point rule: ``segment_instances_dbscan`` is the exact form."""
+    lab, lab32 = _instance_labels(xyz, labels, min_size, ignore)
     idx, d2 = _neighbour_table(xyz, k, neighbors)
-    lab = labels.detach().to(dev)
-    active = lab >= 0
-    if ignore is not None:
-        if isinstance(ignore, torch.Tensor) and ignore.dtype is torch.bool:
-            if ignore.shape != lab.shape:
-                raise ValueError(f"a bool ignore marks rows and must be [{n}], got {tuple(ignore.shape)}")
-            active &= ~ignore.to(dev)
-        else:
-            active &= ~torch.isin(lab, torch.as_tensor(ignore, device=dev).to(lab.dtype).reshape(-1))
-    lab32 = torch.where(active, lab, torch.full_like(lab, -1)).to(torch.int32)
-    comp, _, sizes, first = _knn.components(idx, d2, _max_d2_of(max_dist, dev), lab32)
-    keep = sizes >= int(min_size)                                   # sizes past the count are 0
-    new_id = torch.cumsum(keep, dim=0, dtype=torch.int32) - 1
-    num = int(keep.sum())                                           # the one read-back
-    at = comp.clamp_min(0).to(torch.int64)
-    instance = torch.where((comp >= 0) & keep[at], new_id[at], torch.full_like(comp, -1))
-    kept = torch.argsort((~keep).to(torch.uint8), stable=True)[:num]            # the kept components, ascending
-    return instance, num, lab[first[kept].to(torch.int64)], sizes[kept]
+    comp, _, sizes, first = _knn.components(idx, d2, _max_d2_of(max_dist, lab.device), lab32)
+    return _instances_of(comp, sizes, first, lab, min_size)
+
+
+@torch.no_grad()
+def segment_instances_dbscan(xyz, labels, eps, min_pts=8, min_size=1, ignore=None):
+    """``segment_instances`` by exact DBSCAN instead of the kNN graph: ``(instance, num_instances, instance_label,
+    instance_size)`` with the same meaning, the same ``min_size`` / ``ignore`` handling and the same one read-back.
+
+    One ``knn.dbscan(xyz, eps, min_pts, labels)`` call under the same-label rule: a row is a core when at least ``min_pts`` rows
+    of its own label (itself included) lie within ``eps``; cores within ``eps`` of each other share an instance; a non-core row
+    joins the instance of its nearest core within ``eps`` and joins nothing else, so a thin bridge of sparse points between two
+    objects does not merge them; rows with no core in reach are noise (-1).  Instances are numbered by ascending smallest CORE
+    row, ``instance_size`` counts the border rows too."""
+    lab, lab32 = _instance_labels(xyz, labels, min_size, ignore)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"points must be [n, 3], got {tuple(xyz.shape)}")
+    r = _knn.dbscan(xyz, eps, min_pts, lab32)
+    return _instances_of(r.cluster, r.sizes, r.first, lab, min_size)
 
 
 @torch.no_grad()
@@ -1304,7 +1333,36 @@ def component_filter(points, group=None, num_groups=1, k=16, max_dist=None, min_
     ``min_share=None`` keeps the largest component of every group (equal sizes: the one whose smallest row comes first);
     otherwise every component with ``size >= min_share * rows of its group`` (compared in fp64) is kept.  The per-group
     reduction runs over per-component tensors in torch; nothing is read back.  Use: ``render_queries(..., pre_mask=
-    component_filter(xyz, leaf_group, num_groups))``."""
+    component_filter(xyz, leaf_group, num_groups))``.  ``density_filter`` is the same filter on exact DBSCAN clusters: every
+    point within ``eps`` counts, and a thin chain of sparse points joins nothing."""
+    lab, G = _filter_groups(points, group, num_groups, min_share)
+    idx, d2 = _neighbour_table(points, k, None)
+    comp, _, sizes, first = _knn.components(idx, d2, _max_d2_of(max_dist, points.device), lab)
+    return _keep_bulk(comp, sizes, first, lab, G, min_share)
+
+
+@torch.no_grad()
+def density_filter(points, group=None, num_groups=1, eps=None, min_pts=8, min_share=None):
+    """``component_filter`` by exact DBSCAN: keep-mask bool [n] that keeps the dense bulk of every group and drops sparse points AND
+    dense floaters beside it.
+
+    All groups go through one ``knn.dbscan(points, eps, min_pts, group)`` call: clusters never cross groups, a row is kept when
+    its cluster is; noise rows, and rows with an id outside ``[0, num_groups)``, are not kept.  ``min_share=None`` keeps the
+    largest cluster of every group (equal sizes: the one whose smallest core row comes first); otherwise every cluster with
+    ``size >= min_share * clustered rows of its group`` (compared in fp64).  ``eps`` is required: a float >= 0 or a one-element
+    device tensor.  Nothing is read back.  Use: ``render_queries(..., pre_mask=density_filter(xyz, leaf_group, num_groups,
+    eps=...))``."""
+    if eps is None:
+        raise ValueError("density_filter needs eps")
+    lab, G = _filter_groups(points, group, num_groups, min_share)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be [n, 3], got {tuple(points.shape)}")
+    r = _knn.dbscan(points, eps, min_pts, lab)
+    return _keep_bulk(r.cluster, r.sizes, r.first, lab, G, min_share)
+
+
+def _filter_groups(points, group, num_groups, min_share):
+    """(lab int32 [n], G) of the bulk filters: the group of every row, -1 outside ``[0, num_groups)``"""
     _need_gpu(points, "points")
     n, dev, G = points.shape[0] if points.dim() else -1, points.device, int(num_groups)
     if G < 1:
@@ -1320,8 +1378,12 @@ def component_filter(points, group=None, num_groups=1, k=16, max_dist=None, min_
         if group.shape != (n,):
             raise ValueError(f"group must be [{n}], got {tuple(group.shape)}")
         lab = torch.where((group < 0) | (group >= G), -1, group).to(torch.int32)
-    idx, d2 = _neighbour_table(points, k, None)
-    comp, _, sizes, first = _knn.components(idx, d2, _max_d2_of(max_dist, dev), lab)
+    return lab, G
+
+
+def _keep_bulk(comp, sizes, first, lab, G, min_share):
+    """The per-group reduction of the bulk filters over numbered components"""
+    n, dev = comp.shape[0], comp.device
     # per component c (tensors of n entries, the ones past the count hold first = -1): its group, slot G for none
     real = first >= 0
     cgroup = torch.where(real, lab[first.clamp_min(0).to(torch.int64)], torch.full_like(first, G)).to(torch.int64)
