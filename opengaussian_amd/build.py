@@ -32,9 +32,12 @@ EXTRA = {
     "refine.hip": ["-ffp-contract=off"],
     # squared distances as (dx*dx + dy*dy) + dz*dz, the bits tests/knn_restatement.py computes
     "knn.hip": ["-ffp-contract=off"],
-    # the same d2 bits, and a box lower bound that is the same expression on the per-axis gaps: monotone only uncontracted
+    # the K-nearest search over sorted boxes (the walk of csrc/knn_boxes.h): the same d2 bits, and a box lower bound that is the same
+    # expression on the per-axis gaps: monotone only uncontracted
+    "knn_search.hip": ["-ffp-contract=off"],
+    # the sort into boxes and the gather-sum, whose every fmaf is written out
     "knn_neighbors.hip": ["-ffp-contract=off"],
-    # the same walk (csrc/knn_boxes.h) between two point sets: the same d2 bits and the same monotone bound
+    # the index and the start boxes of a two-set search: Morton cells as the sort of knn_neighbors.hip makes them
     "knn_query.hip": ["-ffp-contract=off"],
     # the same walk with a fixed threshold (radius counts, DBSCAN): the same d2 bits and the same monotone bound
     "knn_radius.hip": ["-ffp-contract=off"],

@@ -1,11 +1,21 @@
-// What the exact neighbour searches share: the sorted-box front half and the search kernel (internal; the C ABI is
-// include/ogs_knn.h).
+// What the exact neighbour searches share: the sorted set, its carve, the bound of a box and the lane of a walk (internal; the C ABI
+// is include/ogs_knn.h).
 //
-// knn_sort_into_boxes (knn_neighbors.hip) is the front half of ogs_knn_neighbors, the whole of ogs_knn_index_build, and what groups
-// the queries of ogs_knn_query:
+// THE SORTED SET.  knn_sort_into_boxes (knn_neighbors.hip) is the front half of ogs_knn_neighbors and ogs_knn_dbscan, the whole of
+// ogs_knn_index_build, and what groups the queries of ogs_knn_query and ogs_knn_radius_count:
 //   bounding box -> 30-bit Morton keys -> four stable radix passes -> coordinates gathered into sorted order, NaN-padded to whole
-//   boxes of kKnnBox points, with the sorted ids and the axis-aligned bounds of every box.
-// knn_search_kernel is the search both run: a wave of 64 queries, one per lane, against boxes visited outward from a start box.
+//   BOXES of kKnnBox = 64 points, with the sorted ids and the axis-aligned bounds of every box.
+//
+// THE WALK.  One single-wave workgroup owns one RUN of kKnnBox consecutive sorted queries, one query per lane (KnnLane); the
+// run is a box of its own set, so it has bounds.  Candidate boxes are tested 64 at a time, one per lane, by the lower bound of d2
+// between the run's bounds and the candidate's (KnnLane::bound: the expression, and why it needs no margin), and a box is skipped only when that bound is STRICTLY above the
+// walk's threshold.  A visited box is staged in LDS coordinate by coordinate and read with broadcast 16-byte reads, four points of
+// one coordinate at a time; every lane tests its query against all 64 points with d2 = (dx*dx + dy*dy) + dz*dz (the files that
+// hold a walk are compiled with -ffp-contract=off).  A padding lane or point has NaN coordinates and the id kNoId: its d2 is a
+// NaN and compares false with everything.  Two kernels walk, each with a staging and a pair loop of its own:
+//   knn_search_kernel (knn_search.hip)    the threshold is the largest K-th d2 of the wave's queries and falls; boxes are visited
+//                                         outward from a start box
+//   radius_walk_kernel (knn_radius.hip)   the threshold is fixed; boxes are visited in index order
 #pragma once
 
 #include "ogs_common.h"
@@ -20,6 +30,10 @@ constexpr int kBoundBlocks = 256;                       // workgroups (and parti
 constexpr int kNoId = INT_MAX;                          // id of an empty list slot and of a padding point: above every real id
 static_assert(kBoundBlocks <= kBlock, "one thread folds one partial record");
 
+constexpr int64_t knn_nbox(int64_t n) { return (n + kKnnBox - 1) / kKnnBox; }      // boxes of n points, runs of n queries
+// a set the searches take: its padded rows and its box count fit an int
+inline bool knn_size_ok(int64_t n) { return n >= 0 && n <= (int64_t)INT32_MAX - kKnnBox; }
+
 struct KnnSortScratch {                                 // only needed while knn_sort_into_boxes runs
     float* partial;                                     // [kBoundBlocks][6] min xyz, max xyz
     uint32_t* keys[2];                                  // [n] Morton keys, ping-pong; keys[0] holds the sorted keys at the end
@@ -33,10 +47,27 @@ struct KnnBoxes {                                       // what a search reads o
     float* box;                                         // [6][nbox] min xyz, max xyz of every box
     uint32_t* first_key;                                // [nbox] Morton key of every box's first point; may be nullptr
     float* frame;                                       // [6] min xyz, max xyz of the set: the frame of its keys; may be nullptr
+    // the sorted set of n points; keyed: with first_key and frame (what a start box is found by)
+    static KnnBoxes carve(Carver& c, int64_t n, bool keyed) {
+        KnnBoxes b{};
+        const size_t nbox = (size_t)knn_nbox(n), npad = nbox * kKnnBox;
+        if (keyed) b.frame = c.take<float>(6);
+        b.sx = c.take<float>(npad); b.sy = c.take<float>(npad); b.sz = c.take<float>(npad);
+        b.sid = c.take<int32_t>(npad);
+        b.box = c.take<float>(6 * nbox);
+        if (keyed) b.first_key = c.take<uint32_t>(nbox);
+        return b;
+    }
 };
 
 // n in [1, INT32_MAX - kKnnBox]; pts [n, 3]; everything else as the structs say.  No read-back, nothing waits on another workgroup.
 int knn_sort_into_boxes(int n, const float* pts, const KnnSortScratch& t, const KnnBoxes& out, hipStream_t s);
+
+// The search (knn_search.hip): nruns runs of the sorted queries q against the nbox boxes of r, outward from box start[run]; K in
+// [1, kKnnMaxK] rounds up to the next list size the search is compiled for.  One set against itself: q == r, start == nullptr
+// (a run starts at itself), nruns == nbox.
+int knn_launch_search(int nruns, int nbox, int K, int exclude_self, const KnnBoxes& q, const int32_t* start, const KnnBoxes& r,
+                      int32_t* idx, float* d2, hipStream_t s);
 
 // the persistent index of a point set (ogs_knn_index_build): what ogs_knn_query and ogs_knn_radius_count carve out of `index`
 struct IndexLayout {
@@ -45,12 +76,7 @@ struct IndexLayout {
     static IndexLayout carve(void* p, int64_t n) {
         Carver c(p);
         IndexLayout t{};
-        const size_t nbox = (size_t)((n + kKnnBox - 1) / kKnnBox), npad = nbox * kKnnBox;
-        t.b.frame = c.take<float>(6);
-        t.b.sx = c.take<float>(npad); t.b.sy = c.take<float>(npad); t.b.sz = c.take<float>(npad);
-        t.b.sid = c.take<int32_t>(npad);
-        t.b.box = c.take<float>(6 * nbox);
-        t.b.first_key = c.take<uint32_t>(nbox);
+        t.b = KnnBoxes::carve(c, n, true);
         t.bytes = c.off;
         return t;
     }
@@ -69,6 +95,34 @@ struct SortTmp {
         return t;
     }
 };
+
+// tmp of a call that sorts one set and walks it: the sort's scratch and the set, unkeyed (ogs_knn_neighbors; with start, the queries
+// of ogs_knn_query; without, those of ogs_knn_radius_count; ogs_knn_dbscan goes on carving from c)
+struct SortedTmp {
+    KnnSortScratch sort;
+    KnnBoxes boxes;
+    int32_t* start;                                     // [nbox] start box of every run; with_start only
+    size_t bytes;
+    static SortedTmp carve(Carver& c, int64_t n, bool with_start = false) {
+        SortedTmp t{};
+        t.sort = SortTmp::carve(c, n).sort;
+        t.boxes = KnnBoxes::carve(c, n, false);
+        if (with_start) t.start = c.take<int32_t>((size_t)knn_nbox(n));
+        t.bytes = c.off;
+        return t;
+    }
+};
+
+// The front half of the two-set calls (knn_query.hip), after their own argument checks: tmp [tmp_bytes] is checked against
+// SortedTmp of the m queries (the error names ogs_<name>_tmp_bytes), the index of n points is carved, read only from here on, and
+// the queries are sorted into runs.
+struct KnnTwoSets {
+    KnnBoxes q, r;                                      // the queries in runs, the reference in boxes
+    int32_t* start;                                     // [nruns], not filled; with_start only
+    int nruns, nbox;
+};
+int knn_sort_queries(int64_t n, const void* index, int64_t m, const float* queries, void* tmp, size_t tmp_bytes, const char* name,
+                     bool with_start, hipStream_t s, KnnTwoSets& out);
 
 __device__ __forceinline__ float wave_min_f(float v) {
     for (int m = kWave / 2; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, kWave));
@@ -111,144 +165,45 @@ __device__ __forceinline__ bool knn_before(float d, int j, float bd, int bi) {
     return d < bd || (d == bd && j < bi);
 }
 
-// offset o of the outward walk: 0, +1, -1, +2, -2, ...
-__device__ __forceinline__ int knn_delta(int o) { return (o & 1) ? (o + 1) >> 1 : -(o >> 1); }
+// One lane of a walk: its query and the bounds of its run.  Registers only.  (radius_walk_kernel keeps this set-up and the bound
+// written out in its own text, for a measured reason it states; what it writes out must stay equal to these.)
+struct KnnLane {
+    float qx, qy, qz;                                   // NaN in a padding lane
+    int qid;                                            // the query's row in the caller's order; kNoId in a padding lane
+    bool valid;
+    float qlo[3], qhi[3];                               // the run's bounds (wave-uniform)
 
-#ifndef OGS_KNN_BOXES_NO_SEARCH     // knn_radius.hip walks the boxes with a kernel of its own and wants no copy of this one
-namespace {        // internal linkage: every file that includes this builds and registers its own copy of the kernel (no -fgpu-rdc)
-
-// The search: one single-wave workgroup per RUN of kKnnBox queries (gridDim.x runs), one query per lane.  The queries are the
-// sorted set (qsx, qsy, qsz, qsid, qbox) -- NaN coordinates and qsid = kNoId in a padding lane, where nothing is ever inserted --
-// and the candidates the sorted set (sx, sy, sz, sid, box) of nbox boxes; ogs_knn_neighbors passes the same set twice.  The
-// candidate boxes are visited outward in sorted order from a start box: start[run] (clamped to [0, nbox)), or, with
-// start == nullptr, box `run` itself (one set: the run IS that box).  64 candidates at a time, one per lane, are tested against
-// the run's bounds, and a box is skipped when its lower bound is STRICTLY above the largest K-th d2 of the wave's queries (an
-// equal distance with a smaller id still displaces).  The lower bound is the d2 expression itself on the per-axis gaps
-// max(lo_c - hi_q, lo_q - hi_c, 0): round-to-nearest subtraction, product and sum are monotone, so the bound is <= the computed
-// fp32 d2 of every pair of the two boxes and needs no safety margin -- wherever the walk starts: it reaches every box, and the
-// start only decides how fast the threshold falls.  A visited box is staged in LDS coordinate by coordinate and read with
-// broadcast 16-byte reads, four points of one coordinate at a time.  With exclude_self a candidate whose id is the query's own
-// is left out.  Row qsid of idx_out / d2_out [*, K] takes the first K pairs of the lane's list; an empty slot is (-1, +inf).
-template <int KT>
-__global__ __launch_bounds__(kKnnBox) void knn_search_kernel(int nbox, int K, int exclude_self, const float* __restrict__ qsx,
-                                                             const float* __restrict__ qsy, const float* __restrict__ qsz,
-                                                             const int32_t* __restrict__ qsid, const float* __restrict__ qbox,
-                                                             const int32_t* __restrict__ start, const float* __restrict__ sx,
-                                                             const float* __restrict__ sy, const float* __restrict__ sz,
-                                                             const int32_t* __restrict__ sid, const float* __restrict__ box,
-                                                             int32_t* __restrict__ idx_out, float* __restrict__ d2_out) {
-    __shared__ __attribute__((aligned(16))) float cx[kKnnBox], cy[kKnnBox], cz[kKnnBox];
-    __shared__ __attribute__((aligned(16))) int cid[kKnnBox];
-    const int lane = threadIdx.x, run = blockIdx.x, nruns = gridDim.x;
-    const int b = start ? min(max(start[run], 0), nbox - 1) : run;
-    const size_t p = (size_t)run * kKnnBox + lane;
-    const float qx = qsx[p], qy = qsy[p], qz = qsz[p];
-    const int qid = qsid[p];
-    const bool valid = qid != kNoId;
-    const int self = exclude_self ? qid : -1;
-    float qlo[3], qhi[3];
+    // lane `lane` of run `run` of the sorted set (qsx, qsy, qsz, qsid, qbox) of nruns runs
+    __device__ __forceinline__ void load(int run, int nruns, int lane, const float* __restrict__ qsx, const float* __restrict__ qsy,
+                                         const float* __restrict__ qsz, const int32_t* __restrict__ qsid,
+                                         const float* __restrict__ qbox) {
+        const size_t p = (size_t)run * kKnnBox + lane;
+        qx = qsx[p]; qy = qsy[p]; qz = qsz[p];
+        qid = qsid[p];
+        valid = qid != kNoId;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { qlo[a] = qbox[(size_t)a * nruns + run]; qhi[a] = qbox[(size_t)(3 + a) * nruns + run]; }
-
-    float bd[KT];
-    int bi[KT];
-#pragma unroll
-    for (int k = 0; k < KT; ++k) { bd[k] = INFINITY; bi[k] = kNoId; }
-
-    float T = INFINITY;                                            // largest K-th d2 among the wave's queries
-    const int reach = max(b, nbox - 1 - b);                        // |delta| of the farthest box
-    for (int o0 = 0; o0 <= 2 * reach; o0 += kKnnBox) {
-        // ---- 64 candidate boxes, one per lane: the lower bound of d2 between the two boxes --------------------------------
-        const int c = b + knn_delta(o0 + lane);
-        const bool inside = c >= 0 && c < nbox;
-        float lb = 0.f;
-        if (inside) {
-            float g[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float clo = box[(size_t)a * nbox + c], chi = box[(size_t)(3 + a) * nbox + c];
-                g[a] = fmaxf(fmaxf(clo - qhi[a], qlo[a] - chi), 0.f);
-            }
-            lb = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
-        }
-        unsigned long long todo = __ballot(inside && !(lb > T));    // (a NaN bound is visited)
-        while (todo) {
-            const int l = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const float lbl = __shfl(lb, l, kWave);
-            if (lbl > T) continue;                                 // T has fallen since the ballot (wave-uniform)
-            const int cb = b + knn_delta(o0 + l);                  // in [0, nbox): lane l was `inside`
-            // ---- stage the box, then every query against its 64 points -----------------------------------------------------
-            const size_t cp = (size_t)cb * kKnnBox + lane;
-            const float lx = sx[cp], ly = sy[cp], lz = sz[cp];
-            const int lid = sid[cp];
-            __syncthreads();                                       // the previous box has been consumed
-            cx[lane] = lx; cy[lane] = ly; cz[lane] = lz; cid[lane] = lid;
-            __syncthreads();
-#pragma unroll 2
-            for (int v = 0; v < kKnnBox; v += 4) {
-                const float4 x4 = *reinterpret_cast<const float4*>(cx + v);
-                const float4 y4 = *reinterpret_cast<const float4*>(cy + v);
-                const float4 z4 = *reinterpret_cast<const float4*>(cz + v);
-                const int4 i4 = *reinterpret_cast<const int4*>(cid + v);
-                const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, ys[4] = {y4.x, y4.y, y4.z, y4.w}, zs[4] = {z4.x, z4.y, z4.z, z4.w};
-                const int js[4] = {i4.x, i4.y, i4.z, i4.w};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float dx = qx - xs[u], dy = qy - ys[u], dz = qz - zs[u];
-                    const float d = (dx * dx + dy * dy) + dz * dz;  // NaN for a padding point: before nothing
-                    const int j = js[u];
-                    if (knn_before(d, j, bd[KT - 1], bi[KT - 1]) && j != self) {
-                        // slot k takes the candidate where it goes before slot k but not before slot k - 1, and the old
-                        // slot k - 1 where it goes before both; static indices only
-#pragma unroll
-                        for (int k = KT - 1; k >= 1; --k) {
-                            const bool here = knn_before(d, j, bd[k], bi[k]), above = knn_before(d, j, bd[k - 1], bi[k - 1]);
-                            bd[k] = here ? (above ? bd[k - 1] : d) : bd[k];
-                            bi[k] = here ? (above ? bi[k - 1] : j) : bi[k];
-                        }
-                        if (knn_before(d, j, bd[0], bi[0])) { bd[0] = d; bi[0] = j; }
-                    }
-                }
-            }
-            float kth = bd[KT - 1];
-#pragma unroll
-            for (int k = 0; k < KT - 1; ++k) kth = k == K - 1 ? bd[k] : kth;
-            T = wave_max_f(valid ? kth : -INFINITY);
-        }
+        for (int a = 0; a < 3; ++a) { qlo[a] = qbox[(size_t)a * nruns + run]; qhi[a] = qbox[(size_t)(3 + a) * nruns + run]; }
     }
-    if (!valid) return;
-    const size_t o = (size_t)qid * (size_t)K;                      // qid in [0, rows of the query set): clamped by the gather
+
+    // Lower bound of the computed fp32 d2 between any query of the run and any point of box c in [0, nbox) of
+    // `box`: the d2 expression itself on the per-axis gaps g = max(lo_c - hi_q, lo_q - hi_c, 0).  It needs no safety margin.  For a
+    // pair (q, p) of the two boxes and an axis where g > 0, say lo_c > hi_q: p >= lo_c and q <= hi_q, and the round-to-nearest
+    // difference is monotone in either operand -- rounding maps a larger exact value to a larger or equal float, and is symmetric in
+    // the sign -- so |q - p| as computed is >= lo_c - hi_q as computed, which is g; where g = 0 there is nothing to show.  All values are
+    // then non-negative, where the rounded product and the rounded sum are monotone in both operands for the same reason, so each
+    // term of (g0*g0 + g1*g1) + g2*g2 is <= the matching term of (dx*dx + dy*dy) + dz*dz, in the same order of operations -- which is
+    // why the two must stay the same expression and uncontracted: an fma rounds once where the other side rounds twice.
+    // fmaxf drops a NaN (a box of NaN points, inf - inf): that axis then contributes no gap and skips nothing; should a bound come
+    // out a NaN all the same, every walk tests `!(lb > T)` and visits the box.
+    __device__ __forceinline__ float bound(const float* __restrict__ box, int nbox, int c) const {
+        float g[3];
 #pragma unroll
-    for (int k = 0; k < KT; ++k) {
-        if (k < K) {
-            const bool filled = bi[k] != kNoId;
-            idx_out[o + k] = filled ? bi[k] : -1;
-            d2_out[o + k] = filled ? bd[k] : INFINITY;
+        for (int a = 0; a < 3; ++a) {
+            const float clo = box[(size_t)a * nbox + c], chi = box[(size_t)(3 + a) * nbox + c];
+            g[a] = fmaxf(fmaxf(clo - qhi[a], qlo[a] - chi), 0.f);
         }
+        return (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
     }
-}
-
-template <int KT>
-int knn_launch_search_lists(int nruns, int nbox, int K, int exclude_self, const KnnBoxes& q, const int32_t* start,
-                            const KnnBoxes& r, int32_t* idx, float* d2, hipStream_t s) {
-    OGS_LAUNCH(knn_search_kernel<KT>, dim3((unsigned)nruns), dim3(kKnnBox), 0, s, nbox, K, exclude_self, q.sx, q.sy, q.sz, q.sid,
-               q.box, start, r.sx, r.sy, r.sz, r.sid, r.box, idx, d2);
-    OGS_LAUNCH_CHECK(0, s);
-    return OGS_OK;
-}
-
-// nruns runs of the sorted queries q against the nbox boxes of r; K in [1, kKnnMaxK] rounds up to the next list size the search
-// is compiled for.  One set against itself: q == r, start == nullptr, nruns == nbox.
-int knn_launch_search(int nruns, int nbox, int K, int exclude_self, const KnnBoxes& q, const int32_t* start, const KnnBoxes& r,
-                      int32_t* idx, float* d2, hipStream_t s) {
-    if (K <= 4) return knn_launch_search_lists<4>(nruns, nbox, K, exclude_self, q, start, r, idx, d2, s);
-    if (K <= 8) return knn_launch_search_lists<8>(nruns, nbox, K, exclude_self, q, start, r, idx, d2, s);
-    if (K <= 16) return knn_launch_search_lists<16>(nruns, nbox, K, exclude_self, q, start, r, idx, d2, s);
-    return knn_launch_search_lists<32>(nruns, nbox, K, exclude_self, q, start, r, idx, d2, s);
-}
-
-}  // namespace
-#endif
+};
 
 }  // namespace ogs

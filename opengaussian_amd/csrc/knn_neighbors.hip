@@ -1,53 +1,23 @@
 // Exact K nearest neighbours WITH indices at scene scale, and the fixed-degree gather-sum over them (include/ogs_knn.h).
 //
-// ogs_knn_neighbors: sort once, search in boxes.
+// ogs_knn_neighbors: sort once, search in boxes.  This file holds the sort -- knn_sort_into_boxes, the front half every search
+// over sorted boxes begins with (knn_boxes.h describes the sorted set and the walk over it):
 //   1. bounding box of the cloud (two stages: per-workgroup partials, folded again by every workgroup of the key kernel),
 //   2. a 30-bit Morton key per point (10 bits per axis, every cell clamped to [0, 1023] whatever the coordinate is),
 //   3. (key, id) sorted by four stable radix passes (binning.hip; the three-launch passes: nothing waits on another workgroup),
-//   4. the coordinates gathered into sorted order, coordinate-wise, and the axis-aligned bounds of every run of kKnnBox = 64
-//      consecutive sorted points (a BOX),
-//   5. the search: one wave owns one box of queries, one query per lane.  A lane keeps its K best (d2, id) pairs in registers
-//      as a sorted list (templated on 4 / 8 / 16 / 32; a requested K rounds up and the first K pairs are stored).  Candidate
-//      boxes are visited outward from the own box in sorted order: 64 candidates at a time, one per lane, are tested against
-//      the own box's bounds, and a box is skipped when its lower bound is STRICTLY above the largest K-th d2 of the wave's
-//      queries (an equal distance with a smaller id still displaces).  The lower bound is the d2 expression itself on the
-//      per-axis gaps max(lo_c - hi_q, lo_q - hi_c, 0): round-to-nearest subtraction, product and sum are monotone, so the
-//      bound is <= the computed fp32 d2 of every pair of the two boxes and needs no safety margin.  A visited box is staged in
-//      LDS coordinate by coordinate and read with broadcast 16-byte reads, four points of one coordinate at a time.
-//      A cloud that cannot be pruned (all points coincident: every bound and every K-th value is 0) visits every box: one brute
-//      pass of n^2 pairs, still correct.
-//   The order (d2, id) is total, so the result is unique and does not depend on the order of visits.
-//   Steps 1-4 are knn_sort_into_boxes (defined here, declared in knn_boxes.h) and the kernel of step 5 is knn_search_kernel
-//   (knn_boxes.h): knn_query.hip runs both on two point sets.
+//   4. the coordinates gathered into sorted order, coordinate-wise, and the axis-aligned bounds of every box.
+// The search itself is knn_search_kernel (knn_search.hip), here with the set against itself: a run of queries IS a box, and its walk
+// starts there.
 //
 // ogs_knn_aggregate: out[i, c] = sum_k w[i, k] * X[idx[i, k], c] as one fmaf chain per element, k ascending, one thread per
 // output element (per four columns where D and the bases allow 16-byte accesses); no [n, K, D] buffer, no atomics.
 //
-// This file is compiled with -ffp-contract=off: d2 = (dx*dx + dy*dy) + dz*dz, exactly so (the fmaf of the aggregate is explicit).
+// This file is compiled with -ffp-contract=off: every fmaf of the aggregate is written out, and nothing else here may become one.
 #include "knn_boxes.h"
 #include "../../include/ogs_knn.h"
 
 namespace ogs {
 namespace {
-
-struct NeighborsTmp {
-    KnnSortScratch sort;
-    KnnBoxes boxes;                                     // without first_key / frame: the search starts at the own box
-    size_t bytes;
-    static NeighborsTmp carve(void* p, int64_t n) {
-        Carver c(p);
-        NeighborsTmp t{};
-        const size_t nbox = (size_t)((n + kKnnBox - 1) / kKnnBox), npad = nbox * kKnnBox;
-        t.sort.partial = c.take<float>((size_t)kBoundBlocks * 6);
-        for (int i = 0; i < 2; ++i) { t.sort.keys[i] = c.take<uint32_t>((size_t)n); t.sort.vals[i] = c.take<uint32_t>((size_t)n); }
-        t.boxes.sx = c.take<float>(npad); t.boxes.sy = c.take<float>(npad); t.boxes.sz = c.take<float>(npad);
-        t.boxes.sid = c.take<int32_t>(npad);
-        t.boxes.box = c.take<float>(6 * nbox);
-        t.sort.sort_tmp = c.take<char>(sort_tmp_bytes(n));
-        t.bytes = c.off;
-        return t;
-    }
-};
 
 // min / max of six values over the workgroup; every thread returns with the result.  fminf / fmaxf drop NaNs.
 __device__ __forceinline__ void block_bounds(float (&lo)[3], float (&hi)[3], float (*sh)[6]) {
@@ -171,7 +141,7 @@ __global__ __launch_bounds__(kBlock) void knn_aggregate_kernel(int64_t total, in
 }  // namespace
 
 int knn_sort_into_boxes(int n, const float* pts, const KnnSortScratch& t, const KnnBoxes& out, hipStream_t s) {
-    const int nbox = (n + kKnnBox - 1) / kKnnBox;
+    const int nbox = (int)knn_nbox(n);
     const int nparts = min(kBoundBlocks, (n + kBlock - 1) / kBlock);
     OGS_LAUNCH(knn_bounds_kernel, dim3((unsigned)nparts), dim3(kBlock), 0, s, n, pts, t.partial);
     OGS_LAUNCH_CHECK(0, s);
@@ -201,25 +171,27 @@ size_t ogs_knn_box_points(void) { return kKnnBox; }
 size_t ogs_knn_max_k(void) { return kKnnMaxK; }
 
 size_t ogs_knn_neighbors_tmp_bytes(int64_t n) {
-    if (n <= 0 || n > (int64_t)INT32_MAX - kKnnBox) return 0;
-    return NeighborsTmp::carve(nullptr, n).bytes;
+    if (n <= 0 || !knn_size_ok(n)) return 0;
+    Carver c(nullptr);
+    return SortedTmp::carve(c, n).bytes;
 }
 
 int ogs_knn_neighbors(int64_t n, const float* points, int32_t K, int32_t exclude_self, int32_t* idx, float* d2, void* tmp,
                       size_t tmp_bytes, void* stream_) {
-    if (n < 0 || n > (int64_t)INT32_MAX - kKnnBox || K < 1 || K > kKnnMaxK || n * (int64_t)K >= ((int64_t)1 << 31)) {
+    if (!knn_size_ok(n) || K < 1 || K > kKnnMaxK || n * (int64_t)K >= ((int64_t)1 << 31)) {
         set_error("knn_neighbors: bad sizes (n=%lld K=%d; 1 <= K <= %d, n * K < 2^31)", (long long)n, K, kKnnMaxK);
         return OGS_ERR_INVALID_ARG;
     }
     if (n == 0) return OGS_OK;
     if (!points || !idx || !d2 || !tmp) { set_error("knn_neighbors: NULL pointer"); return OGS_ERR_INVALID_ARG; }
-    const NeighborsTmp t = NeighborsTmp::carve(tmp, n);
+    Carver c(tmp);
+    const SortedTmp t = SortedTmp::carve(c, n);                    // unkeyed: the search starts at the own box
     if (tmp_bytes < t.bytes) {
         set_error("knn_neighbors: tmp has %zu bytes, %zu needed (ogs_knn_neighbors_tmp_bytes)", tmp_bytes, t.bytes);
         return OGS_ERR_INVALID_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    const int ni = (int)n, nbox = (ni + kKnnBox - 1) / kKnnBox;
+    const int ni = (int)n, nbox = (int)knn_nbox(n);
     const int rc = knn_sort_into_boxes(ni, points, t.sort, t.boxes, s);
     if (rc != OGS_OK) return rc;
     return knn_launch_search(nbox, nbox, K, exclude_self ? 1 : 0, t.boxes, nullptr, t.boxes, idx, d2, s);

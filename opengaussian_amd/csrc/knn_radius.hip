@@ -1,14 +1,11 @@
 // Every point within a radius, without a neighbour list: radius counts over a persistent index and exact DBSCAN
 // (include/ogs_knn.h: ogs_knn_radius_count, ogs_knn_dbscan).
 //
-// The walk is the one of knn_search_kernel (knn_boxes.h) with a FIXED threshold instead of a falling K-th distance: one
-// single-wave workgroup per run of kKnnBox = 64 sorted queries, one query per lane; 64 candidate boxes per round are tested
-// against the run's bounds with the same lower-bound expression, and a box is visited unless lb > r2 (strict; a NaN bound is
-// visited).  The threshold never moves, so the order of the visits does not matter: the boxes are walked in index order and
-// there is no start box.  A visited box is staged in LDS coordinate by coordinate and read with broadcast 16-byte reads.  The
-// pair test is d2 <= r2 as an fp32 compare: equality counts, a NaN on either side counts nothing, and the NaN coordinates of a
-// padding point make its d2 a NaN.  r2 is a DEVICE scalar; when it is a NaN or negative no pair can pass and the walk is skipped
-// (every box would be visited otherwise, to count nothing).
+// The walk of knn_boxes.h with a FIXED threshold r2 instead of the falling K-th distance of knn_search.hip: a box is visited
+// unless its bound is above r2.  The threshold never moves, so the order of the visits does not matter: the boxes are walked in
+// index order and there is no start box.  The pair test is d2 <= r2 as an fp32 compare: equality counts, a NaN on either side
+// counts nothing, and the NaN coordinates of a padding point make its d2 a NaN.  r2 is a DEVICE scalar; when it is a NaN or
+// negative no pair can pass and the walk is skipped (every box would be visited otherwise, to count nothing).
 //
 // Labels ride along as one more LDS word per candidate, the TAG, gathered through sid while the box is staged: the candidate's
 // label when it is >= 0, -1 otherwise; the query's tag is its label when that is >= 0 and INT_MIN otherwise, so that "same label,
@@ -33,7 +30,6 @@
 // All workgroup barriers sit at the staging of a box, in wave-uniform control flow, outside the divergent unite code.  No float
 // atomics, no read-back, no workgroup waits on another.  Memory is O(n) whatever the radius is.
 // This file is compiled with -ffp-contract=off: d2 = (dx*dx + dy*dy) + dz*dz, exactly so, and a lower bound that is monotone.
-#define OGS_KNN_BOXES_NO_SEARCH
 #include "knn_boxes.h"
 #include "knn_union.h"
 
@@ -69,6 +65,9 @@ __global__ __launch_bounds__(kKnnBox) void radius_walk_kernel(RadiusArgs g, cons
     __shared__ __attribute__((aligned(16))) int cid[kKnnBox], ctag[kKnnBox];
     const int lane = threadIdx.x, run = blockIdx.x, nruns = gridDim.x, nbox = g.nbox;
     const size_t p = (size_t)run * kKnnBox + lane;
+    // The lane and the bound below are KnnLane::load and KnnLane::bound (knn_boxes.h) written out, the set-up in this kernel's own
+    // order (label and core flag before the run's bounds): with either of the two called instead the compiler schedules these
+    // kernels differently, and the link pass measured 0.8 % slower, the tagged count 0.5 %.
     const float qx = qsx[p], qy = qsy[p], qz = qsz[p];
     const int qid = qsid[p];
     const bool valid = qid != kNoId;
@@ -94,7 +93,7 @@ __global__ __launch_bounds__(kKnnBox) void radius_walk_kernel(RadiusArgs g, cons
         const int c = r * kKnnBox + lane;
         const bool inside = c < nbox;
         float lb = 0.f;
-        if (inside) {
+        if (inside) {                                              // KnnLane::bound, and it must stay that expression     
             float gap[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -181,26 +180,8 @@ int launch_walk(int nruns, const RadiusArgs& g, const KnnBoxes& q, const KnnBoxe
     return OGS_OK;
 }
 
-struct RadiusCountTmp {
-    KnnSortScratch sort;
-    KnnBoxes runs;                                      // the queries in runs of kKnnBox; no first_key, no frame
-    size_t bytes;
-    static RadiusCountTmp carve(void* p, int64_t m) {
-        Carver c(p);
-        RadiusCountTmp t{};
-        const size_t nruns = (size_t)((m + kKnnBox - 1) / kKnnBox), npad = nruns * kKnnBox;
-        t.sort = SortTmp::carve(c, m).sort;
-        t.runs.sx = c.take<float>(npad); t.runs.sy = c.take<float>(npad); t.runs.sz = c.take<float>(npad);
-        t.runs.sid = c.take<int32_t>(npad);
-        t.runs.box = c.take<float>(6 * nruns);
-        t.bytes = c.off;
-        return t;
-    }
-};
-
 struct DbscanTmp {
-    KnnSortScratch sort;
-    KnnBoxes boxes;                                     // no first_key, no frame
+    SortedTmp s;                                        // the sort's scratch and the set, unkeyed
     uint8_t* core_sorted;                               // [nbox * kKnnBox]
     int32_t* anchor;                                    // [n]
     ComponentsTmp comps;
@@ -208,20 +189,14 @@ struct DbscanTmp {
     static DbscanTmp carve(void* p, int64_t n) {
         Carver c(p);
         DbscanTmp t{};
-        const size_t nbox = (size_t)((n + kKnnBox - 1) / kKnnBox), npad = nbox * kKnnBox;
-        t.sort = SortTmp::carve(c, n).sort;
-        t.boxes.sx = c.take<float>(npad); t.boxes.sy = c.take<float>(npad); t.boxes.sz = c.take<float>(npad);
-        t.boxes.sid = c.take<int32_t>(npad);
-        t.boxes.box = c.take<float>(6 * nbox);
-        t.core_sorted = c.take<uint8_t>(npad);
+        t.s = SortedTmp::carve(c, n);
+        t.core_sorted = c.take<uint8_t>((size_t)knn_nbox(n) * kKnnBox);
         t.anchor = c.take<int32_t>((size_t)n);
         t.comps = ComponentsTmp::carve(c, n);
         t.bytes = c.off;
         return t;
     }
 };
-
-bool size_ok(int64_t n) { return n >= 0 && n <= (int64_t)INT32_MAX - kKnnBox; }
 
 }  // namespace
 }  // namespace ogs
@@ -231,14 +206,15 @@ using namespace ogs;
 extern "C" {
 
 size_t ogs_knn_radius_count_tmp_bytes(int64_t n, int64_t m) {
-    if (n <= 0 || m <= 0 || !size_ok(n) || !size_ok(m)) return 0;
-    return RadiusCountTmp::carve(nullptr, m).bytes;
+    if (n <= 0 || m <= 0 || !knn_size_ok(n) || !knn_size_ok(m)) return 0;
+    Carver c(nullptr);
+    return SortedTmp::carve(c, m).bytes;
 }
 
 int ogs_knn_radius_count(int64_t n, const void* index, int64_t m, const float* queries, const float* radius2,
                          const int32_t* ref_labels, const int32_t* query_labels, int32_t* count, void* tmp, size_t tmp_bytes,
                          void* stream_) {
-    if (!size_ok(n) || !size_ok(m)) {
+    if (!knn_size_ok(n) || !knn_size_ok(m)) {
         set_error("knn_radius_count: bad sizes (n=%lld m=%lld; 0 <= n, m <= INT32_MAX - %d)", (long long)n, (long long)m, kKnnBox);
         return OGS_ERR_INVALID_ARG;
     }
@@ -254,29 +230,23 @@ int ogs_knn_radius_count(int64_t n, const void* index, int64_t m, const float* q
         return OGS_OK;
     }
     if (!index || !queries || !radius2 || !tmp) { set_error("knn_radius_count: NULL pointer"); return OGS_ERR_INVALID_ARG; }
-    const RadiusCountTmp q = RadiusCountTmp::carve(tmp, m);
-    if (tmp_bytes < q.bytes) {
-        set_error("knn_radius_count: tmp has %zu bytes, %zu needed (ogs_knn_radius_count_tmp_bytes)", tmp_bytes, q.bytes);
-        return OGS_ERR_INVALID_ARG;
-    }
-    const KnnBoxes r = IndexLayout::carve(const_cast<void*>(index), n).b;       // read only from here on
-    const int mi = (int)m, nruns = (mi + kKnnBox - 1) / kKnnBox, nbox = ((int)n + kKnnBox - 1) / kKnnBox;
-    const int rc = knn_sort_into_boxes(mi, queries, q.sort, q.runs, s);
+    KnnTwoSets w;
+    const int rc = knn_sort_queries(n, index, m, queries, tmp, tmp_bytes, "knn_radius_count", false, s, w);
     if (rc != OGS_OK) return rc;
     RadiusArgs g{};
-    g.nbox = nbox; g.n = n; g.r2 = radius2; g.ref_labels = ref_labels; g.query_labels = query_labels; g.count = count;
-    return ref_labels ? launch_walk<kCount, true>(nruns, g, q.runs, r, s) : launch_walk<kCount, false>(nruns, g, q.runs, r, s);
+    g.nbox = w.nbox; g.n = n; g.r2 = radius2; g.ref_labels = ref_labels; g.query_labels = query_labels; g.count = count;
+    return ref_labels ? launch_walk<kCount, true>(w.nruns, g, w.q, w.r, s) : launch_walk<kCount, false>(w.nruns, g, w.q, w.r, s);
 }
 
 size_t ogs_knn_dbscan_tmp_bytes(int64_t n) {
-    if (n <= 0 || !size_ok(n)) return 0;
+    if (n <= 0 || !knn_size_ok(n)) return 0;
     return DbscanTmp::carve(nullptr, n).bytes;
 }
 
 int ogs_knn_dbscan(int64_t n, const float* points, const float* eps2, int32_t min_pts, const int32_t* labels, int32_t* cluster,
                    uint8_t* core, int32_t* degree, int32_t* sizes, int32_t* first, int32_t* count, void* tmp, size_t tmp_bytes,
                    void* stream_) {
-    if (!size_ok(n) || min_pts < 1) {
+    if (!knn_size_ok(n) || min_pts < 1) {
         set_error("knn_dbscan: bad sizes (n=%lld min_pts=%d; 0 <= n <= INT32_MAX - %d, 1 <= min_pts)", (long long)n, min_pts, kKnnBox);
         return OGS_ERR_INVALID_ARG;
     }
@@ -294,18 +264,19 @@ int ogs_knn_dbscan(int64_t n, const float* points, const float* eps2, int32_t mi
     }
     uint32_t* status_word = async_status_word();
     if (!status_word) return OGS_ERR_HIP;
-    const int nbox = ((int)n + kKnnBox - 1) / kKnnBox;
-    int rc = knn_sort_into_boxes((int)n, points, t.sort, t.boxes, s);
+    const int nbox = (int)knn_nbox(n);
+    const KnnBoxes& b = t.s.boxes;
+    int rc = knn_sort_into_boxes((int)n, points, t.s.sort, b, s);
     if (rc != OGS_OK) return rc;
     RadiusArgs g{};
     g.nbox = nbox; g.min_pts = min_pts; g.n = n; g.r2 = eps2; g.ref_labels = labels; g.query_labels = labels;
     g.count = degree; g.core = core; g.core_sorted = t.core_sorted;
-    rc = labels ? launch_walk<kCount, true>(nbox, g, t.boxes, t.boxes, s) : launch_walk<kCount, false>(nbox, g, t.boxes, t.boxes, s);
+    rc = labels ? launch_walk<kCount, true>(nbox, g, b, b, s) : launch_walk<kCount, false>(nbox, g, b, b, s);
     if (rc != OGS_OK) return rc;
     OGS_LAUNCH(radius_identity_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n, t.comps.parent);
     OGS_LAUNCH_CHECK(0, s);
     g.parent = t.comps.parent; g.anchor = t.anchor; g.status_word = status_word;
-    rc = launch_walk<kLink, true>(nbox, g, t.boxes, t.boxes, s);
+    rc = launch_walk<kLink, true>(nbox, g, b, b, s);
     if (rc != OGS_OK) return rc;
     return knn_components_tail(n, nullptr, t.anchor, cluster, sizes, first, count, t.comps, stream_);
 }

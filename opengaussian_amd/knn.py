@@ -174,16 +174,13 @@ def neighbors(points: torch.Tensor, k: int, exclude_self: bool = True):
     ``(dx*dx + dy*dy) + dz*dz`` of ``group_ksum``, equal distances go to the smaller index, so the result is unique and two
     calls give the same bytes.  Slots past the end of the list (fewer than k candidates) hold idx = -1, d2 = +inf.
     1 <= k <= 32 and n * k < 2^31.  Nothing is read back from the device."""
-    _need_gpu(points, "points")
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be [n, 3], got {tuple(points.shape)}")
-    n, dev, k = points.shape[0], points.device, int(k)
-    pts = points.detach().to(torch.float32).contiguous()
+    pts = _points_arg(points, "points")
+    n, dev, k = pts.shape[0], pts.device, int(k)
     idx = torch.empty((n, k), dtype=torch.int32, device=dev)
     d2 = torch.empty((n, k), dtype=torch.float32, device=dev)
     L = _lib.lib()
     nbytes = int(L.ogs_knn_neighbors_tmp_bytes(n))
-    tmp = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    tmp = _tmp(nbytes, dev)
     check(L.ogs_knn_neighbors(n, ptr(pts), k, int(bool(exclude_self)), ptr(idx), ptr(d2), ptr(tmp), nbytes, _stream()),
           "ogs_knn_neighbors")
     return idx, d2
