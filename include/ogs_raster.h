@@ -248,8 +248,13 @@ int ogs_raster_forward_tiny(const OgsRasterFwdArgs* args, void* stream);
 
 /* List-length limits of the render phase's per-tile depth sort (test hook for their boundaries; no effect on results):
  * level 0: the longest list one wave sorts alone; level 1: the longest list a workgroup sorts in LDS (longer lists take
- * passes through global memory); 0 for any other level. */
+ * passes through global memory); level 2: the bucket cap in force (below); 0 for any other level. */
 size_t ogs_raster_tile_sort_capacity(int32_t level);
+/* A one-wave list is cut into buckets on its top differing key bits and every entry ranked inside its bucket; a list whose
+ * largest bucket holds more than the bucket cap takes stable radix passes instead.  Same lists either way (test hook; no effect
+ * on results): bucket_cap > 0 forces the cap, 0 hands the choice back to the library, a negative value leaves it as it is.
+ * Process-wide.  Returns OGS_OK. */
+int ogs_raster_tile_sort_debug(int32_t bucket_cap);
 
 /* The counting sort by tile of a default streaming pass (test hooks; no effect on results).  The emitted pairs are cut into B
  * chunks, each a multiple of ogs_raster_tile_count_trip() pairs long.  ogs_raster_tile_count_debug returns the B a pass with a

@@ -124,6 +124,7 @@ SIGNATURES = {
     "ogs_raster_backward": (C.c_int, [C.POINTER(OgsRasterBwdArgs), _vp]),
     "ogs_raster_tiny_max_points": (C.c_size_t, []),
     "ogs_raster_tile_sort_capacity": (C.c_size_t, [C.c_int32]),
+    "ogs_raster_tile_sort_debug": (C.c_int, [C.c_int32]),
     "ogs_raster_tile_count_debug": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "ogs_raster_tile_count_trip": (C.c_size_t, []),
     "ogs_raster_tile_place_debug": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),

@@ -12,6 +12,7 @@
 // too short for the count table.
 // Grouped passes (up to 2^31 virtual tiles of a few entries) and the small path instead sort the P
 // Gaussians by depth once and emit the duplicates in that order.
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -785,7 +786,9 @@ __global__ __launch_bounds__(kCountBlock) void tile_place_kernel(const uint32_t*
 // (4 B per Gaussian), by the id in the value; the reach flag (bit 31) travels with the value.  Only the bits that differ inside
 // the tile are sorted on: [lowest, highest differing bit] in ceil(span / 8) passes of <= 8 bits.
 // A workgroup takes four tiles (tile_order[4b .. 4b+3]):
-//   * lists up to kWaveSortCap entries: one wave each, no workgroup barrier -- the common case (S1M: ~440 entries);
+//   * lists up to kWaveSortCap entries: one wave each, no workgroup barrier -- the common case (S1M: ~440 entries).  These need no
+//     stable pass at all, (key, id) being a total order: one bucket pass and a ranking inside each bucket (wave_bucket_rank), the
+//     LSD passes below only for a list whose largest bucket is long (clustered depths, many equal keys);
 //   * then, one after the other, its lists up to kTileSortCap entries: all four waves, in LDS;
 //   * longer lists: the same four-wave ranking on chunks of kTileSortCap entries, passes ping-pong between the segment and
 //     the same positions of `scratch` (a D-sized buffer the tile sort left free), a histogram pass over the list per digit.
@@ -809,6 +812,7 @@ struct TileSortLds {
 // invalid instruction
 typedef __attribute__((address_space(3))) volatile uint32_t LdsWord;
 typedef __attribute__((address_space(3))) unsigned long long LdsMask;
+static_assert(offsetof(TileSortLds, kv) % 8 == 0, "a wave's quarter of kv is read as 64-bit pairs");
 __device__ __forceinline__ LdsWord* lds_words(uint32_t* p) { return (LdsWord*)p; }
 __device__ __forceinline__ LdsMask* wave_masks(TileSortLds& sm, int wave) { return (LdsMask*)(sm.kv + wave * 2 * kWaveSortCap); }
 
@@ -977,9 +981,159 @@ __device__ __forceinline__ void wave_lsd_passes(LdsWord* hist, LdsMask* masks, L
     }
 }
 
-// One wave sorts a list of 2 .. kWaveSortCap entries in its quarter of the key / value space.
+// Timing probes of the one-wave path.  They give WRONG lists by construction, so the switches exist only in a
+// -DOGS_EXPERIMENTS variant build; the shipped library compiles all three to `false`.
+#if defined(OGS_EXPERIMENTS) && defined(OGS_TSORT_LOADS_ONLY)
+constexpr bool kTsortLoadsOnly = true;       // loads, key gathers, AND / OR; nothing ranked, nothing written
+#else
+constexpr bool kTsortLoadsOnly = false;
+#endif
+#if defined(OGS_EXPERIMENTS) && defined(OGS_TSORT_SKIP_PASSES)
+constexpr bool kTsortSkipPasses = true;      // the list goes through LDS and out again in the order it came in
+#else
+constexpr bool kTsortSkipPasses = false;
+#endif
+#if defined(OGS_EXPERIMENTS) && defined(OGS_TSORT_LSD_ONLY)
+constexpr bool kTsortLsdOnly = true;         // the bucket path compiled out: the LSD passes alone (right lists)
+#else
+constexpr bool kTsortLsdOnly = false;
+#endif
+
+// min / max over the wave of the first ipl sort words of every lane (`keep` masks them)
+__device__ __forceinline__ void wave_min_max(const uint32_t (&w)[kTileSortItems], int ipl, uint32_t keep, uint32_t& w_min,
+                                             uint32_t& w_max) {
+    w_min = 0xFFFFFFFFu; w_max = 0u;
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        if (i >= ipl) continue;
+        w_min = min(w_min, w[i] & keep);
+        w_max = max(w_max, w[i] & keep);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        w_min = min(w_min, (uint32_t)__shfl_xor((int)w_min, d, kWave));
+        w_max = max(w_max, (uint32_t)__shfl_xor((int)w_max, d, kWave));
+    }
+}
+
+typedef __attribute__((address_space(3))) uint32_t LdsCount;
+typedef __attribute__((address_space(3))) volatile unsigned long long LdsPair;
+
+// The ranking loop of wave_bucket_rank over the first IPL items of every lane, without a branch inside a step (a guard per
+// item cost more than the step's reads).  cw: the bucket's count << 16 | the entries found smaller so far -- 0 for an item that
+// takes no part, which then reads some entry of the list and counts nothing.  t < count  <=>  (t << 16 | 0xFFFF) < cw, whatever
+// cw's low half (below the count) holds.  The reads of a step are independent of each other and of the step before.
+constexpr int kRankGroup = 8;                  // reads in flight per lane
+template <int IPL>
+__device__ __forceinline__ void bucket_rank_steps(LdsPair* pairs, const unsigned long long (&mine)[kTileSortItems],
+                                                  const uint32_t (&st)[kTileSortItems], uint32_t (&cw)[kTileSortItems], int cmax,
+                                                  int n) {
+#pragma unroll 1
+    for (int t = 0; t < cmax; ++t) {
+        const uint32_t tt = ((uint32_t)t << 16) | 0xFFFFu;
+#pragma unroll
+        for (int g = 0; g < IPL; g += kRankGroup) {
+            unsigned long long other[kRankGroup];
+#pragma unroll
+            for (int i = g; i < min(IPL, g + kRankGroup); ++i)
+                other[i - g] = pairs[min((int)st[i] + t, n - 1)];                       // past the bucket: not counted
+#pragma unroll
+            for (int i = g; i < min(IPL, g + kRankGroup); ++i)
+                cw[i] += (tt < cw[i] && other[i - g] < mine[i]) ? 1u : 0u;              // against itself: 0
+        }
+    }
+}
+
+// One-wave path, lists of distinct (key, id): one bucket pass that is NOT stable, then every entry is ranked inside its bucket on
+// the total order (key, id).  The digit is (key - the list's smallest key) >> shift, the shift that leaves kBucketBits bits of
+// the list's key range (the ids' when the list has ONE key): monotone, so bucket d holds only entries smaller than those of
+// bucket d + 1, and at least half of the buckets lie inside the range -- the top differing bits of two floats either side of a
+// power of two are their exponents, two buckets for the whole list.  An entry takes its slot with one LDS atomic with return
+// (all of a lane's atomics are in flight at once), the counts are scanned into bucket starts, (key, id word) pairs go to
+// start + slot, and the final position is start + the bucket's entries that compare less: the same for any arrival order.
+// The id word is the value rotated by one, the id above the reach flag: ids are distinct, so the words order as the ids do.
+// Returns false with nothing moved (key / val untouched) when the largest bucket holds more than bucket_cap entries -- the
+// ranking loop costs its length for the whole wave -- and the caller then runs the LSD passes; true with the values in wv.
+constexpr int kBucketBits = 8;                 // 256 counts per wave: TileSortLds::hist, nothing new in LDS
+__device__ __forceinline__ bool wave_bucket_rank(LdsWord* hist, LdsWord* wk, LdsWord* wv, const uint32_t (&key)[kTileSortItems],
+                                                 const uint32_t (&val)[kTileSortItems], int ipl, int n, int bucket_cap) {
+    const int lane = threadIdx.x & (kWave - 1);
+    uint32_t w_min, w_max;
+    wave_min_max(key, ipl, 0xFFFFFFFFu, w_min, w_max);
+    const bool by_id = __builtin_amdgcn_readfirstlane((int)w_min) == __builtin_amdgcn_readfirstlane((int)w_max);     // wave-uniform
+    if (by_id) wave_min_max(val, ipl, kGidMask, w_min, w_max);
+    const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_min);
+    const uint32_t range = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_max) - base;
+    if (range == 0u) return false;                               // (a list of ONE id: not a tile's list; the passes leave it alone)
+    const int shift = max(0, 32 - __builtin_clz(range) - kBucketBits);           // range >> shift < 1 << kBucketBits
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hist[lane + j * kWave] = 0u;
+    __builtin_amdgcn_wave_barrier();
+    uint32_t slot[kTileSortItems];
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        if (i >= ipl) continue;                                  // wave-uniform
+        const uint32_t d = ((by_id ? val[i] & kGidMask : key[i]) - base) >> shift;
+        slot[i] = 0u;
+        if (i * kWave + lane < n)
+            slot[i] = __hip_atomic_fetch_add((LdsCount*)(hist + d), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+    __builtin_amdgcn_wave_barrier();
+    // bucket starts: lane l scans digits 4l .. 4l + 3; the largest count decides the path
+    uint32_t c[4], sum = 0, big = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { c[j] = hist[4 * lane + j]; sum += c[j]; big = max(big, c[j]); }
+    uint32_t run = wave_inclusive_scan(sum) - sum;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) big = max(big, (uint32_t)__shfl_xor((int)big, d, kWave));
+    const int cmax = __builtin_amdgcn_readfirstlane((int)big);
+    if (cmax > bucket_cap) return false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { hist[4 * lane + j] = run | (c[j] << 10); run += c[j]; }        // start < 1024 where count > 0
+    __builtin_amdgcn_wave_barrier();
+    // n pairs: the whole quarter at n = kWaveSortCap.  A lane past the end holds a copy of the last entry, which is never
+    // scattered and takes no part in the ranking
+    LdsPair* pairs = (LdsPair*)wk;
+    unsigned long long mine[kTileSortItems];
+    uint32_t st[kTileSortItems], cw[kTileSortItems];
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {                   // start | count << 10 | slot << 21 in one register
+        if (i >= ipl) continue;
+        slot[i] = hist[((by_id ? val[i] & kGidMask : key[i]) - base) >> shift] | (slot[i] << 21);
+    }
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        uint32_t s_i = 0u, c_i = 0u;                             // an item past ipl takes no part (and is not read below
+        unsigned long long m_i = 0ull;                           // unless its group of the ranking loop holds a live one)
+        if (i < ipl) {
+            const bool valid = i * kWave + lane < n;
+            c_i = valid ? ((slot[i] >> 10) & 0x7FFu) << 16 : 0u;
+            s_i = slot[i] & 0x3FFu;
+            m_i = ((unsigned long long)key[i] << 32) | (unsigned long long)((val[i] << 1) | (val[i] >> 31));
+            if (valid) pairs[s_i + (slot[i] >> 21)] = m_i;
+        }
+        st[i] = s_i; cw[i] = c_i; mine[i] = m_i;
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (ipl <= 4) bucket_rank_steps<4>(pairs, mine, st, cw, cmax, n);
+    else if (ipl <= 8) bucket_rank_steps<8>(pairs, mine, st, cw, cmax, n);
+    else if (ipl <= 12) bucket_rank_steps<12>(pairs, mine, st, cw, cmax, n);
+    else bucket_rank_steps<kTileSortItems>(pairs, mine, st, cw, cmax, n);
+    __builtin_amdgcn_wave_barrier();                             // every pair has been read: the values may overwrite them
+#pragma unroll
+    for (int i = 0; i < kTileSortItems; ++i) {
+        if (i >= ipl) continue;
+        const uint32_t w = (uint32_t)mine[i];                    // the value back from its id word
+        if (i * kWave + lane < n) wv[st[i] + (cw[i] & 0xFFFFu)] = (w >> 1) | (w << 31);
+    }
+    __builtin_amdgcn_wave_barrier();
+    return true;
+}
+
+// One wave sorts a list of 2 .. kWaveSortCap entries in its quarter of the key / value space: buckets and the ranking inside
+// them when no bucket holds more than bucket_cap entries, otherwise the stable LSD passes and the look at the ties.
 __device__ __forceinline__ void wave_sort_list(TileSortLds& sm, uint32_t* __restrict__ seg, int n,
-                                               const uint32_t* __restrict__ depth_keys) {
+                                               const uint32_t* __restrict__ depth_keys, int bucket_cap) {
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     LdsWord* wk = lds_words(sm.kv + wave * 2 * kWaveSortCap);
     LdsWord* wv = wk + kWaveSortCap;
@@ -991,6 +1145,24 @@ __device__ __forceinline__ void wave_sort_list(TileSortLds& sm, uint32_t* __rest
     uint32_t k_and, k_or;
     wave_and_or(key, ipl, 0xFFFFFFFFu, k_and, k_or);
     const uint32_t kdiff = (uint32_t)__builtin_amdgcn_readfirstlane((int)(k_and ^ k_or));
+    if (kTsortLoadsOnly) {
+        if (kdiff == 0x5A5A5A5Au) seg[0] = key[0];               // (keeps the loads alive)
+        return;
+    }
+    if (kTsortSkipPasses) {
+#pragma unroll
+        for (int i = 0; i < kTileSortItems; ++i) {
+            if (i >= ipl) continue;
+            if (i * kWave + lane < n) { wk[i * kWave + lane] = key[i]; wv[i * kWave + lane] = val[i]; }
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int j = lane; j < n; j += kWave) seg[j] = wv[j];
+        return;
+    }
+    if (!kTsortLsdOnly && wave_bucket_rank(hist, wk, wv, key, val, ipl, n, bucket_cap)) {
+        for (int j = lane; j < n; j += kWave) seg[j] = wv[j];
+        return;
+    }
     if (kdiff != 0u) {
         wave_lsd_passes(hist, masks, wk, wv, key, key, val, rank, ipl, n, kdiff, false);
     } else {                                                     // one key for the whole list: only the id order is open
@@ -1226,7 +1398,7 @@ __global__ __launch_bounds__(kBlock) void tile_depth_sort_kernel(const uint2* __
                                                                  const uint32_t* __restrict__ tile_order,
                                                                  uint32_t* __restrict__ point_list,
                                                                  const uint32_t* __restrict__ depth_keys,
-                                                                 uint32_t* __restrict__ scratch) {
+                                                                 uint32_t* __restrict__ scratch, int bucket_cap) {
     __shared__ TileSortLds sm;
     const int wave = threadIdx.x >> 6;
     if (threadIdx.x < kTileSortWaves) {
@@ -1237,7 +1409,7 @@ __global__ __launch_bounds__(kBlock) void tile_depth_sort_kernel(const uint2* __
     // (readfirstlane: the list bounds are uniform -- the addresses then live in SGPRs, not in 2 VGPRs per item)
     const uint32_t x = (uint32_t)__builtin_amdgcn_readfirstlane((int)sm.range[wave].x);
     const int n = __builtin_amdgcn_readfirstlane((int)(sm.range[wave].y - sm.range[wave].x));
-    if (n >= 2 && n <= kWaveSortCap) wave_sort_list(sm, point_list + x, n, depth_keys);
+    if (n >= 2 && n <= kWaveSortCap) wave_sort_list(sm, point_list + x, n, depth_keys, bucket_cap);
 #pragma unroll 1
     for (int w = 0; w < kTileSortWaves; ++w) {
         const uint32_t xw = (uint32_t)__builtin_amdgcn_readfirstlane((int)sm.range[w].x);
@@ -1545,13 +1717,20 @@ int launch_tile_count_binning(const uint32_t* keys, const uint32_t* vals, int64_
     return OGS_OK;
 }
 
+// test hook (ogs_raster_tile_sort_debug): the forced bucket cap of the one-wave path; 0: the rule
+static int g_tile_sort_bucket_cap = 0;
+void tile_sort_debug(int bucket_cap) {
+    if (bucket_cap >= 0) g_tile_sort_bucket_cap = bucket_cap;
+}
+int tile_sort_bucket_cap() { return g_tile_sort_bucket_cap > 0 ? g_tile_sort_bucket_cap : kWaveBucketCap; }
+
 int launch_tile_depth_sort(const uint2* ranges, int64_t tiles, const uint32_t* tile_order, uint32_t* point_list,
                            const uint32_t* depth_keys, uint32_t* scratch, hipStream_t s, int debug) {
     if (tiles <= 0) return OGS_OK;
     if (tiles >= (1ll << 31)) { set_error("tile_depth_sort: %lld tiles", (long long)tiles); return OGS_ERR_UNSUPPORTED; }
     const unsigned grid = (unsigned)((tiles + kTileSortWaves - 1) / kTileSortWaves);
     OGS_LAUNCH(tile_depth_sort_kernel, dim3(grid), dim3(kBlock), 0, s, ranges, (int)tiles, tile_order, point_list, depth_keys,
-               scratch);
+               scratch, tile_sort_bucket_cap());
     OGS_LAUNCH_CHECK(debug, s);
     return OGS_OK;
 }

@@ -186,7 +186,7 @@ using namespace ogs;
 
 extern "C" {
 
-int ogs_version(void) { return 410; }
+int ogs_version(void) { return 420; }
 
 int ogs_check_async_status(void) { return check_async_status("ogs_check_async_status"); }
 
@@ -538,7 +538,15 @@ int ogs_raster_compact_kept(int32_t W, int32_t H, int32_t C, const void* image_b
 size_t ogs_raster_tiny_max_points(void) { return (size_t)kTinyMaxP; }
 
 size_t ogs_raster_tile_sort_capacity(int32_t level) {
-    return level == 0 ? (size_t)kWaveSortCap : level == 1 ? (size_t)kTileSortCap : 0;
+    return level == 0 ? (size_t)kWaveSortCap : level == 1 ? (size_t)kTileSortCap : level == 2 ? (size_t)tile_sort_bucket_cap() : 0;
+}
+
+// Tests: the bucket cap of the one-wave depth sort.  bucket_cap > 0 forces it (1: every list of two entries or more takes the LSD
+// passes; above the list length: every list is ranked inside its buckets), 0 gives the choice back to the library, a negative
+// value leaves it as it is.  Process-wide: a test restores 0 when it is done.
+int ogs_raster_tile_sort_debug(int32_t bucket_cap) {
+    tile_sort_debug(bucket_cap);
+    return OGS_OK;
 }
 
 // Tests: the chunk count B the counting sort by tile takes for a list capacity D and a grid of `tiles` (0: such a pass takes the

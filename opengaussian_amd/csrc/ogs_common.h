@@ -434,6 +434,12 @@ inline bool block_sum_offsets(const OgsRasterFwdArgs& a) { return per_tile_depth
 constexpr int kTileSortItems = 16;
 constexpr int kTileSortCap = kBlock * kTileSortItems;       // 4096 entries: 32 KB of keys + values, 4 workgroups per CU
 constexpr int kWaveSortCap = kTileSortCap / (kBlock / kWave);   // 1024: lists one wave sorts alone (a quarter of that space)
+// One-wave lists: a bucket pass on the top 8 bits of the list's key range and a ranking inside each bucket, unless the list's
+// largest bucket holds more than the cap (clustered depths, many equal keys): such a list takes the stable LSD passes.  The
+// crossover of the two lies between 32 and 64 entries for lists of 512 and of 1024 (DESIGN 3j has the sweep).
+constexpr int kWaveBucketCap = 32;
+void tile_sort_debug(int bucket_cap);                      // test hook; > 0 forces the cap, 0 hands back, < 0 leaves as it is
+int tile_sort_bucket_cap();                                // the cap in force
 int launch_tile_depth_sort(const uint2* ranges, int64_t tiles, const uint32_t* tile_order, uint32_t* point_list,
                            const uint32_t* depth_keys, uint32_t* scratch, hipStream_t s, int debug);
 inline int num_groups_of(int g) { return g > 1 ? g : 1; }
