@@ -110,6 +110,52 @@ int ogs_kmeans_wide_inertia(const float* dist, const float* w, int64_t N, double
 int ogs_kmeans_wide_lloyd(const float* X, const float* w, int64_t N, int32_t D, float* C, int32_t k, int32_t metric, int32_t iters,
                           int32_t* ids, float* dist, float* counts, double* inertia, void* tmp, size_t tmp_bytes, void* stream);
 
+/*
+ * ---- wide seeding (csrc/kmeans_seed.hip) ---------------------------------------------------------------------------------------------
+ * Exact k-means++ (D^2) seeding of the wide k-means: k rounds, round r draws one row with probability proportional to its mass
+ * (w_i in round 0, w_i times its squared distance to the nearest centre so far afterwards) and makes it centre r.  Sizes,
+ * pointers, tmp (ogs_kmeans_wide_seed_tmp_bytes), errors and `stream` as in the block above; N = 0 launches and writes nothing.
+ * Inputs must be finite.  Every step is fixed below, so the result is unique: tests/kmeans_seed_restatement.py restates it in NumPy
+ * and every output is equal to it byte for byte.
+ *
+ *   w [N] >= 0, NULL = 1.   row_scale [N], NULL = 1.   C [k, D] out: the centres.   rows [k] out: the rows they are.
+ *   ids [N] out (may be NULL): the nearest seeded centre.   d2 [N] out (may be NULL): the squared distance to it.
+ *   stats [4] int64 out (may be NULL): [0] centres seeded, [1] (row, round) pairs whose distance was evaluated in the rounds
+ *   r >= 1, [2] pairs skipped by the bound, [1] + [2] = N (stats[0] - 1); [3] = 0.
+ *
+ * Points    y_ij = fl32(row_scale_i * x_ij).  L2 passes NULL; cosine passes 1 / |x_i|: D^2 sampling on the unit sphere, mass
+ *           proportional to 1 - cos.  No square root and no division happens inside.
+ * Distance  dist(a, b) in fp32, no FMA: t_j = fl32(fl32(a_j - b_j)^2); accumulator q (0 <= q < 256) sums the t_j with
+ *           j mod 256 = q in ascending j; then s[q] = s[2 q] + s[2 q + 1], eight times, 256 values down to one.  The same order for
+ *           every D and every alignment (absent terms are exact zeros).
+ * Draw      rand64(seed, r) is splitmix64: z = seed + (r + 1) 0x9E3779B97F4A7C15; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;
+ *           z = (z ^ z >> 27) 0x94D049BB133111EB; z ^= z >> 31 (mod 2^64).  Masses are integers q_i < 2^31, T = their sum (exact in
+ *           int64), t = (rand64 * T) >> 64, the pick is the smallest i whose inclusive prefix sum exceeds t: a row of mass 0 is never
+ *           picked.
+ * Round 0   q_i = floor(ldexp(w_i, 31 - E0)), E0 = the frexp exponent of max w.  C[0] = y_pick; d2_i = dist(y_i, C[0]), ids_i = 0.
+ * Round r   q_i = floor(ldexp(fl32(w_i * d2_i), 31 - E)), E = the frexp exponent of max_i fl32(w_i * d2_i) after round 0, kept for
+ *           all rounds (masses only fall).  C[r] = y_pick.  A row changes only when dist(y_i, C[r]) < d2_i, strictly: then d2_i is
+ *           that distance and ids_i = r; ties stay with the earlier centre.
+ * No mass   T = 0 before round r (fewer distinct weighted points than k): the call ends there, rows[r ..] = -1, C[r ..] is not
+ *           touched, stats[0] = r.  With stats[0] = 0 (no weight at all) ids and d2 are not written either.
+ * Pruning   prune != 0 skips row i in round r, unread, when with d = d2_i and b = dist(C[r], C[ids_i])
+ *               d == 0   or   ( d >= 2^-100  and  fl32(b (1 - 2^-10)) >= fl32(fl32(4 d) (1 + 2^-10)) ).
+ *           Proof that dist(y_i, C[r]) >= d then, so the row would not have changed.  d == 0: a distance is never negative.
+ *           Otherwise write a, b', e for the exact squared distances y_i-C[ids_i], C[r]-C[ids_i], y_i-C[r]; a computed distance is
+ *           within a factor 1 +- g, g = (D + 4) 2^-24 <= 2^-13, of the exact one (underflow adds at most D 2^-150, nothing beside
+ *           2^-100).  (1) The rule gives b >= 4 d (1 + 2^-10), hence b' / a >= 4 (1 + 2^-10) (1 - g) / (1 + g) >= 4 (1 + 2^-11).
+ *           (2) Triangle inequality: sqrt(e) >= sqrt(b') - sqrt(a) >= (2 sqrt(1 + 2^-11) - 1) sqrt(a), so e >= (1 + 2^-11) a.
+ *           (3) dist(y_i, C[r]) >= e (1 - g) >= (1 + 2^-11) (1 - g) d / (1 + g) >= d.
+ *           Every output has the same bytes with prune = 0 and prune = 1; only stats[1] and stats[2] differ.
+ * No float atomics, no waits between workgroups, one writer per element; nothing is read back, so all k rounds are launched and the
+ * rounds after the mass ran out return at once.  A workgroup of the row pass owns ogs_kmeans_wide_seed_rows() rows (256).
+ */
+size_t ogs_kmeans_wide_seed_rows(void);
+size_t ogs_kmeans_wide_seed_tmp_bytes(int64_t N, int32_t D, int32_t k);    /* 0 for sizes outside the limits */
+int ogs_kmeans_wide_seed(const float* X, const float* w, const float* row_scale, int64_t N, int32_t D, int32_t k, uint64_t seed,
+                         int32_t prune, float* C, int32_t* rows, int32_t* ids, float* d2, int64_t* stats, void* tmp, size_t tmp_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,10 @@ SIGNATURES = {
     "ogs_kmeans_wide_inertia": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_size_t, _vp]),
     "ogs_kmeans_wide_lloyd": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp,
                                         _vp, C.c_size_t, _vp]),
+    "ogs_kmeans_wide_seed_rows": (C.c_size_t, []),
+    "ogs_kmeans_wide_seed_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "ogs_kmeans_wide_seed": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, C.c_size_t, _vp]),
     "ogs_query_max_leaves": (C.c_size_t, []),
     "ogs_query_max_top": (C.c_size_t, []),
     "ogs_query_max_classes": (C.c_size_t, []),

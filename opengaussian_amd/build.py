@@ -27,6 +27,8 @@ EXTRA = {
     "kmeans.hip": ["-ffp-contract=off"],
     # wide k-means: every fmaf of the bias, distance and norm chains is written out; the scores themselves are MFMA sums
     "kmeans_wide.hip": ["-ffp-contract=off"],
+    # wide seeding: dist() is differences, squares and adds in the one order include/ogs_kmeans.h states, the bits NumPy computes
+    "kmeans_seed.hip": ["-ffp-contract=off"],
     "adam.hip": ["-ffp-contract=off"],
     # footprint alpha and the uint8 pixel made of it: the bits of a P = 1 pass through the blend kernels
     "refine.hip": ["-ffp-contract=off"],

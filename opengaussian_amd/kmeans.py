@@ -180,6 +180,52 @@ def wide_lloyd(feat: torch.Tensor, centers: torch.Tensor, iters: int, metric: st
     return ids.to(torch.int64), dist, counts, inertia
 
 
+def wide_seed(feat: torch.Tensor, k: int, metric: str = "l2", weights=None, seed: int = 0, prune: bool = True):
+    """Exact k-means++ (D^2) seeding of the wide k-means in HIP (include/ogs_kmeans.h, "wide seeding"): ``k`` rounds, each draws one
+    row of ``feat`` [N, D] with probability proportional to ``weights`` times its squared distance to the nearest centre so far.
+    ``"cosine"`` seeds the rows scaled to unit length (mass proportional to 1 - cos); all-zero rows then weigh 0.  ``prune`` skips,
+    unread, the rows the triangle inequality proves unchanged: the same bytes either way.  The same bytes every run.
+
+    Returns ``(centers fp32 [k, D], rows int64 [k] -- -1 past ``stats[0]``, ids int64 [N], d2 fp32 [N], stats int64 [4] on the
+    device: centres seeded, (row, round) pairs evaluated, pairs skipped, 0)``.  Fewer than k distinct weighted rows seed fewer
+    centres: ``centers[stats[0]:]`` is then zero."""
+    if metric not in WIDE_METRICS:
+        raise ValueError(f"metric must be one of {sorted(WIDE_METRICS)}, got {metric!r}")
+    if feat.dim() != 2:
+        raise ValueError(f"feat must be [N, D], got {tuple(feat.shape)}")
+    N, D = int(feat.shape[0]), int(feat.shape[1])
+    k = int(k)
+    lib = _lib.lib()
+    if not 1 <= D <= lib.ogs_kmeans_wide_max_dim():
+        raise ValueError(f"D={D}: the wide k-means takes 1 <= D <= {lib.ogs_kmeans_wide_max_dim()}")
+    if not 1 <= k <= lib.ogs_kmeans_wide_max_k():
+        raise ValueError(f"k={k}: the wide k-means takes 1 <= k <= {lib.ogs_kmeans_wide_max_k()}")
+    if N >= 1 << 31:
+        raise ValueError(f"N={N}: at most 2^31 - 1 rows")
+    if weights is not None and tuple(weights.shape) != (N,):
+        raise ValueError(f"weights must be [{N}], got {tuple(weights.shape)}")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+    _need_gpu(feat, "feat")
+    f = feat.detach().to(torch.float32).contiguous()
+    w = None if weights is None else weights.detach().to(device=f.device, dtype=torch.float32).contiguous()
+    scale = None
+    if metric == "cosine":
+        norm = f.norm(dim=1)
+        scale = torch.where(norm > 0, 1.0 / norm, torch.zeros_like(norm))
+        w = (norm > 0).to(torch.float32) if w is None else torch.where(norm > 0, w, torch.zeros_like(w))
+    centers = torch.zeros(k, D, dtype=torch.float32, device=f.device)
+    rows = torch.full((k,), -1, dtype=torch.int32, device=f.device)
+    ids = torch.zeros(N, dtype=torch.int32, device=f.device)
+    d2 = torch.zeros(N, dtype=torch.float32, device=f.device)
+    stats = torch.zeros(4, dtype=torch.int64, device=f.device)
+    nbytes = int(lib.ogs_kmeans_wide_seed_tmp_bytes(N, D, k))
+    tmp = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
+    check(lib.ogs_kmeans_wide_seed(ptr(f), ptr(w), ptr(scale), N, D, k, int(seed), int(bool(prune)), ptr(centers), ptr(rows), ptr(ids),
+                                   ptr(d2), ptr(stats), ptr(tmp), nbytes, _stream()), "ogs_kmeans_wide_seed")
+    return centers, rows.to(torch.int64), ids.to(torch.int64), d2, stats
+
+
 class _GatherSTE(torch.autograd.Function):
     """value = centres[ids][:, :out_dim]; gradient goes straight through to the instance features
     (kmeans_quantize.py:273-275: ins_feat - ins_feat.detach() + sampled_centers[:, :6])."""

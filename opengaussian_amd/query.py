@@ -848,7 +848,9 @@ def build_codebook(features, k, weights=None, metric="cosine", iters=10, init=No
     ``features`` [N, D] and ``weights`` [N] are what ``features_from_votes`` returns (fp64 is cast to fp32); D up to 1024, k up to
     16384.  A row is VALID when its weight is positive (no weights: every row) and it is not all zero; the other rows are
     assigned like any row but move no centre.  ``init`` [k, D] are the starting centres, or ``None``: the valid rows at a
-    ``torch.randperm`` seeded with ``seed`` (ValueError when there are fewer than k).  ``"cosine"`` normalises the starting
+    ``torch.randperm`` seeded with ``seed`` (ValueError when there are fewer than k), or ``"k-means++"``: exact D^2 seeding over
+    the valid rows with their weights (``kmeans.wide_seed``, HIP, drawn from ``seed``; ValueError when fewer than k distinct rows
+    could be seeded) -- the start to take for scenes whose clusters differ widely in size.  ``"cosine"`` normalises the starting
     centres and keeps them unit vectors; ``"l2"`` clusters the raw vectors.  ``iters`` Lloyd iterations of
     ``kmeans.wide_lloyd`` (HIP, the same bytes every run), then the final assignment.
 
@@ -862,7 +864,10 @@ def build_codebook(features, k, weights=None, metric="cosine", iters=10, init=No
     k = int(k)
     if weights is not None and tuple(weights.shape) != (N,):
         raise ValueError(f"weights must be [{N}], got {tuple(weights.shape)}")
-    if init is not None and tuple(init.shape) != (k, D):
+    plus_plus = isinstance(init, str)
+    if plus_plus and init != "k-means++":
+        raise ValueError(f"init must be None, \"k-means++\" or a [{k}, {D}] tensor, got {init!r}")
+    if init is not None and not plus_plus and tuple(init.shape) != (k, D):
         raise ValueError(f"init must be [{k}, {D}], got {tuple(init.shape)}")
     if metric not in _kmeans.WIDE_METRICS:
         raise ValueError(f"metric must be one of {sorted(_kmeans.WIDE_METRICS)}, got {metric!r}")
@@ -882,6 +887,12 @@ def build_codebook(features, k, weights=None, metric="cosine", iters=10, init=No
             init = features[rows[torch.randperm(rows.numel(), generator=gen)[:k].to(rows.device)]]
         _need_gpu(features, "features")
         feat = _f32(features)
+        if plus_plus:
+            seed_w = valid.to(torch.float32) if weights is None else torch.where(valid, weights.to(feat.device, torch.float32), 0.0)
+            init, _, _, _, stats = _kmeans.wide_seed(feat, k, metric, seed_w, int(seed))
+            seeded = int(stats[0])                       # the one read-back of a seeded build
+            if seeded < k:
+                raise ValueError(f"k-means++ could seed {seeded} of k={k} centres: too few distinct valid rows")
         centers = init.detach().to(device=feat.device, dtype=torch.float32).contiguous().clone()
         if metric == "cosine":
             centers = torch.nn.functional.normalize(centers, dim=1)
