@@ -66,7 +66,8 @@ def _ksum_sorted(points, group, num_groups, k, want_kth=True):
         if G != 1:
             raise ValueError("group=None means one group")
         order = gid = None
-        begin = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        # made on the device: a host list would be uploaded with a copy that waits for the stream (the filter reads nothing back)
+        begin = torch.arange(2, dtype=torch.int64, device=dev) * n
     else:
         _need_gpu(group, "group")
         if group.shape != (n,):

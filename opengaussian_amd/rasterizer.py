@@ -137,9 +137,11 @@ _BG_TILED: dict = {}
 
 
 def _tiled_bg(bg: torch.Tensor, Cn: int) -> torch.Tensor:
-    """the 3-wide background tiled over a fused pass's channels; cached per (storage, version): training passes the same
-    background tensor every iteration and a `repeat` is a launch plus an allocation on a path that is all host time"""
-    key = (bg.data_ptr(), bg._version, Cn, bg.device)
+    """the 3-wide background tiled over a fused pass's channels; cached per (storage, version, stream): training passes the same
+    background tensor every iteration and a `repeat` is a launch plus an allocation on a path that is all host time.
+    Per stream, like _TINY_SCRATCH: the `repeat` runs on the stream of the pass that first asks, and nothing would order a pass
+    on another stream that found the entry behind it (it blended an untiled, uninitialised background)."""
+    key = (bg.data_ptr(), bg._version, Cn, bg.device, _stream())
     hit = _BG_TILED.get(key)
     if hit is None:
         if len(_BG_TILED) > 16:

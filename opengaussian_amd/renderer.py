@@ -238,7 +238,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, iteration,
 
     # same CPU RNG draws, in the same order, as the reference (:121-124)
     prob = torch.rand(1)
-    rescale_factor = torch.tensor(1.0, dtype=torch.float32, device=dev)
+    # filled on the device: torch.tensor(1.0, device=dev) uploads a host scalar with a copy that waits for the stream, which
+    # made every call -- the one-launch re-blend of a kept pass included -- a host synchronisation
+    rescale_factor = torch.ones((), dtype=torch.float32, device=dev)
     rescaled = bool(prob > 0.5 and rescale)
     if rescaled:
         rescale_factor = torch.rand(1).to(dev)
