@@ -181,6 +181,32 @@ typedef struct OgsRasterBwdArgs {
                                     features-only pass with at most 8 feature sums) are zero already -- OgsRasterFwdArgs.bwd_clear
                                     of the forward, and nothing wrote them since -- and the call skips its fill.  0: the call
                                     clears them (the behaviour without this field). */
+    /* Camera gradients (optional; no reference counterpart: the reference treats the camera as a constant).  For the loss L of
+     * this pass (dL_dcolor, dL_ddepth, dL_dalpha) the partial derivatives of L with respect to the three camera arrays AS THE
+     * KERNELS READ THEM, each array treated as independent of the other two:
+     *   dL_dviewmatrix [16], in the storage order of `viewmatrix` (p_view.x = V[0] x + V[4] y + V[8] z + V[12], ...): depth through
+     *       the z row, cov2D through the translation and through the rotation block (T = J W); entries 3, 7, 11, 15 are never read
+     *       by a pass and are written as exact 0.0f;
+     *   dL_dprojmatrix [16]: the pixel position through the hx, hy, hw rows, p_w = 1 / (hw + 1e-7f) differentiated as written;
+     *       entries 2, 6, 10, 14 are exact zeros;
+     *   dL_dcampos [3]: the view direction (mean - campos, normalised) of the SH colours, the clamp mask respected; exact zeros in
+     *       a colors_precomp pass.
+     * The paths are those dL_dmeans3D takes.  Cull, skip and saturation decisions are constants, culled and untouched Gaussians
+     * contribute nothing, and where the +-1.3 tanfov clamp of tx/tz, ty/tz is active the clamped branch is detached (SURVEY.md
+     * A.5).  Any parametrisation of the camera (an se(3) delta, full_proj = view @ P, campos = view.inverse()[3, :3]) is a chain
+     * rule over these 35 numbers.  Every entry is an fp64 sum, in a fixed order, of one fp32 term per Gaussian, rounded once: two
+     * calls on the same state give the same bits, and |error| stays within fp32 rounding of sum |term|.
+     * All three NULL: the call is what it is without these fields -- the same launches, the same bytes.  Any one non-NULL: all
+     * three and pose_tmp must be given (else OGS_ERR_INVALID_ARG), num_groups must be <= 1 (else OGS_ERR_UNSUPPORTED), the pass is
+     * never the features-only one, and two launches follow the per-Gaussian backward on the same stream; all 35 floats are written
+     * on every such call (P == 0, or a view that culls everything: zeros).  The per-Gaussian outputs may then ALL be NULL (a frozen
+     * model whose pose trains): the full blend backward runs and only the 35 floats are written.  Not differentiated: tanfovx /
+     * tanfovy / the image size. */
+    float* dL_dviewmatrix;
+    float* dL_dprojmatrix;
+    float* dL_dcampos;
+    void* pose_tmp;              /* ogs_raster_backward_pose_tmp_bytes(P): one row of partial sums per 256 Gaussians, every row
+                                    written by the call (no clear needed) */
 } OgsRasterBwdArgs;
 
 int ogs_version(void);
@@ -202,6 +228,9 @@ size_t ogs_raster_image_bytes(int32_t W, int32_t H);
 size_t ogs_raster_image_bytes_grouped(int32_t W, int32_t H, int32_t num_groups);
 size_t ogs_raster_binning_tmp_bytes(int64_t num_rendered, int32_t W, int32_t H);
 size_t ogs_raster_backward_tmp_bytes(int32_t P);
+size_t ogs_raster_backward_pose_tmp_bytes(int32_t P);      /* OgsRasterBwdArgs.pose_tmp */
+/* Test hook: how many per-workgroup rows of pose_tmp the second camera-gradient launch adds per step. */
+int ogs_pose_partial_chunk(void);
 size_t ogs_raster_sorted_bytes(int64_t num_rendered, int32_t C);
 size_t ogs_raster_quad_list_bytes(int64_t num_rendered);
 

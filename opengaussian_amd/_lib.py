@@ -46,6 +46,7 @@ class OgsRasterBwdArgs(C.Structure):
         ("dL_dmeans2D", _vp), ("dL_dcolors", _vp), ("dL_dopacity", _vp), ("dL_dmeans3D", _vp),
         ("dL_dcov3D", _vp), ("dL_dsh", _vp), ("dL_dscales", _vp), ("dL_drotations", _vp), ("num_groups", C.c_int32), ("dL_dsh_rgb", _vp),
         ("bwd_tmp_is_clear", C.c_int32),
+        ("dL_dviewmatrix", _vp), ("dL_dprojmatrix", _vp), ("dL_dcampos", _vp), ("pose_tmp", _vp),
     ]
 
 
@@ -111,6 +112,8 @@ SIGNATURES = {
     "ogs_raster_image_bytes_grouped": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "ogs_raster_binning_tmp_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "ogs_raster_backward_tmp_bytes": (C.c_size_t, [C.c_int32]),
+    "ogs_raster_backward_pose_tmp_bytes": (C.c_size_t, [C.c_int32]),
+    "ogs_pose_partial_chunk": (C.c_int, []),
     "ogs_raster_sorted_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "ogs_raster_quad_list_bytes": (C.c_size_t, [C.c_int64]),
     "ogs_raster_forward_geometry": (C.c_int, [C.POINTER(OgsRasterFwdArgs), _vp, C.POINTER(C.c_int64)]),

@@ -251,6 +251,8 @@ size_t ogs_raster_quad_list_bytes(int64_t D) {
     return align_up((size_t)(5 * (D > 0 ? D : 1) + 2 * kQuadPad) * sizeof(uint32_t));
 }
 size_t ogs_raster_backward_tmp_bytes(int32_t P) { return align_up((size_t)(P > 0 ? P : 1) * 16 * sizeof(double)); }
+size_t ogs_raster_backward_pose_tmp_bytes(int32_t P) { return pose_tmp_bytes(P); }
+int ogs_pose_partial_chunk(void) { return pose_partial_chunk(); }
 
 // raw_rest: NULL for the existing entry; otherwise `a` is raw_fwd_args' copy and this is the raw model's features_rest (which may
 // itself be NULL when M == 1: `raw` says which form runs)
@@ -600,6 +602,21 @@ int ogs_raster_forward_tiny_raw(const OgsRasterFwdArgs* a, const OgsRawModel* ra
 static int backward_impl(const OgsRasterBwdArgs* a, void* stream_, const OgsRawModelGrads* raw_grads) {
     if (!a) { set_error("args == NULL"); return OGS_ERR_INVALID_ARG; }
     if (a->C != 3 && a->C != 6 && a->C != 9) { set_error("backward: C=%d unsupported (3, 6, 9)", a->C); return OGS_ERR_UNSUPPORTED; }
+    // camera gradients (pose_bwd.hip): all of the three outputs and their scratch, or none
+    const bool pose = backward_wants_pose(*a);
+    if (pose) {
+        if (!a->dL_dviewmatrix || !a->dL_dprojmatrix || !a->dL_dcampos || !a->pose_tmp) {
+            set_error("backward: dL_dviewmatrix, dL_dprojmatrix, dL_dcampos and pose_tmp must be given together");
+            return OGS_ERR_INVALID_ARG;
+        }
+        if (a->P < 0) { set_error("backward: P=%d", a->P); return OGS_ERR_INVALID_ARG; }
+        if (a->num_groups > 1) {
+            set_error("backward: camera gradients of a grouped pass (num_groups=%d) are not supported", a->num_groups);
+            return OGS_ERR_UNSUPPORTED;
+        }
+        // nothing was blended: the 35 floats are still written, as zeros (the fold of no rows)
+        if (a->P == 0) return launch_pose_backward(*a, GeomState{}, nullptr, static_cast<hipStream_t>(stream_), false);
+    }
     if (a->P == 0) return OGS_OK;
     // the features-only pass reads the blend state and the radii alone: a caller that kept only those (the re-blend of a kept
     // pass, ogs_raster_forward_reblend) may leave the per-Gaussian inputs, geom_buffer and point_list NULL
@@ -626,6 +643,13 @@ static int backward_impl(const OgsRasterBwdArgs* a, void* stream_, const OgsRawM
     if (a->num_groups < 0) { set_error("backward: num_groups=%d", a->num_groups); return OGS_ERR_INVALID_ARG; }
     const ImageState is = ImageState::carve(const_cast<void*>(a->image_buffer), a->W, a->H, num_groups_of(a->num_groups));
     void* grad_rec = a->bwd_tmp;
+    if (pose) {
+        // what pose_partials_kernel re-derives the covariance from; every check of such a call comes before its first launch
+        if (!a->cov3D_precomp && (!a->scales || !a->rotations)) {
+            set_error("backward: camera gradients need scales + rotations or cov3D_precomp"); return OGS_ERR_INVALID_ARG;
+        }
+        if (a->num_rendered > 0 && (!a->sorted_rec || !a->quad_list)) { set_error("backward: sorted_rec / quad_list == NULL"); return OGS_ERR_INVALID_ARG; }
+    }
     // features-only pass: a record is the feature sums alone, 64 bytes when they fit (feat_grad_stride) -- half the fill.  (A strided
     // hipMemset2DAsync over the front halves of full-size records cost 0.1 ms against 0.016 ms for a contiguous fill: measured.)
     const int rec_doubles = feat_only ? feat_grad_stride(a->C, a->shs ? 3 : 0) : grad_stride(a->C);
@@ -634,7 +658,15 @@ static int backward_impl(const OgsRasterBwdArgs* a, void* stream_, const OgsRawM
     if (a->num_rendered > 0 && (!a->sorted_rec || !a->quad_list)) { set_error("backward: sorted_rec / quad_list == NULL"); return OGS_ERR_INVALID_ARG; }
     int rc = launch_blend_backward(*a, is, grad_rec, s);
     if (rc != OGS_OK) return rc;
-    return launch_preprocess_backward(*a, gs, grad_rec, s, raw_grads);
+    if (!pose) return launch_preprocess_backward(*a, gs, grad_rec, s, raw_grads);
+    // a pose-only call (frozen model) has no per-Gaussian output: preprocess_backward would read every record to write nothing
+    const bool per_gaussian = a->dL_dmeans2D || a->dL_dcolors || a->dL_dopacity || a->dL_dmeans3D || a->dL_dcov3D || a->dL_dsh ||
+                              a->dL_dscales || a->dL_drotations || a->dL_dsh_rgb || (raw_grads && raw_grads->features_rest);
+    if (per_gaussian) {
+        rc = launch_preprocess_backward(*a, gs, grad_rec, s, raw_grads);
+        if (rc != OGS_OK) return rc;
+    }
+    return launch_pose_backward(*a, gs, grad_rec, s, raw_grads != nullptr);
 }
 
 int ogs_raster_backward(const OgsRasterBwdArgs* a, void* stream_) { return backward_impl(a, stream_, nullptr); }

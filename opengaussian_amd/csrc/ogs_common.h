@@ -460,10 +460,18 @@ int launch_preprocess_backward(const OgsRasterBwdArgs& a, const GeomState& gs, c
                                const OgsRawModelGrads* raw_grads = nullptr);
 // Only dL/dcolors_precomp is requested (every other output pointer NULL): the stage >= 1 training graph
 // (train.py:431-436) -> features-only kernels.
+// Camera gradients (pose_bwd.hip) are asked for: they need the geometry slots of the record, so such a pass is never features-only.
+inline bool backward_wants_pose(const OgsRasterBwdArgs& a) { return a.dL_dviewmatrix || a.dL_dprojmatrix || a.dL_dcampos; }
 inline bool backward_is_features_only(const OgsRasterBwdArgs& a) {
     return a.dL_dcolors != nullptr && a.colors_precomp != nullptr && !a.dL_dmeans2D && !a.dL_dopacity &&
-           !a.dL_dmeans3D && !a.dL_dcov3D && !a.dL_dsh && !a.dL_dscales && !a.dL_drotations && !a.dL_dsh_rgb;
+           !a.dL_dmeans3D && !a.dL_dcov3D && !a.dL_dsh && !a.dL_dscales && !a.dL_drotations && !a.dL_dsh_rgb &&
+           !backward_wants_pose(a);
 }
+// the two camera-gradient launches (partials per workgroup into a.pose_tmp, then one workgroup folds them into the 35 floats);
+// P == 0: the fold alone, which writes zeros.  raw: `a` holds the raw model in its pointer slots, as launch_preprocess_backward
+int launch_pose_backward(const OgsRasterBwdArgs& a, const GeomState& gs, const void* grad_rec, hipStream_t s, bool raw);
+size_t pose_tmp_bytes(int P);
+int pose_partial_chunk();
 int launch_sh_grad_from_views(int P, int V, int sh_degree, int sh_coeffs, const float* means3D, const float* campos,
                               const float* dL_drgb, float* dL_dsh, hipStream_t s);
 int launch_wave_fold16_test(const float* in, float* out, hipStream_t s);

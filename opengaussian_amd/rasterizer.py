@@ -181,16 +181,49 @@ class full_binning:
 HOST_BWD_CLEAR = True
 
 
-def _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov) -> int:
+def _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov, pose=False) -> int:
     """Bytes of the gradient record ogs_raster_backward uses (and clears) for the gradient families `need` selects: 64 per
     Gaussian when only dL/dcolors_precomp of at most 8 channels is produced (features-only pass), else 128 (csrc/ogs_common.h
-    grad_stride / feat_grad_stride; the backward supports Cn <= 9)."""
+    grad_stride / feat_grad_stride; the backward supports Cn <= 9).  pose: the camera tensors train -- never features-only, the
+    full record even when no per-Gaussian family is selected."""
+    if pose:
+        return P * 128
     want_cols = bool(need[3]) and cols is not None
     other = (need[0] or need[1] or (need[2] and shs is not None) or need[4] or (need[5] and scl is not None)
              or (need[6] and rot is not None) or (need[7] and cov is not None))
     feat_only = want_cols and not other
     feat_sums = Cn - (3 if shs is not None else 0)
     return P * (64 if (feat_only and feat_sums <= 8) else 128)
+
+
+def _camera_leaves(rs):
+    """(viewmatrix, projmatrix, campos) of the settings when autograd has to reach one of them, else (): the three trailing
+    inputs of _RasterizeGaussians / _RasterizeModel.  Empty for every caller whose camera is a constant, whose call is then
+    argument for argument what it was before the camera could train."""
+    cam = (rs.viewmatrix, rs.projmatrix, rs.campos)
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam):
+        return cam
+    return ()
+
+
+def _pose_outputs(lib, b, P, dev):
+    """allocates the three camera gradients and their scratch and points `b` at them; returns (g_view, g_proj, g_campos, tmp)"""
+    g_view = torch.empty(16, dtype=torch.float32, device=dev)
+    g_proj = torch.empty(16, dtype=torch.float32, device=dev)
+    g_campos = torch.empty(3, dtype=torch.float32, device=dev)
+    tmp = torch.empty(int(lib.ogs_raster_backward_pose_tmp_bytes(P)), dtype=torch.uint8, device=dev)
+    b.dL_dviewmatrix, b.dL_dprojmatrix, b.dL_dcampos, b.pose_tmp = ptr(g_view), ptr(g_proj), ptr(g_campos), ptr(tmp)
+    return g_view, g_proj, g_campos, tmp
+
+
+def _pose_like(cam):
+    """(shape, dtype, device) of the three camera inputs: what their gradients must look like (the tensors are not held)"""
+    return tuple((t.shape, t.dtype, t.device) for t in cam)
+
+
+def _pose_grads(need3, grads, like):
+    """the gradients autograd gets for the three camera inputs: in their shapes, dtypes and devices, None where not needed"""
+    return tuple(g.reshape(shape).to(device=dev, dtype=dtype) if n else None for n, g, (shape, dtype, dev) in zip(need3, grads, like))
 
 
 def _fwd_args(rs, P, Cn, m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, color, depth, alpha, radii, group_ids, G):
@@ -297,7 +330,10 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings: GaussianRasterizationSettings, geom_channels: int = 0, sh_rgb_sink=None,
-                group_ids=None, num_groups: int = 1, keep_sink=None, force_streaming: bool = False):
+                group_ids=None, num_groups: int = 1, keep_sink=None, force_streaming: bool = False,
+                viewmatrix=None, projmatrix=None, campos=None):
+        # viewmatrix / projmatrix / campos (optional): the settings' camera tensors again, as autograd inputs (_camera_leaves) --
+        # given when one of them requires grad; the pass reads the camera from the settings either way
         # force_streaming (internal, label_map): a P <= TINY_MAX_P pass takes the streaming path, which leaves the state a
         # label map walks; the default path selection is untouched
         rs = raster_settings
@@ -308,6 +344,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         G = max(int(num_groups), 1)
         ctx.num_groups = G
+        pose = any(ctx.needs_input_grad[15:18])
+        ctx.pose_like = _pose_like((viewmatrix, projmatrix, campos)) if pose else None
+        if pose and G > 1:
+            raise RuntimeError("camera gradients of a grouped pass are not supported: detach the camera tensors")
         if G > 1:
             if group_ids is None or group_ids.shape[0] != means3D.shape[0]:
                 raise RuntimeError("a grouped pass needs group_ids [P]")
@@ -335,7 +375,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             Cn = 3 if cols is None else int(cols.shape[1])
         if Cn not in SUPPORTED_CHANNELS:
             raise RuntimeError(f"the blended channel count must be 3, 6, 9 or 12, got {Cn}")
-        if Cn not in BACKWARD_CHANNELS and any(ctx.needs_input_grad[:8]):
+        if Cn not in BACKWARD_CHANNELS and (any(ctx.needs_input_grad[:8]) or pose):
             # fail here, not in the middle of loss.backward()
             raise RuntimeError(f"a {Cn}-channel pass is forward-only (backward supports {BACKWARD_CHANNELS} channels): "
                                "detach the inputs or split the pass")
@@ -385,11 +425,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             return color, radii, depth, alpha
 
         need = ctx.needs_input_grad
-        if HOST_BWD_CLEAR and G == 1 and not rs.debug and any(need[:8]):
+        if HOST_BWD_CLEAR and G == 1 and not rs.debug and (any(need[:8]) or pose):
             # the gradient record of this pass' backward: allocated here, zeroed by the render phase on its way, held until the
             # backward runs.  How much of it the backward uses is known from the requires_grad flags
             bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
-            a.bwd_clear, a.bwd_clear_bytes = ptr(bwd_tmp), _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov)
+            a.bwd_clear, a.bwd_clear_bytes = ptr(bwd_tmp), _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov, pose)
         geom, image, point_list, sorted_rec, quad_list, D = _streaming_render(a, dev, lib, rs.debug)
         ctx.num_rendered = D
         if a.bwd_clear:
@@ -410,7 +450,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         rs = ctx.raster_settings
         P, Cn = ctx.P, ctx.Cn
         if P == 0:
-            return (None,) * 15
+            return (None,) * 18
         lib = _lib.lib()
         H, W = int(rs.image_height), int(rs.image_width)
         scratch = None
@@ -456,12 +496,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         # takes a fresh buffer and the fill
         bwd_tmp, is_clear = ctx.bwd_tmp, False
         if bwd_tmp is not None:
-            is_clear = ctx.bwd_clear_bytes >= _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov)
+            is_clear = ctx.bwd_clear_bytes >= _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov, ctx.pose_like is not None)
             ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
         else:
             bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
 
         b = OgsRasterBwdArgs()
+        pose_out = _pose_outputs(lib, b, P, dev) if ctx.pose_like is not None else None
         b.bwd_tmp_is_clear = int(is_clear)
         b.P, b.W, b.H, b.C = P, W, H, Cn
         b.sh_degree = int(rs.sh_degree)
@@ -487,7 +528,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             _DEBUG_KEEP_BWD_TMP.append(bwd_tmp)
         if sink is not None:
             sink.append(g_sh_rgb)
-        return g_m3, g_m2, g_sh, g_col, g_op, g_scl, g_rot, g_cov, None, None, None, None, None, None, None
+        g_cam = (None, None, None) if pose_out is None else _pose_grads(need[15:18], pose_out[:3], ctx.pose_like)
+        return (g_m3, g_m2, g_sh, g_col, g_op, g_scl, g_rot, g_cov, None, None, None, None, None, None, None) + g_cam
 
 
 # ---- kept passes: the frozen-geometry cache ------------------------------------------------------------------------------
@@ -989,6 +1031,10 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     """sh_rgb_sink (extension, data parallelism): a list.  When given, backward does NOT produce the dense
     dL/dsh (shs.grad stays None); it appends the [P,3] clamp-masked gradient of the SH-evaluated RGB instead, from
     which dp.ShGradExchange rebuilds the sum over views of dL/dsh (see include/ogs_raster.h, dL_dsh_rgb)."""
+    cam = _camera_leaves(raster_settings)
+    if cam:
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, raster_settings, 0, sh_rgb_sink, None, 1, None, False, *cam)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, 0, sh_rgb_sink)
 
@@ -1015,6 +1061,10 @@ def rasterize_fused(means3D, means2D, opacities, shs, extra_feats, raster_settin
     args = (means3D, means2D, shs, extra_feats, opacities, empty if scales is None else scales,
             empty if rotations is None else rotations, empty if cov3D_precomp is None else cov3D_precomp, raster_settings,
             3 if detach_extra_from_geometry else 0, sh_rgb_sink)
+    cam = _camera_leaves(raster_settings)
+    if cam:
+        # a camera that trains: nothing of the pass is frozen, whatever `frozen_key` vouches for
+        return _RasterizeGaussians.apply(*args, None, 1, None, False, *cam)
     if frozen_key is None or not means3D.is_cuda or not KEPT_PASSES.enabled(means3D.device) or raster_settings.debug or \
             (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in
                                              (means3D, means2D, opacities, shs, scales, rotations, cov3D_precomp))):
@@ -1044,10 +1094,13 @@ class _RasterizeModel(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, extra_feats,
-                raster_settings: GaussianRasterizationSettings, geom_channels: int = 0):
+                raster_settings: GaussianRasterizationSettings, geom_channels: int = 0, viewmatrix=None, projmatrix=None,
+                campos=None):
         rs = raster_settings
         ctx.geom_channels = int(geom_channels)
         ctx.set_materialize_grads(False)
+        pose = any(ctx.needs_input_grad[10:13])         # as _RasterizeGaussians: the settings' camera tensors as inputs
+        ctx.pose_like = _pose_like((viewmatrix, projmatrix, campos)) if pose else None
         for t, name in ((means3D, "means3D"), (features_dc, "features_dc"), (opacity_raw, "opacity_raw"),
                         (scaling_raw, "scaling_raw"), (rotation_raw, "rotation_raw")):
             _require_gpu(t, name)
@@ -1074,7 +1127,7 @@ class _RasterizeModel(torch.autograd.Function):
         Cn = 3 + (0 if cols is None else int(cols.shape[1]))
         if Cn not in SUPPORTED_CHANNELS:
             raise RuntimeError(f"the blended channel count must be 3, 6, 9 or 12, got {Cn}")
-        if Cn not in BACKWARD_CHANNELS and any(ctx.needs_input_grad[:8]):
+        if Cn not in BACKWARD_CHANNELS and (any(ctx.needs_input_grad[:8]) or pose):
             raise RuntimeError(f"a {Cn}-channel pass is forward-only (backward supports {BACKWARD_CHANNELS} channels): "
                                "detach the inputs or split the pass")
         bg = _f32c(rs.bg.to(dev))
@@ -1112,9 +1165,9 @@ class _RasterizeModel(torch.autograd.Function):
             ctx.mark_non_differentiable(radii)
             return color, radii, depth, alpha
         need = ctx.needs_input_grad
-        if HOST_BWD_CLEAR and not rs.debug and any(need[:8]):
+        if HOST_BWD_CLEAR and not rs.debug and (any(need[:8]) or pose):
             bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
-            a.bwd_clear, a.bwd_clear_bytes = ptr(bwd_tmp), _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot)
+            a.bwd_clear, a.bwd_clear_bytes = ptr(bwd_tmp), _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot, pose)
         geom, image, point_list, sorted_rec, quad_list, D = _streaming_render(a, dev, lib, rs.debug, raw)
         ctx.num_rendered = D
         if a.bwd_clear:
@@ -1125,17 +1178,17 @@ class _RasterizeModel(torch.autograd.Function):
         return color, radii, depth, alpha
 
     @staticmethod
-    def _record_bytes(need, P, Cn, dc, cols, scl, rot) -> int:
+    def _record_bytes(need, P, Cn, dc, cols, scl, rot, pose=False) -> int:
         # in _RasterizeGaussians' order: means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D
         return _grad_record_bytes((need[0], need[1], need[2] or need[3], need[7], need[4], need[5], need[6], False), P, Cn, dc,
-                                  cols, scl, rot, None)
+                                  cols, scl, rot, None, pose)
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
         rs = ctx.raster_settings
         P, Cn, M = ctx.P, ctx.Cn, ctx.M
         if P == 0:
-            return (None,) * 10
+            return (None,) * 13
         lib = _lib.lib()
         H, W = int(rs.image_height), int(rs.image_width)
         scratch = None
@@ -1171,7 +1224,7 @@ class _RasterizeModel(torch.autograd.Function):
         gd, ga = _f32c(grad_depth), _f32c(grad_alpha)
         bwd_tmp, is_clear = ctx.bwd_tmp, False
         if bwd_tmp is not None:
-            is_clear = ctx.bwd_clear_bytes >= _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot)
+            is_clear = ctx.bwd_clear_bytes >= _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot, ctx.pose_like is not None)
             ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
         else:
             bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
@@ -1193,9 +1246,11 @@ class _RasterizeModel(torch.autograd.Function):
         grads = OgsRawModelGrads()
         grads.features_dc, grads.features_rest, grads.scaling, grads.rotation, grads.opacity = \
             ptr(g_dc), ptr(g_rest), ptr(g_scl), ptr(g_rot), ptr(g_op)
+        pose_out = _pose_outputs(lib, b, P, dev) if ctx.pose_like is not None else None
         check(lib.ogs_raster_backward_raw(C.byref(b), C.byref(raw), C.byref(grads), _stream()), "ogs_raster_backward_raw")
         scratch = None
-        return g_m3, g_m2, g_dc, g_rest, g_op, g_scl, g_rot, g_col, None, None
+        g_cam = (None, None, None) if pose_out is None else _pose_grads(need[10:13], pose_out[:3], ctx.pose_like)
+        return (g_m3, g_m2, g_dc, g_rest, g_op, g_scl, g_rot, g_col, None, None) + g_cam
 
 
 def rasterize_model(means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings,
@@ -1207,7 +1262,8 @@ def rasterize_model(means3D, means2D, features_dc, features_rest, opacity_raw, s
     to the raw parameters: no activated copies, no torch graph between the parameters and the rasterizer.  Same four outputs,
     bit for bit those of the existing pass fed with activate_model's outputs.  CPU tensors raise: there is no fallback."""
     return _RasterizeModel.apply(means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
-                                 extra_feats, raster_settings, 3 if (detach_extra_from_geometry and extra_feats is not None) else 0)
+                                 extra_feats, raster_settings, 3 if (detach_extra_from_geometry and extra_feats is not None) else 0,
+                                 *_camera_leaves(raster_settings))
 
 
 def activate_model(features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw):

@@ -118,7 +118,8 @@ def _frozen_geometry_key(viewpoint_camera, pc, pipe, xyz, scaling_modifier):
     by the entry, so an address cannot be handed out again while its key is in use.  NOT covered: writes through `.data` or
     raw pointers (they leave the counter alone) -- call ``rasterizer.clear_kept()`` after such a write, or set
     OGS_KEPT_PASSES_GB=0.  Returns None when the model does not look like the reference's GaussianModel (no such attributes,
-    `get_xyz` not the `_xyz` parameter itself), when anything still requires grad, or under `pipe.debug`."""
+    `get_xyz` not the `_xyz` parameter itself), when anything still requires grad -- a camera tensor included -- or under
+    `pipe.debug`."""
     if getattr(pipe, "debug", False) or getattr(pipe, "compute_cov3D_python", False) or getattr(pipe, "convert_SHs_python", False):
         return None
     params = []
@@ -131,6 +132,10 @@ def _frozen_geometry_key(viewpoint_camera, pc, pipe, xyz, scaling_modifier):
         return None
     cam = (viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center)
     if not all(isinstance(t, torch.Tensor) for t in cam):
+        return None
+    if any(t.requires_grad for t in cam):
+        # a camera that trains (pose.CameraPose): its tensors are rebuilt every call, a key made of their recycled addresses
+        # could serve the pass of an older pose
         return None
     ident = lambda t: (t.data_ptr(), t._version, tuple(t.shape))
     key = (tuple(ident(t) for t in params), tuple(ident(t) for t in cam), int(viewpoint_camera.image_height),
@@ -253,7 +258,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, iteration,
     # a 12-channel pass has no backward (gradient record: C + 7 <= 16 slots): only fuse / widen that far without grad
     differentiable = torch.is_grad_enabled() and any(
         t is not None and t.requires_grad for t in (means3D, means2D, opacity, scales, rotations, cov3D_precomp, shs,
-                                                    colors_precomp, ins_feat) + (tuple(raw.values()) if raw is not None else ()))
+                                                    colors_precomp, ins_feat, raster_settings.viewmatrix,
+                                                    raster_settings.projmatrix, raster_settings.campos)
+        + (tuple(raw.values()) if raw is not None else ()))
     max_pass_channels = 9 if differentiable else 12
     can_fuse = (render_color and render_feat_map and not rescaled and ins_feat.shape[-1] in (3, 6, 9)
                 and ins_feat.shape[-1] + 3 <= max_pass_channels)
