@@ -323,3 +323,17 @@ def prof_collect() -> dict:
 def ptr(t):
     """Device pointer of a torch tensor (or None)."""
     return None if t is None else t.data_ptr()
+
+
+def mark_written(*tensors):
+    """Tell torch that a kernel wrote these tensors through their raw pointers: bump each one's version counter, as an in-place
+    torch op would.  The counter is shared by a tensor, its ``detach()`` aliases and its views, so everything keyed on
+    ``(data_ptr, _version)`` -- the kept passes and images, the tiled background, ``CameraPose`` -- and autograd's saved-tensor
+    check see the write.  Every public call that writes a caller-visible tensor through ``data_ptr()`` calls this after it has
+    enqueued its launches, for exactly the tensors it wrote (DESIGN.md section 3b lists them).  Host bookkeeping only: no
+    launch, no synchronisation.  ``None`` entries are skipped; leaves that require grad are fine, in either grad mode."""
+    import torch
+    written = [t for t in tensors if t is not None]
+    if written:
+        with torch.no_grad():
+            torch.autograd.graph.increment_version(written)

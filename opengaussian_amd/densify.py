@@ -242,6 +242,7 @@ def add_densification_stats(state: DensifyState, viewspace_grad: torch.Tensor, u
     mr = state.max_radii2D if rad is not None else None
     check(_lib.lib().ogs_densify_stats(N, ptr(g), int(g.shape[1]), ptr(vis), ptr(rad), ptr(state.xyz_gradient_accum),
                                        ptr(state.denom), ptr(mr), _stream()), "ogs_densify_stats")
+    _lib.mark_written(state.xyz_gradient_accum, state.denom, mr)       # mr: None unless the kernel took the radii
 
 
 def reset_opacity(state: DensifyState) -> Dict[str, nn.Parameter]:

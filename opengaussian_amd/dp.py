@@ -161,6 +161,7 @@ class ShGradExchange:
         g = self.wait()
         if not g.is_cuda:
             raise RuntimeError("ShGradExchange.rebuild needs the HIP library (GPU tensors)")
+        given = out is not None
         if out is None:
             out = torch.empty(self.P, self.M, 3, dtype=torch.float32, device=g.device)
         m3 = means3D.detach().to(torch.float32).contiguous()
@@ -170,6 +171,8 @@ class ShGradExchange:
         _lib.check(_lib.lib().ogs_sh_grad_from_views(self.P, self.world, int(sh_degree), self.M, m3.data_ptr(),
                                                      cp.data_ptr(), g.data_ptr(), out.data_ptr(),
                                                      torch.cuda.current_stream().cuda_stream), "ogs_sh_grad_from_views")
+        if given:
+            _lib.mark_written(out)                  # the caller's tensor, written through its raw pointer
         return out
 
 
@@ -388,6 +391,9 @@ class ShardedAdam:
             arr = (OgsAdamTensor * len(chunk))(*chunk)
             _lib.check(_lib.lib().ogs_adam_step(arr, len(chunk), float(self.betas[0]), float(self.betas[1]), float(self.eps),
                                                 torch.cuda.current_stream().cuda_stream), "ogs_adam_step")
+        if descs:
+            # written through raw pointers; the parameter views move with `flat` below, through torch's own copy / all-gather
+            _lib.mark_written(self.my_param, self.exp_avg, self.exp_avg_sq)
         if self.on:
             dist.all_gather_into_tensor(self.flat, self.my_param, group=self.group)
         else:

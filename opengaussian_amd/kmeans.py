@@ -41,6 +41,7 @@ def lloyd(feat: torch.Tensor, centers: torch.Tensor, iters: int, nchunks: int, k
     check(lib.ogs_kmeans_lloyd(ptr(f) if N else None, N, d, ptr(centers), k, int(k if k_active is None else k_active),
                                int(iters), int(nchunks), ptr(ids) if N else None, int(id_offset), ptr(tmp), _stream()),
           "ogs_kmeans_lloyd")
+    _lib.mark_written(centers)                  # updated through its raw pointer: move its version counter, as torch would
     return ids
 
 
@@ -72,6 +73,8 @@ def lloyd_sharded(feat: torch.Tensor, centers: torch.Tensor, iters: int, nchunks
             dist.all_reduce(table, op=dist.ReduceOp.SUM, group=group)
         check(lib.ogs_kmeans_update(ptr(table), k, d, int(nchunks), ptr(counts), ptr(centers), _stream()),
               "ogs_kmeans_update")
+    if int(iters) > 0:
+        _lib.mark_written(centers)
     return assign(f, centers[:ka], id_offset) if N else torch.empty(0, dtype=torch.int64, device=f.device)
 
 
@@ -156,6 +159,7 @@ def wide_update(feat: torch.Tensor, ids: torch.Tensor, centers: torch.Tensor, me
     tmp, nbytes = _wide_tmp(N, D, k, f.device)
     check(_lib.lib().ogs_kmeans_wide_update(ptr(f), ptr(w), N, D, ptr(i32), k, m, ptr(centers), ptr(counts), ptr(tmp), nbytes,
                                             _stream()), "ogs_kmeans_wide_update")
+    _lib.mark_written(centers)
     return counts
 
 
@@ -177,6 +181,7 @@ def wide_lloyd(feat: torch.Tensor, centers: torch.Tensor, iters: int, metric: st
     tmp, nbytes = _wide_tmp(N, D, k, f.device)
     check(_lib.lib().ogs_kmeans_wide_lloyd(ptr(f), ptr(w), N, D, ptr(centers), k, m, int(iters), ptr(ids), ptr(dist), ptr(counts),
                                            ptr(inertia), ptr(tmp), nbytes, _stream()), "ogs_kmeans_wide_lloyd")
+    _lib.mark_written(centers)
     return ids.to(torch.int64), dist, counts, inertia
 
 

@@ -35,6 +35,7 @@ class FusedAdam(torch.optim.Optimizer):
         lib = _lib.lib()
         stream = torch.cuda.current_stream().cuda_stream
         keep = []                                   # contiguous gradient copies must outlive the launch call
+        written = []                                # every stepped parameter and its two moments
         # descriptors of EVERY group, bucketed by (beta1, beta2, eps) -- launch-level constants of ogs_adam_step.  The
         # reference's seven groups share them (scene/gaussian_model.py:230), so a step is ONE launch.
         buckets = {}
@@ -69,6 +70,7 @@ class FusedAdam(torch.optim.Optimizer):
                 d.exp_avg, d.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
                 d.numel, d.lr, d.step = p.numel(), float(group["lr"]), int(st["step"].item())
                 descs.append(d)
+                written += [p, st["exp_avg"], st["exp_avg_sq"]]
         self.last_step_launches = 0
         for (beta1, beta2, eps), descs in buckets.items():
             for i in range(0, len(descs), MAX_TENSORS):
@@ -76,4 +78,6 @@ class FusedAdam(torch.optim.Optimizer):
                 arr = (OgsAdamTensor * len(chunk))(*chunk)
                 check(lib.ogs_adam_step(arr, len(chunk), beta1, beta2, eps, stream), "ogs_adam_step")
                 self.last_step_launches += 1
+        # the kernel wrote through raw pointers: move the version counters torch.optim.Adam's in-place ops would have moved
+        _lib.mark_written(*written)
         return loss

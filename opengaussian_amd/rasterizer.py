@@ -634,8 +634,9 @@ class KeptPasses:
         e.P, e.W, e.H, e.Cn, e.fused, e.D = kept["P"], W, H, Cn, bool(kept["fused"]), used
         e.E = Cn - 3 if e.fused else Cn
         e.full_binning = kept["full_binning"]
-        e.radii = kept["radii"]
         try:
+            # the entry's own copy (4 B per Gaussian): the pass already handed `radii` to its caller, who may write into it
+            e.radii = kept["radii"].clone()
             # the pass laid its records and quadrant streams out by the ranges of the sorted list, sized for a capacity; what is
             # kept is what the tiles PACKED (all a re-blend reads), re-laid out by the exclusive scan of those counts
             e.image = image.clone()
@@ -720,7 +721,8 @@ KEPT_IMAGES = KeptImages()
 
 
 def clear_kept():
-    """Forget every kept pass and kept image (after parameter values were written behind torch's back: `.data`, raw pointers)."""
+    """Forget every kept pass and kept image (after parameter values were written behind torch's back: torch ops on `.data`, a
+    foreign kernel on `data_ptr()`; this library's own raw-pointer writers move the version counters themselves)."""
     KEPT_PASSES.clear()
     KEPT_IMAGES.clear()
 
@@ -739,6 +741,10 @@ class _ReblendKept(torch.autograd.Function):
         cols = _f32c(extra_feats)
         if cols is None or tuple(cols.shape) != (P, entry.E):
             raise RuntimeError(f"the kept pass blends {entry.E} caller channels of {P} Gaussians, got {tuple(extra_feats.shape)}")
+        if Cn not in BACKWARD_CHANNELS and ctx.needs_input_grad[0]:
+            # as _RasterizeGaussians.forward: fail here, not in the middle of loss.backward()
+            raise RuntimeError(f"a {Cn}-channel pass is forward-only (backward supports {BACKWARD_CHANNELS} channels): "
+                               "detach the inputs or split the pass")
         bg = _f32c(rs.bg.to(dev))
         if bg is None or bg.numel() != Cn:
             if bg is not None and bg.numel() == 3 and Cn > 3:
@@ -759,7 +765,7 @@ class _ReblendKept(torch.autograd.Function):
         PASS_STATS["reblend"] += 1
         ctx.entry, ctx.raster_settings = entry, rs
         ctx.save_for_backward(cols)
-        radii = entry.radii.detach()                   # an alias: the pass' radii are those of the kept pass
+        radii = entry.radii.clone()                    # the kept pass' radii, as the caller's own tensor (backward reads the entry's)
         ctx.mark_non_differentiable(radii)
         return color, radii, depth, alpha
 
@@ -923,6 +929,8 @@ def label_votes(kept, pixel_labels, num_labels, rows=None, num_rows=None, out=No
     lv.rows, lv.num_rows = ptr(row), Rn
     lv.votes = ptr(votes)
     check(_lib.lib().ogs_raster_label_votes(C.byref(_kept_args(state)), C.byref(lv), _stream()), "ogs_raster_label_votes")
+    if out is not None:
+        _lib.mark_written(out)                         # the caller's table, accumulated into through its raw pointer
     return votes
 
 
@@ -977,6 +985,8 @@ def feature_votes(kept, features, valid=None, rows=None, num_rows=None, out=None
     fv.rows, fv.num_rows = ptr(row), Rn
     fv.votes = ptr(votes)
     check(_lib.lib().ogs_raster_feature_votes(C.byref(_kept_args(state)), C.byref(fv), _stream()), "ogs_raster_feature_votes")
+    if out is not None:
+        _lib.mark_written(out)
     return votes
 
 

@@ -115,8 +115,11 @@ def _frozen_geometry_key(viewpoint_camera, pc, pipe, xyz, scaling_modifier):
     "nothing changed": the storage address and torch's version counter of each parameter (every in-place update -- an optimizer
     step, `reset_opacity`, densification's `cat` -- bumps the counter or moves the storage; `.detach()`, which train.py repeats
     every iteration, does neither), the camera's matrices likewise, and the scalar settings of the pass.  The tensors are held
-    by the entry, so an address cannot be handed out again while its key is in use.  NOT covered: writes through `.data` or
-    raw pointers (they leave the counter alone) -- call ``rasterizer.clear_kept()`` after such a write, or set
+    by the entry, so an address cannot be handed out again while its key is in use.  The library's own raw-pointer writers --
+    FusedAdam / ShardedAdam steps, the k-means centre updates, the densification statistics -- move the counter themselves
+    (``_lib.mark_written``, table in DESIGN.md section 3b), so a detached alias of a parameter they step is seen as changed.
+    What still leaves the counter alone: a FOREIGN kernel writing through ``data_ptr()`` and torch ops on ``p.data`` (`.data`
+    has a counter of its own) -- call ``rasterizer.clear_kept()`` after such a write, or ``_lib.mark_written(p)``, or set
     OGS_KEPT_PASSES_GB=0.  Returns None when the model does not look like the reference's GaussianModel (no such attributes,
     `get_xyz` not the `_xyz` parameter itself), when anything still requires grad -- a camera tensor included -- or under
     `pipe.debug`."""
