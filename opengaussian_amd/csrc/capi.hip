@@ -297,20 +297,10 @@ static int forward_geometry_impl(const OgsRasterFwdArgs* a_in, void* stream_, in
         // three passes, the scan and duplicate run on the visible count (device word; the launches stay sized for P).  On the
         // bench scene that is 14 % of the Gaussians; a camera inside a room-scale scene sees a fraction of the model
         // (the reference only ever sorts the pairs of visible Gaussians: SURVEY.md Appendix A.2).
-        const bool sweep = radix_onesweep_enabled(a->P);
-        if (sweep) {
-            const int shifts[4] = {0, 8, 16, 24}, nbits[4] = {8, 8, 8, 8};
-            rc = radix_sort_begin(gt.keys[0], a->P, nullptr, 4, shifts, nbits, gt.sort_tmp, s, a->debug, true);
-            if (rc != OGS_OK) return rc;
-        }
-        for (int pass = 0; pass < 4; ++pass) {
-            const int in = pass & 1, out = in ^ 1;
-            const bool drop = pass == 0;
-            const uint32_t* n_pass = drop ? nullptr : gt.visible();
-            rc = sweep ? radix_sort_pass(pass, 4, gt.keys[in], gt.order[in], gt.keys[out], gt.order[out], a->P, 8 * pass, 8, gt.sort_tmp, s, a->debug, n_pass, drop, drop ? gt.visible() : nullptr)
-                       : radix_pass(gt.keys[in], gt.order[in], gt.keys[out], gt.order[out], a->P, 8 * pass, 8, gt.sort_tmp, s, a->debug, n_pass, drop, drop ? gt.visible() : nullptr);
-            if (rc != OGS_OK) return rc;
-        }
+        const RadixSort depth_sort = {{gt.keys[0], gt.keys[1]}, {gt.order[0], gt.order[1]}, a->P, nullptr, 4, {0, 8, 16, 24}, {8, 8, 8, 8},
+                                      true, gt.visible(), gt.sort_tmp};
+        rc = radix_sort(depth_sort, s, a->debug);
+        if (rc != OGS_OK) return rc;
         // offsets[r] = exclusive scan of tiles_touched in depth order; total = num_rendered
         rc = exclusive_scan_u32(gt.tiles_touched, gt.order[0], gt.offsets, a->P, gt.num_rendered, gt.sort_tmp, s, a->debug, gt.visible());
         if (rc != OGS_OK) return rc;
@@ -434,30 +424,18 @@ static int render_impl(const OgsRasterFwdArgs* a, int64_t D, bool deferred, hipS
             rc = launch_duplicate(*a, gs, gt, bt.tile_keys[0], vbuf[0], (uint32_t)D, cull, !per_tile, s,
                                   zero_in_dup ? is.ranges : nullptr, zero_in_dup ? (int)tiles : 0);
             if (rc != OGS_OK) return rc;
-            const bool sweep = radix_onesweep_enabled(D);
-            int shifts[4], nbits[4];
+            RadixSort tile_sort = {{bt.tile_keys[0], bt.tile_keys[1]}, {vbuf[0], vbuf[1]}, D, n_dev, passes, {}, {}, cull, bt.kept, bt.sort_tmp};
             for (int p = 0; p < passes; ++p) {
-                shifts[p] = p * per;
-                nbits[p] = (p == passes - 1) ? (bits == 0 ? 1 : bits - shifts[p]) : per;
+                tile_sort.shift[p] = p * per;
+                tile_sort.bits[p] = (p == passes - 1) ? (bits == 0 ? 1 : bits - tile_sort.shift[p]) : per;
             }
             if (passes == 2 && (bits & 1)) {
                 // odd digit total: the SMALLER digit goes first -- the first pass ranks every pair, the second only those that survive
                 // the drop (13 bits: 6 + 7 instead of 7 + 6, a few us on the scatters)
-                nbits[0] = bits / 2; shifts[1] = nbits[0]; nbits[1] = bits - nbits[0];
+                tile_sort.bits[0] = bits / 2; tile_sort.shift[1] = tile_sort.bits[0]; tile_sort.bits[1] = bits - tile_sort.bits[0];
             }
-            if (sweep) {
-                rc = radix_sort_begin(bt.tile_keys[0], D, n_dev, passes, shifts, nbits, bt.sort_tmp, s, a->debug, cull);
-                if (rc != OGS_OK) return rc;
-            }
-            for (int p = 0; p < passes; ++p) {
-                const int in = p & 1, out = in ^ 1;
-                const bool drop = cull && p == 0;
-                // launches stay sized for D (the host does not know the kept count); workgroups past it find nothing to do
-                const uint32_t* n_pass = (cull && p > 0) ? bt.kept : n_dev;
-                rc = sweep ? radix_sort_pass(p, passes, bt.tile_keys[in], vbuf[in], bt.tile_keys[out], vbuf[out], D, shifts[p], nbits[p], bt.sort_tmp, s, a->debug, n_pass, drop, drop ? bt.kept : nullptr)
-                           : radix_pass(bt.tile_keys[in], vbuf[in], bt.tile_keys[out], vbuf[out], D, shifts[p], nbits[p], bt.sort_tmp, s, a->debug, n_pass, drop, drop ? bt.kept : nullptr);
-                if (rc != OGS_OK) return rc;
-            }
+            rc = radix_sort(tile_sort, s, a->debug);
+            if (rc != OGS_OK) return rc;
             rc = launch_tile_ranges(bt.tile_keys[passes & 1], D, is.ranges, tiles, s, a->debug, cull ? bt.kept : n_dev, zero_in_dup);
             if (rc != OGS_OK) return rc;
         }
@@ -751,38 +729,27 @@ int ogs_selftest_radix_sort(uint32_t* keys0, uint32_t* vals0, uint32_t* keys1, u
         set_error("selftest_radix_sort: bad arguments"); return OGS_ERR_INVALID_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    uint32_t* k[2] = {keys0, keys1};
-    uint32_t* v[2] = {vals0, vals1};
     const int passes = (key_bits + 7) / 8, per = (key_bits + passes - 1) / passes;
-    int shifts[4], nbits[4];
-    for (int p = 0; p < passes; ++p) { shifts[p] = p * per; nbits[p] = p == passes - 1 ? key_bits - shifts[p] : per; }
     // variant bit 0: one launch per pass; bit 1: drop mode -- keys equal to 0xFFFFFFFF leave in the first pass (the tile sort of the
     // default binning mode); the number of keys left is returned in bits 1.. of *result_buffer
     // variant bit 2: the look-back waits of the one-launch passes get a bound of ZERO polls -- fault injection for the
     // sticky status word: the call must come back with OGS_ERR_DEVICE (and a wrong permutation)
-    const bool sweep = (variant & 1) != 0, drop = (variant & 2) != 0;
-    const int spin_limit = (variant & 4) ? 0 : -1;
+    const bool drop = (variant & 2) != 0;
+    RadixSort sort = {{keys0, keys1}, {vals0, vals1}, n, n_dev, passes, {}, {}, drop, nullptr, tmp,
+                      (variant & 1) ? RadixImpl::OneLaunch : RadixImpl::ThreeLaunch, items, (variant & 4) ? 0 : -1};
+    for (int p = 0; p < passes; ++p) { sort.shift[p] = p * per; sort.bits[p] = p == passes - 1 ? key_bits - sort.shift[p] : per; }
     (void)take_async_status();       // the hook reports what THIS sort does
-    uint32_t* kept = nullptr;
     if (drop) {
-        OGS_HIP_CHECK(hipMalloc(&kept, sizeof(uint32_t)));
+        OGS_HIP_CHECK(hipMalloc(&sort.kept, sizeof(uint32_t)));
         // poisoned, as the render phase's scratch is (torch.empty): every path of the first pass must write it
-        OGS_HIP_CHECK(hipMemsetAsync(kept, 0xA5, sizeof(uint32_t), s));
+        OGS_HIP_CHECK(hipMemsetAsync(sort.kept, 0xA5, sizeof(uint32_t), s));
     }
-    int rc = OGS_OK;
-    if (sweep) rc = radix_sort_begin(k[0], n, n_dev, passes, shifts, nbits, tmp, s, 0, drop, items);
-    for (int p = 0; p < passes && rc == OGS_OK; ++p) {
-        const int in = p & 1, out = in ^ 1;
-        const bool d0 = drop && p == 0;
-        const uint32_t* n_pass = (drop && p > 0) ? kept : n_dev;
-        rc = sweep ? radix_sort_pass(p, passes, k[in], v[in], k[out], v[out], n, shifts[p], nbits[p], tmp, s, 0, n_pass, d0, d0 ? kept : nullptr, items, spin_limit)
-                   : radix_pass(k[in], v[in], k[out], v[out], n, shifts[p], nbits[p], tmp, s, 0, n_pass, d0, d0 ? kept : nullptr);
-    }
+    int rc = radix_sort(sort, s, 0);
     uint32_t kept_host = 0;
     if (drop) {
-        if (rc == OGS_OK && hipMemcpyAsync(&kept_host, kept, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess) rc = OGS_ERR_HIP;
+        if (rc == OGS_OK && hipMemcpyAsync(&kept_host, sort.kept, sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess) rc = OGS_ERR_HIP;
         (void)hipStreamSynchronize(s);
-        (void)hipFree(kept);
+        (void)hipFree(sort.kept);
     } else {
         (void)hipStreamSynchronize(s);
     }

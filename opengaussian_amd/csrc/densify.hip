@@ -6,7 +6,7 @@
 // state per densify_and_prune (scene/gaussian_model.py:357-510).  Here:
 //   densify_flags_kernel   one pass over the N rows: decides per row whether it survives, is cloned, is split,
 //                          and how many of its copies survive the final prune (reference semantics, see capi below)
-//   (three exclusive scans, binning.hip)
+//   (three exclusive scans, radix_sort.hip)
 //   densify_map_kernel     writes the output row map  src_row[r], kind[r]  in the reference's final order
 //                          [surviving old rows | clones | first split children | second split children]
 //   rows_gather_kernel     ONE launch moves every tensor (<= 32 descriptors): dst[r] = src[src_row[r]], moments of

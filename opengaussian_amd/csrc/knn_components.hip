@@ -8,7 +8,7 @@
 //            single atomic is issued.
 //   hook     one thread per slot: find both roots with path halving, CAS the larger root under the smaller.
 //   flatten  comp[i] = the root of i (-1: inactive), flag[i] = (comp[i] == i).
-//   scan     dense = exclusive scan of flag, count = its total (exclusive_scan_u32, binning.hip).
+//   scan     dense = exclusive scan of flag, count = its total (exclusive_scan_u32, radix_sort.hip).
 //   number   comp[i] = dense[root].
 //   sizes    the member lists of the components are the reverse lists of comp seen as an [n, 1] table (ogs_knn_transpose: a
 //            stable radix sort, the rows of a component ascending); sizes[c] = the length of list c, first[c] = its first

@@ -4,7 +4,7 @@
 // sized from host-known bounds and every count that depends on the data stays in device memory.
 //
 // ogs_knn_transpose: key = idx (a value outside [0, R) becomes kDropKey), value = the flat slot number e = i * K + k; the
-//   three-launch stable radix passes of binning.hip, ceil(bits(R - 1) / 8) of them, the first one dropping the invalid slots.
+//   three-launch stable radix passes of radix_sort.hip, ceil(bits(R - 1) / 8) of them, the first one dropping the invalid slots.
 //   A stable sort of ascending values by key leaves every row's slots ascending, so the result is unique.  begin[r] is the
 //   lower bound of r in the sorted keys (a binary search per row: a row without an incoming edge gets begin[r] == begin[r + 1]
 //   with no fill loop whose length depends on the data).
@@ -474,17 +474,18 @@ int ogs_knn_transpose(int64_t n, int32_t K, int64_t R, const int32_t* idx, int32
     int key_bits = 1;
     while (key_bits < 31 && ((int64_t)1 << key_bits) < R) ++key_bits;        // keys are 0 .. R - 1
     const int npass = (key_bits + 7) / 8;
-    uint32_t* vbuf[2] = {t.vals, reinterpret_cast<uint32_t*>(slots)};
-    const int v0 = (npass & 1) ? 0 : 1;                 // the last pass writes into `slots`
-    OGS_LAUNCH(graph_keys_kernel, dim3((unsigned)blocks_for(E)), dim3(kBlock), 0, s, E, R, idx, t.keys[0], vbuf[v0]);
-    OGS_LAUNCH_CHECK(0, s);
+    // the invalid slots are dropped and t.kept is left holding the count; three-launch passes: nothing waits on another workgroup
+    RadixSort sort = {{t.keys[0], t.keys[1]}, {}, E, nullptr, npass, {}, {}, true, t.kept, t.sort_tmp, RadixImpl::ThreeLaunch};
+    sort.vals[npass & 1] = reinterpret_cast<uint32_t*>(slots);       // the last pass writes into `slots`
+    sort.vals[(npass & 1) ^ 1] = t.vals;
     for (int pass = 0; pass < npass; ++pass) {
-        const int bits = min(8, key_bits - 8 * pass);
-        // the first pass drops the invalid slots and leaves the count; the later ones read it from there
-        const int rc = radix_pass(t.keys[pass & 1], vbuf[(v0 + pass) & 1], t.keys[(pass + 1) & 1], vbuf[(v0 + pass + 1) & 1], E,
-                                  8 * pass, bits, t.sort_tmp, s, 0, pass ? t.kept : nullptr, pass == 0, pass == 0 ? t.kept : nullptr);
-        if (rc != OGS_OK) return rc;
+        sort.shift[pass] = 8 * pass;
+        sort.bits[pass] = min(8, key_bits - 8 * pass);
     }
+    OGS_LAUNCH(graph_keys_kernel, dim3((unsigned)blocks_for(E)), dim3(kBlock), 0, s, E, R, idx, t.keys[0], sort.vals[0]);
+    OGS_LAUNCH_CHECK(0, s);
+    const int rc = radix_sort(sort, s, 0);
+    if (rc != OGS_OK) return rc;
     OGS_LAUNCH(graph_begin_kernel, dim3((unsigned)blocks_for(R + 1)), dim3(kBlock), 0, s, R, E, (const uint32_t*)t.keys[npass & 1],
                (const uint32_t*)t.kept, begin);
     OGS_LAUNCH_CHECK(0, s);

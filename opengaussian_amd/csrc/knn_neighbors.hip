@@ -4,7 +4,7 @@
 // over sorted boxes begins with (knn_boxes.h describes the sorted set and the walk over it):
 //   1. bounding box of the cloud (two stages: per-workgroup partials, folded again by every workgroup of the key kernel),
 //   2. a 30-bit Morton key per point (10 bits per axis, every cell clamped to [0, 1023] whatever the coordinate is),
-//   3. (key, id) sorted by four stable radix passes (binning.hip; the three-launch passes: nothing waits on another workgroup),
+//   3. (key, id) sorted by four stable radix passes (radix_sort.hip; the three-launch passes: nothing waits on another workgroup),
 //   4. the coordinates gathered into sorted order, coordinate-wise, and the axis-aligned bounds of every box.
 // The search itself is knn_search_kernel (knn_search.hip), here with the set against itself: a run of queries IS a box, and its walk
 // starts there.
@@ -148,12 +148,11 @@ int knn_sort_into_boxes(int n, const float* pts, const KnnSortScratch& t, const 
     OGS_LAUNCH(knn_keys_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n, pts, t.partial, nparts,
                t.keys[0], t.vals[0], out.frame);
     OGS_LAUNCH_CHECK(0, s);
-    const int shifts[4] = {0, 8, 16, 24}, nbits[4] = {8, 8, 8, 6};  // 30 key bits; an even number of passes ends in [0]
-    for (int pass = 0; pass < 4; ++pass) {
-        const int in = pass & 1, o = in ^ 1;
-        const int rc = radix_pass(t.keys[in], t.vals[in], t.keys[o], t.vals[o], n, shifts[pass], nbits[pass], t.sort_tmp, s, 0);
-        if (rc != OGS_OK) return rc;
-    }
+    // 30 key bits; an even number of passes ends in [0]
+    const RadixSort sort = {{t.keys[0], t.keys[1]}, {t.vals[0], t.vals[1]}, n, nullptr, 4, {0, 8, 16, 24}, {8, 8, 8, 6},
+                            false, nullptr, t.sort_tmp, RadixImpl::ThreeLaunch};
+    const int rc = radix_sort(sort, s, 0);
+    if (rc != OGS_OK) return rc;
     const int wpb = kBlock / kWave;
     OGS_LAUNCH(knn_gather_kernel, dim3((unsigned)((nbox + wpb - 1) / wpb)), dim3(kBlock), 0, s, n, nbox, pts, t.vals[0], t.keys[0],
                out.sx, out.sy, out.sz, out.sid, out.box, out.first_key);

@@ -45,7 +45,7 @@ void set_error(const char* fmt, ...);
 // in a healthy run, so it costs nothing there -- and carries on without hanging or writing out of bounds.  The host reads
 // (and clears) the word wherever it already synchronises with the stream: after the num_rendered read-back of a forward,
 // at the entry of the next forward / backward, in the self-test hooks; ogs_check_async_status() turns it into
-// OGS_ERR_DEVICE.  Producers: the bounded look-back spin of radix_onesweep_kernel (binning.hip), and the scatter of the query
+// OGS_ERR_DEVICE.  Producers: the bounded look-back spin of radix_onesweep_kernel (radix_sort.hip), and the scatter of the query
 // split (query.hip) when a row's position lies at or beyond the capacity it was given, and the walks and retry loops of the
 // union-find (knn_components.hip) when one passes the bound that n sets for it.
 constexpr uint32_t kAsyncRadixSpin = 1u;
@@ -252,19 +252,9 @@ const uint32_t* launch_tile_order(const ImageState& is, int64_t vtiles, int P, h
 const uint32_t* tile_order_of(const ImageState& is, int64_t vtiles, int P);      // what the forward of this pass used
 int launch_export_n_contrib(const OgsRasterFwdArgs& a, const ImageState& is, uint32_t* out, hipStream_t s);
 
-// radix sort / scan (binning.hip) ---------------------------------------------------------------
-// keys per thread of a radix pass: 8 (2048-key workgroups) for long lists, 4 for short ones so that a P-sized
-// sort still spreads over several workgroups per CU
-// (round 4: 8 instead of 16 for the long lists -- 20 KB instead of 37 KB of LDS per workgroup, twice the workgroups in flight:
-// radix_scatter at the D size 0.074 -> 0.061 ms per step, the histogram / row-scan side 0.007 slower, A-B on one box)
-constexpr int kSortItemsLarge = 8;
-inline int sort_items_for(int64_t n) { return n <= (int64_t)(3 << 20) ? 4 : kSortItemsLarge; }
-inline int sort_blocks_for(int64_t n) {
-    const int64_t tile = (int64_t)kBlock * sort_items_for(n);
-    return (int)((n + tile - 1) / tile);
-}
+// radix sort / scan (radix_sort.hip) ------------------------------------------------------------
 size_t scan_tmp_bytes(int64_t n);
-size_t sort_tmp_bytes(int64_t n);                      // histogram + scan scratch for one pass
+size_t sort_tmp_bytes(int64_t n);                      // scratch of a whole sort of n keys, either implementation
 
 // exclusive prefix sum of n uint32 (in may equal out); if total != nullptr the grand total is
 // written there (device).  `gather` (optional) makes element i = in[gather[i]].
@@ -272,26 +262,28 @@ size_t sort_tmp_bytes(int64_t n);                      // histogram + scan scrat
 // count read as zeros and their outputs are not written.
 int exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32_t* out, int64_t n,
                        uint32_t* total, void* tmp, hipStream_t stream, int debug, const uint32_t* n_dev = nullptr);
-// One-launch-per-pass variant (decoupled look-back): radix_sort_begin zeroes the scratch and histograms every digit of
-// the `npass` planned passes in one read of the keys; radix_sort_pass is pass `pass` of that plan (ONE launch).
-// radix_onesweep_enabled(n): false for n >= 2^30 or OGS_RADIX=legacy (then use radix_pass, three launches per pass).
-// drop = true: keys equal to kDropKey are not part of the sort -- they are left out of the histograms and of the output of the
-// pass, which comes out COMPACTED; kept_out (device, optional) receives the number of keys the pass wrote, the element count of
-// every later pass.  (The tile sort drops the (Gaussian, tile) pairs that cannot reach a pixel of their tile: duplicate_kernel.)
+// Stable LSD radix sort of n (key, value) pairs in npass digit passes, pass p on bits [shift[p], shift[p] + bits[p]) (1..4
+// passes of 1..8 bits).  n is the element count, or -- when n_dev != nullptr -- the CAPACITY the launches are sized for while
+// the kernels read the true count (<= capacity after clamping) from device memory.
+// drop: keys equal to kDropKey are not part of the sort -- they are left out of the histograms and of the output of pass 0,
+// which comes out COMPACTED and stores the number of keys it wrote to *kept (device, required), the element count of every
+// later pass.  (The tile sort drops the (Gaussian, tile) pairs that cannot reach a pixel of their tile: duplicate_kernel.)
+// impl: ThreeLaunch = histogram table, row scan and scatter per pass, nothing waits on another workgroup; OneLaunch = one
+// launch per pass with decoupled look-back, fewer than 2^30 keys; BySize = OneLaunch up to 256 Ki keys (OGS_RADIX=legacy /
+// sweep: never / wherever it can run).
 constexpr uint32_t kDropKey = 0xFFFFFFFFu;
-bool radix_onesweep_enabled(int64_t n);
-// items (0: by size; 4 / 16: the self-test hook forces a tile size) must be the same in radix_sort_begin and every radix_sort_pass
-// of a sort; spin_limit < 0: the default bound of a look-back wait (the self-test hook passes 0 to trip it).
-int radix_sort_begin(const uint32_t* keys, int64_t n, const uint32_t* n_dev, int npass, const int* shifts, const int* bits,
-                     void* tmp, hipStream_t stream, int debug, bool drop = false, int items = 0);
-int radix_sort_pass(int pass, int npass, const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out,
-                    uint32_t* vals_out, int64_t n, int shift, int bits, void* tmp, hipStream_t stream, int debug,
-                    const uint32_t* n_dev = nullptr, bool drop = false, uint32_t* kept_out = nullptr, int items = 0,
-                    int spin_limit = -1);
-// One stable LSD pass on bits [shift, shift+bits) of keys_in (bits <= 8): histogram table, row scan, scatter.
-int radix_pass(const uint32_t* keys_in, const uint32_t* vals_in, uint32_t* keys_out, uint32_t* vals_out,
-               int64_t n, int shift, int bits, void* tmp, hipStream_t stream, int debug,
-               const uint32_t* n_dev = nullptr, bool drop = false, uint32_t* kept_out = nullptr);
+enum class RadixImpl { BySize, ThreeLaunch, OneLaunch };
+struct RadixSort {
+    uint32_t* keys[2]; uint32_t* vals[2];   // pass p reads [p & 1], writes [(p + 1) & 1]; result in [npass & 1]
+    int64_t n; const uint32_t* n_dev;
+    int npass; int shift[4]; int bits[4];
+    bool drop; uint32_t* kept;
+    void* tmp;                               // sort_tmp_bytes(n)
+    RadixImpl impl = RadixImpl::BySize;
+    int items = 0, spin_limit = -1;          // self-test hook only: a forced tile size of the one-launch passes (4 / 16), and the
+                                             // bound of a look-back wait (0 trips it)
+};
+int radix_sort(const RadixSort&, hipStream_t, int debug);
 
 // words of one run of GeomTmp::block_sum holding nb sums: padded, so that block_offsets_kernel loads both runs 16 bytes at a time
 constexpr int kBlockSumPad = 8;

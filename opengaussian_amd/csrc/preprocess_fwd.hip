@@ -459,7 +459,7 @@ __global__ __launch_bounds__(kBlock) void duplicate_kernel(int P_cap, const uint
                                                            const int32_t* __restrict__ group_ids, bool drop_unreachable,
                                                            uint2* __restrict__ zero_ranges, int n_zero) {
     // drop_unreachable: a pair that cannot reach a pixel of its tile gets the key kDropKey, which the counting pass by tile, or
-    // the first pass of the radix tile sort, leaves out (binning.hip) -- the sorted list then holds the reachable pairs only.  Otherwise the pair keeps its tile
+    // the first pass of the radix tile sort, leaves out (binning.hip, radix_sort.hip) -- the sorted list then holds the reachable pairs only.  Otherwise the pair keeps its tile
     // key and only its reach flag (bit 31 of the value) tells pack to skip it: the reference's full list (args.full_binning).
     // group_ids != nullptr (grouped pass): the key is the VIRTUAL tile group * tiles + tile
     // capacity: size of tile_keys / vals.  In the deferred render phase it is a cached estimate and the true
