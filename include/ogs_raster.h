@@ -437,6 +437,18 @@ size_t ogs_selftest_radix_tmp_bytes(int64_t n);
 int ogs_selftest_radix_sort(uint32_t* keys0, uint32_t* vals0, uint32_t* keys1, uint32_t* vals1, int64_t n, int32_t key_bits,
                             int32_t variant, int32_t items, const uint32_t* n_dev, void* tmp, int32_t* result_buffer,
                             void* stream);
+/* Test hook: the exclusive prefix sum every offset of the library comes out of (binning, densify, the kNN graph and index,
+ * connected components), on its own.  out[i] = sum of the elements before i, modulo 2^32, for i < n; element i is in[i], or
+ * in[gather[i]] when gather != NULL.  total (device, optional) receives the sum of all elements.  n_dev (device, optional): the
+ * element count lives in device memory and n is the capacity the launches are sized for; the count is min(*n_dev, n), elements
+ * past it count as zeros and their outputs are NOT written.  n <= 2048 is one launch, n <= 33 554 432 two, above that four
+ * (five with total).  in may equal out, except with gather, and except with total above 33 554 432 elements: both return
+ * OGS_ERR_INVALID_ARG before anything is launched or written, whatever n is (the gather refusal also for n <= 0).
+ * Otherwise n <= 0: *total = 0, nothing else.
+ * tmp: ogs_selftest_scan_tmp_bytes(n) bytes of scratch.  Asynchronous, no read-back. */
+size_t ogs_selftest_scan_tmp_bytes(int64_t n);
+int ogs_selftest_scan_u32(const uint32_t* in, const uint32_t* gather, uint32_t* out, int64_t n, uint32_t* total,
+                          const uint32_t* n_dev, void* tmp, void* stream);
 
 #ifdef __cplusplus
 }

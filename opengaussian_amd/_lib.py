@@ -142,6 +142,8 @@ SIGNATURES = {
     "ogs_selftest_tile_order": (C.c_int, [_vp, C.c_int64, _vp, _vp]),
     "ogs_selftest_radix_tmp_bytes": (C.c_size_t, [C.c_int64]),
     "ogs_selftest_radix_sort": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "ogs_selftest_scan_tmp_bytes": (C.c_size_t, [C.c_int64]),
+    "ogs_selftest_scan_u32": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     "ogs_raster_forward_geometry_raw": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsRawModel), _vp,
                                                   C.POINTER(C.c_int64)]),
     "ogs_raster_forward_tiny_raw": (C.c_int, [C.POINTER(OgsRasterFwdArgs), C.POINTER(OgsRawModel), _vp]),

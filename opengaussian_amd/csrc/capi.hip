@@ -758,6 +758,15 @@ int ogs_selftest_radix_sort(uint32_t* keys0, uint32_t* vals0, uint32_t* keys1, u
     return check_async_status("selftest_radix_sort");
 }
 
+size_t ogs_selftest_scan_tmp_bytes(int64_t n) { return scan_tmp_bytes(n > 0 ? n : 1); }
+
+/* test hook: exclusive_scan_u32 as the library's callers reach it -- no read-back, no synchronisation */
+int ogs_selftest_scan_u32(const uint32_t* in, const uint32_t* gather, uint32_t* out, int64_t n, uint32_t* total,
+                          const uint32_t* n_dev, void* tmp, void* stream_) {
+    if (n > 0 && (!in || !out || !tmp)) { set_error("selftest_scan_u32: NULL pointer"); return OGS_ERR_INVALID_ARG; }
+    return exclusive_scan_u32(in, gather, out, n, total, tmp, static_cast<hipStream_t>(stream_), 0, n_dev);
+}
+
 int ogs_raster_export_binning(const OgsRasterFwdArgs* a, int64_t D, uint64_t* keys_out, uint32_t* ranges_out,
                               uint32_t* n_contrib_out, void* stream_) {
     if (!a) { set_error("args == NULL"); return OGS_ERR_INVALID_ARG; }

@@ -256,8 +256,11 @@ int launch_export_n_contrib(const OgsRasterFwdArgs& a, const ImageState& is, uin
 size_t scan_tmp_bytes(int64_t n);
 size_t sort_tmp_bytes(int64_t n);                      // scratch of a whole sort of n keys, either implementation
 
-// exclusive prefix sum of n uint32 (in may equal out); if total != nullptr the grand total is
-// written there (device).  `gather` (optional) makes element i = in[gather[i]].
+// exclusive prefix sum of n uint32; if total != nullptr the grand total is written there (device).  `gather` (optional) makes
+// element i = in[gather[i]].  in may equal out, with two limits, both refused with OGS_ERR_INVALID_ARG before anything is
+// launched: not together with `gather` (element i would read a word another thread has already overwritten), and not together
+// with `total` above 16384 x 2048 elements (the multi-level route takes the total from the last input, which is gone by then).
+// tmp: scan_tmp_bytes(n) bytes; sort_tmp_bytes(n) >= scan_tmp_bytes(n), so a caller may lend it a sort's scratch.
 // n_dev (optional): the element count lives in device memory, n is the capacity the launches are sized for; elements past the
 // count read as zeros and their outputs are not written.
 int exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32_t* out, int64_t n,

@@ -524,11 +524,22 @@ size_t sort_tmp_bytes(int64_t n) {
 
 int exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32_t* out, int64_t n, uint32_t* total,
                        void* tmp, hipStream_t stream, int debug, const uint32_t* n_dev) {
+    // both refusals come before the first launch: a refused call leaves the caller's data as it was
+    if (gather != nullptr && in == out) {
+        // element i reads in[gather[i]], which another thread may already have overwritten with its prefix
+        set_error("exclusive_scan_u32: gather with in-place scan unsupported");
+        return OGS_ERR_INVALID_ARG;
+    }
     if (n <= 0) {
         if (total) OGS_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(uint32_t), stream));
         return OGS_OK;
     }
     const int nb = scan_blocks(n);
+    if (nb > kFlatScanBlocks && total != nullptr && in == out) {
+        // scan_total_kernel adds the last input to the last prefix, and the input is gone by then
+        set_error("exclusive_scan_u32: total with in-place scan unsupported");
+        return OGS_ERR_INVALID_ARG;
+    }
     if (nb == 1) {
         OGS_LAUNCH(scan_apply_kernel<false>, dim3(1), dim3(kBlock), 0, stream, in, gather, out, n,
                            (const uint32_t*)nullptr, total, n_dev);
@@ -552,7 +563,6 @@ int exclusive_scan_u32(const uint32_t* in, const uint32_t* gather, uint32_t* out
                        (const uint32_t*)partials, (uint32_t*)nullptr, n_dev);
     OGS_LAUNCH_CHECK(debug, stream);
     if (total) {
-        if (in == out) { set_error("exclusive_scan_u32: total with in-place scan unsupported"); return OGS_ERR_INVALID_ARG; }
         OGS_LAUNCH(scan_total_kernel, dim3(1), dim3(64), 0, stream, in, gather, (const uint32_t*)out, n, total, n_dev);
         OGS_LAUNCH_CHECK(debug, stream);
     }

@@ -55,6 +55,7 @@ BLOCK_CONFUSION = "opengaussian_amd/query.py, confusion_table: 'one min / max re
 BLOCK_SPLIT = "opengaussian_amd/query.py, multi_split: 'One read-back of the counts per split (the size of ``rows``).'"
 BLOCK_REFINE = "opengaussian_amd/sam_refine.py, refine_sam_masks: 'stage 1 on the host: label classes, not pixels'"
 BLOCK_RADIX = "include/ogs_raster.h, ogs_selftest_radix_sort: '*result_buffer (host) receives 0 or 1'"
+ASYNC_SCAN = "include/ogs_raster.h, ogs_selftest_scan_u32: 'Asynchronous, no read-back.'"
 BLOCK_KEPT_ADMIT = "opengaussian_amd/rasterizer.py, KeptPasses.admit: 'one 8-byte read-back per admitted view'"
 
 # Launchers no case names.  Only profiling and debug hooks may stand here.
@@ -1376,6 +1377,28 @@ def _c_radix(variant):
     return build
 
 
+def _c_scan(dev):
+    """the scan self-test on its two-launch route (reduce, apply), with everything optional: a gather, a device-side count
+    below the capacity and the total.  The outputs past the count are not written: they keep the harness's dirt in every run."""
+    from opengaussian_amd import _lib
+    L = _lib.lib()
+    n, m = 5000, 2503
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int32, device=dev)
+    tmp = _u8(L.ogs_selftest_scan_tmp_bytes(n), dev)
+
+    def inputs(seed):
+        g = _gen(seed, 34)
+        return {"in": torch.randint(0, 301, (m,), generator=g).to(torch.int32),
+                "gather": torch.randint(0, m, (n,), generator=g).to(torch.int32),
+                "n_dev": torch.randint(2500, n + 1, (1,), generator=g).to(torch.int32)}
+
+    def run(b, s):
+        _call("ogs_selftest_scan_u32", _p(b["in"]), _p(b["gather"]), _p(out), n, _p(total), _p(b["n_dev"]), _p(tmp), _st(s))
+        return [out, total]
+    return Prepared(inputs, run, out=[out, total], tmp=[tmp])
+
+
 # ---- the table -------------------------------------------------------------------------------------------------------------------
 GEOM, RENDER, BACKWARD = "ogs_raster_forward_geometry", "ogs_raster_forward_render", "ogs_raster_backward"
 DEFER = ("ogs_raster_read_num_rendered_async", "ogs_raster_forward_render_deferred")
@@ -1496,3 +1519,15 @@ CASES = [
 
 BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
+
+# Cases of self-test hooks.  CASES is what profiles/stream_contract.json holds, name by name; these are what
+# profiles/stream_contract_hooks.json holds, name by name (`python -m tests.stream_harness --measure` writes both), and the one
+# delay of the tests is held against the host times of both files.  Everything that walks the table walks these too:
+# tests/test_80_stream_contract_gpu.py runs them behind the delay like any case, tests/test_stream_table_host.py counts them
+# and demands their profile entries.  A hook only: every entry point of the product belongs in CASES.
+HOOK_CASES = [
+    Case("c_scan_gather_count_total", _c_scan, ("ogs_selftest_scan_u32",), "c", sentence=ASYNC_SCAN),
+]
+ALL_CASES = CASES + HOOK_CASES
+ALL_BY_NAME = {c.name: c for c in ALL_CASES}
+assert len(ALL_BY_NAME) == len(ALL_CASES)

@@ -21,7 +21,11 @@ tests/test_stream_table_host.py (CPU: every `void* stream` prototype of include/
 
 `python -m tests.stream_harness --measure` (on the GPU) times every tabled call on the host after one warm-up call and writes
 profiles/stream_contract.json: the host times and the delay derived from them (at least 10 x the largest, at least 50 ms).
-`python -m tests.stream_harness --table` prints the table: every case with its blocks_host flag and the sentence it is taken from."""
+`python -m tests.stream_harness --table` prints the table: every case with its blocks_host flag and the sentence it is taken from.
+
+The cases of self-test hooks (HOOK_CASES of the table module) run through the same tests as the table's own.  Their host times
+are profiles/stream_contract_hooks.json, which `--measure` writes as well (and `--measure-hooks` alone); the one delay, that of
+profiles/stream_contract.json, must be at least 10 x the largest host time of EITHER file."""
 from __future__ import annotations
 
 import contextlib
@@ -35,6 +39,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROFILE = os.path.join(ROOT, "profiles", "stream_contract.json")
+HOOK_PROFILE = os.path.join(ROOT, "profiles", "stream_contract_hooks.json")
 REAL_SEED, DECOY_SEED = 1234, 4321
 MIN_DELAY_MS = 50.0
 DELAY_FACTOR = 10.0
@@ -112,6 +117,16 @@ _CYCLES_PER_MS = None
 def load_profile() -> dict:
     with open(PROFILE) as f:
         return json.load(f)
+
+
+def load_hook_profile() -> dict:
+    with open(HOOK_PROFILE) as f:
+        return json.load(f)
+
+
+def all_host_ms() -> Dict[str, float]:
+    """the host times of both profiles: what the one delay is held against"""
+    return {**load_profile()["host_ms"], **load_hook_profile()["host_ms"]}
 
 
 def required_delay_ms(host_ms: Dict[str, float]) -> float:
@@ -398,6 +413,21 @@ def measure(path=PROFILE):
     return write_profile({c.name: round(host_time_ms(c, dev), 3) for c in table.CASES}, path)
 
 
+def measure_hooks(path=HOOK_PROFILE):
+    """the host times of the hook cases, taken as measure() takes the table's; the delay stays that of profiles/stream_contract.json"""
+    from tests import stream_contract_cases as table
+    dev = torch.device("cuda:0")
+    doc = {"what": "host wall time (ms) of every hook case (HOOK_CASES) on the default stream after one warm-up call; the delay of "
+                   "profiles/stream_contract.json covers these too.  Written by `python -m tests.stream_harness --measure-hooks`",
+           "device": torch.cuda.get_device_name(0),
+           "host_ms": {c.name: round(host_time_ms(c, dev), 3) for c in table.HOOK_CASES}}
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    return doc
+
+
 def write_profile(host: Dict[str, float], path=PROFILE):
     want = required_delay_ms(host)
     delay_ms = float(50 * -(-want // 50))                        # rounded up to 50 ms
@@ -418,7 +448,7 @@ def print_table():
     """the table as markdown: case, level, blocks_host, the sentence the flag is taken from, the entry points it reaches"""
     from tests import stream_contract_cases as table
     print("| case | level | blocks_host | documented by | reaches |\n|---|---|---|---|---|")
-    for c in table.CASES:
+    for c in table.ALL_CASES:
         print(f"| {c.name} | {c.level} | {c.blocks_host} | {c.sentence or '(neither documented: result only)'} | "
               f"{', '.join(c.reaches)} |")
     print("\nexempt:")
@@ -434,3 +464,7 @@ if __name__ == "__main__":
         out = sys.argv[sys.argv.index("--measure") + 1] if len(sys.argv) > sys.argv.index("--measure") + 1 else PROFILE
         d = measure(out)
         print(json.dumps({k: d[k] for k in ("largest_host_ms", "required_delay_ms", "delay_ms", "measured_delay_ms")}))
+        print(json.dumps(measure_hooks(HOOK_PROFILE if out == PROFILE else out[:-5] + "_hooks.json")["host_ms"]))
+    if "--measure-hooks" in sys.argv:
+        i = sys.argv.index("--measure-hooks")
+        print(json.dumps(measure_hooks(sys.argv[i + 1] if len(sys.argv) > i + 1 else HOOK_PROFILE)["host_ms"]))

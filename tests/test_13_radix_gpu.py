@@ -45,7 +45,7 @@ def test_radix_sort_matches_stable_sort_full_keys(gpu_device, n):
     _check(ties.to(gpu_device), 32, gpu_device, f"ties n={n}")
 
 
-@pytest.mark.parametrize("key_bits", [1, 4, 7, 8, 9, 11, 13, 16, 17, 24, 25, 31])
+@pytest.mark.parametrize("key_bits", [1, 4, 7, 8, 9, 11, 13, 16, 17, 24, 25, 30, 31])      # 30: the 8/8/8/6 plan of the kNN box sort
 def test_radix_sort_every_digit_split(gpu_device, key_bits):
     n = 70_001
     g = torch.Generator().manual_seed(key_bits)
@@ -145,3 +145,91 @@ def test_look_back_bound_of_zero_polls_raises(gpu_device):
         _sort(keys, 32, 1 | 4, gpu_device, items=4)
     assert lib.ogs_check_async_status() == 0
     _check(keys, 32, gpu_device, "after the injected fault")
+
+
+# ---- long lists through the three-launch passes ------------------------------------------------------------------------------------
+# 2048 workgroups per histogram row is one trip of radix_rowscan_kernel's carry loop; up to 3 Mi keys a workgroup takes 1024 keys
+# (radix_hist_kernel<4> / radix_scatter_kernel<4>), above that 2048 (<8>)
+LONG = [(2_097_152, 4), (2_097_153, 4), (3_145_728, 4), (3_145_729, 8), (4_194_305, 8)]
+
+
+def _profiled(call):
+    _lib.prof_enable(1)
+    try:
+        result = call()
+        torch.cuda.synchronize()
+        return result, _lib.prof_collect()
+    finally:
+        _lib.prof_enable(0)
+
+
+def _assert_three_launch_kernels(prof, items, passes, what):
+    calls = lambda name: prof.get(name, {}).get("calls", 0)
+    other = 12 - items
+    assert calls(f"radix_hist_kernel<{items}>") == passes and calls(f"radix_scatter_kernel<{items}>") == passes, (what, sorted(prof))
+    assert calls(f"radix_hist_kernel<{other}>") == 0 and calls(f"radix_scatter_kernel<{other}>") == 0, (what, sorted(prof))
+    assert calls("radix_rowscan_kernel") == passes and not any(k.startswith("radix_onesweep") for k in prof), (what, sorted(prof))
+
+
+@pytest.mark.parametrize("n,items", LONG)
+def test_three_launch_sort_of_long_lists(gpu_device, n, items):
+    """13-bit tile ids (two passes) and all-equal keys (one histogram row carries every count) at the sizes around the second
+    trip of the row scan and around the change of the keys per workgroup, which the profiler's launch names pin"""
+    dev = gpu_device
+    g = torch.Generator(device=dev).manual_seed(n)
+    for what, keys in (("tile ids", torch.randint(0, 1 << 13, (n,), generator=g, device=dev).to(torch.int32)),
+                       ("all equal", torch.full((n,), 4321, dtype=torch.int32, device=dev))):
+        (k, v), prof = _profiled(lambda: _sort(keys, 13, 0, dev))
+        _assert_three_launch_kernels(prof, items, 2, f"{what} n={n}")
+        want_k, want_v = torch.sort(keys.to(torch.int64), stable=True)
+        assert torch.equal(k.to(torch.int64), want_k), f"{what} n={n}: keys"
+        assert torch.equal(v.to(torch.int64), want_v), f"{what} n={n}: stable order (ties by index)"
+
+
+@pytest.mark.parametrize("n", [3_145_729, 4_194_305])
+def test_three_launch_drop_sort_of_long_lists(gpu_device, n):
+    """the headline tile sort: 2048-key workgroups, drop mode, about half the (Gaussian, tile) pairs dropped"""
+    dev = gpu_device
+    g = torch.Generator(device=dev).manual_seed(n + 1)
+    keys = torch.randint(0, 1 << 13, (n,), generator=g, device=dev)
+    dropped = torch.rand(n, generator=g, device=dev) < 0.5
+    keys_in = torch.where(dropped, torch.full_like(keys, -1), keys).to(torch.int32)
+    keep_idx = torch.nonzero(~dropped).flatten()
+    want_k, order = torch.sort(keys[keep_idx], stable=True)
+    (k, v, kept), prof = _profiled(lambda: _sort_drop(keys_in, 13, 0, dev))
+    _assert_three_launch_kernels(prof, 8, 2, f"drop n={n}")
+    assert kept == keep_idx.numel(), (kept, keep_idx.numel())
+    assert torch.equal(k.to(torch.int64), want_k), "keys"
+    assert torch.equal(v.to(torch.int64), keep_idx[order]), "stable order"
+
+
+# ---- a count in device memory, nothing dropped: the tile sort of the full-binning deferred render phase --------------------------
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("capacity,count", [(5000, 0), (5000, 1), (5000, 1234), (5000, 5000), (5000, 5010), (300_007, 150_003)])
+def test_device_side_count_without_drop(gpu_device, variant, capacity, count):
+    """The launches are sized for the capacity and the kernels read min(*n_dev, capacity): the first `count` results are the
+    stable sort of the first `count` keys.  Every write of a pass lands below the count, so behind it the buffer pair of the
+    input still holds the input and the other pair its poison; with a count of 0 nothing is written at all."""
+    dev = gpu_device
+    lib = _lib.lib()
+    g = torch.Generator().manual_seed(capacity + count)
+    keys = torch.randint(0, 1 << 13, (capacity,), generator=g, dtype=torch.int32).to(dev)
+    ids = torch.arange(capacity, dtype=torch.int32, device=dev)
+    tmp = torch.empty(int(lib.ogs_selftest_radix_tmp_bytes(capacity)), dtype=torch.uint8, device=dev)
+    k = [keys.clone(), torch.full_like(keys, -1)]
+    v = [ids.clone(), torch.full_like(ids, -1)]
+    n_dev = torch.tensor([count], dtype=torch.int32, device=dev)
+    res = C.c_int32(-1)
+    _lib.check(lib.ogs_selftest_radix_sort(k[0].data_ptr(), v[0].data_ptr(), k[1].data_ptr(), v[1].data_ptr(), capacity, 13, variant,
+                                           0, n_dev.data_ptr(), tmp.data_ptr(), C.byref(res),
+                                           torch.cuda.current_stream().cuda_stream), "radix")
+    torch.cuda.synchronize()
+    assert res.value == 0, "two passes: the result is in the buffer pair of the input"
+    c = min(count, capacity)
+    want_k, want_v = torch.sort(keys[:c].to(torch.int64), stable=True)
+    assert torch.equal(k[0][:c].to(torch.int64), want_k), "keys"
+    assert torch.equal(v[0][:c].to(torch.int64), want_v), "stable order (ties by index)"
+    assert torch.equal(k[0][c:], keys[c:]) and torch.equal(v[0][c:], ids[c:]), "a key or value at or past the count was written"
+    assert bool((k[1][c:] == -1).all()) and bool((v[1][c:] == -1).all()), "the other buffer pair was written at or past the count"
+    if c == 0:
+        assert bool((k[1] == -1).all()) and bool((v[1] == -1).all()), "a count of 0 wrote to the poisoned output buffers"

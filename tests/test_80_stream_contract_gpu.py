@@ -2,7 +2,7 @@
 torch's current stream; here every public entry point, and every C entry point with a memset, a copy or several launches, runs on
 a fresh side stream behind a long delay (tests/stream_harness.py), off the legacy default stream that forgives a launch on the
 wrong stream.  The table is tests/stream_contract_cases.py; the delay and the host times it is derived from are
-profiles/stream_contract.json."""
+profiles/stream_contract.json, with the host times of the self-test hook cases in profiles/stream_contract_hooks.json."""
 import pytest
 import torch
 
@@ -12,15 +12,19 @@ from tests import stream_harness as H
 pytestmark = pytest.mark.gpu
 
 NAMES = [c.name for c in table.CASES]
+HOOK_NAMES = [c.name for c in table.HOOK_CASES]          # self-test hooks: the same run, host times in a profile of their own
 
 
 @pytest.fixture(scope="module")
 def delay_ms(gpu_device):
-    """the delay of the profile, checked against its own rule and against the clock of this session"""
+    """the delay of the profile, checked against its own rule -- over the host times of the table's cases and of the hook cases --
+    and against the clock of this session"""
     prof = H.load_profile()
     assert set(prof["host_ms"]) == set(NAMES), "profiles/stream_contract.json was measured for another table"
-    required = H.required_delay_ms(prof["host_ms"])
-    assert required >= H.MIN_DELAY_MS and required >= H.DELAY_FACTOR * max(prof["host_ms"].values())
+    assert set(H.load_hook_profile()["host_ms"]) == set(HOOK_NAMES), "profiles/stream_contract_hooks.json: other hook cases"
+    host_ms = H.all_host_ms()
+    required = H.required_delay_ms(host_ms)
+    assert required >= H.MIN_DELAY_MS and required >= H.DELAY_FACTOR * max(host_ms.values())
     assert prof["delay_ms"] >= required, (prof["delay_ms"], required)
     measured = H.measured_delay_ms(prof["delay_ms"])
     print("delay", prof["delay_ms"], "ms asked,", round(measured, 1), "ms measured,", required, "ms required")
@@ -29,9 +33,9 @@ def delay_ms(gpu_device):
 
 
 # ---- a, b, c: every entry point behind the delay ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + HOOK_NAMES)
 def test_call_on_a_side_stream_behind_a_delay(gpu_device, delay_ms, name):
-    case = table.BY_NAME[name]
+    case = table.ALL_BY_NAME[name]
     v = H.run_behind_delay(case, gpu_device, delay_ms)
     print(name, "equal", v.equal, "returned before the delay ended", v.returned_before_delay_ended, "host ms", round(v.host_ms, 2),
           v.detail)

@@ -25,9 +25,15 @@ def test_the_header_scan_finds_the_launchers():
 
 def test_every_launcher_is_named_by_a_case_or_exempt():
     protos = H.stream_prototypes()
-    named = {n for c in table.CASES for n in c.reaches}
+    tabled = {n for c in table.CASES for n in c.reaches}
+    named = tabled | {n for c in table.HOOK_CASES for n in c.reaches}
     missing = protos - named - set(table.EXEMPT)
     assert not missing, f"launchers no stream case reaches: {sorted(missing)}"
+    # the hook cases are for self-test hooks alone: an entry point of the product is named by the table itself
+    for n in sorted(named - tabled):
+        assert HOOK.search(n), f"{n} is no hook: its case belongs in CASES"
+    for c in table.HOOK_CASES:
+        assert all(HOOK.search(n) for n in c.reaches) and c.level == "c", c.name
     assert not set(table.EXEMPT) & named, "exempt and named at once"
     assert set(table.EXEMPT) <= protos, "an exemption for something that is no launcher"
 
@@ -42,7 +48,7 @@ def test_exemptions_are_few_reasoned_and_hooks_only():
 def test_every_name_in_the_table_is_bound():
     from opengaussian_amd import _lib
     protos = H.stream_prototypes()
-    for c in table.CASES:
+    for c in table.ALL_CASES:
         assert c.reaches, c.name
         for n in c.reaches:
             assert n in _lib.SIGNATURES, (c.name, n)
@@ -50,9 +56,9 @@ def test_every_name_in_the_table_is_bound():
 
 
 def test_table_entries_are_complete():
-    names = [c.name for c in table.CASES]
+    names = [c.name for c in table.ALL_CASES]
     assert len(set(names)) == len(names)
-    for c in table.CASES:
+    for c in table.ALL_CASES:
         assert c.level in ("py", "c"), c.name
         if c.blocks_host:
             assert c.sentence, f"{c.name}: blocks_host needs the sentence that documents it"
@@ -74,6 +80,12 @@ def test_the_profile_covers_the_table_and_obeys_its_rule():
     assert set(prof["host_ms"]) == {c.name for c in table.CASES}
     assert all(v > 0 for v in prof["host_ms"].values())
     assert prof["delay_ms"] >= H.required_delay_ms(prof["host_ms"]) >= H.MIN_DELAY_MS
+    # the hook cases: a profile entry each, and the one delay covers them as it covers the table's
+    hooks = H.load_hook_profile()
+    assert set(hooks["host_ms"]) == {c.name for c in table.HOOK_CASES}
+    assert all(v > 0 for v in hooks["host_ms"].values())
+    assert set(H.all_host_ms()) == {c.name for c in table.ALL_CASES}
+    assert prof["delay_ms"] >= H.required_delay_ms(H.all_host_ms()) >= H.MIN_DELAY_MS
 
 
 def test_the_gpu_file_skips_nothing():
