@@ -156,6 +156,42 @@ def _require_gpu(t: torch.Tensor, name: str):
         raise RuntimeError(f"{name} must live on the GPU (got {t.device}); the MI355X rasterizer has no CPU path")
 
 
+# ---- the steps every pass of the facade shares (_RasterizeGaussians, _RasterizeModel, _ReblendKept, the statistics passes) ----
+def _pass_bg(rs, Cn: int, dev) -> torch.Tensor:
+    """the settings' background as contiguous fp32 on `dev`, one entry per blended channel"""
+    bg = _f32c(rs.bg.to(dev))
+    if bg is None or bg.numel() != Cn:
+        if bg is not None and bg.numel() == 3 and Cn > 3:
+            # the facade's bg is 3-wide and the reference applies it to EVERY 3-channel pass (RGB, feat[:, :3],
+            # feat[:, 3:6], gaussian_renderer/__init__.py:55-70,129-151): tile it over the fused channels
+            bg = _tiled_bg(bg, Cn)
+        else:
+            raise RuntimeError(f"bg must have {Cn} entries")
+    return bg
+
+
+def _require_backward_channels(Cn: int, wants_grad: bool):
+    if Cn not in BACKWARD_CHANNELS and wants_grad:
+        # fail in the forward, not in the middle of loss.backward()
+        raise RuntimeError(f"a {Cn}-channel pass is forward-only (backward supports {BACKWARD_CHANNELS} channels): "
+                           "detach the inputs or split the pass")
+
+
+def _pass_camera(rs, dev):
+    """(viewmatrix, projmatrix, campos) of the settings as contiguous fp32 on `dev`"""
+    return _f32c(rs.viewmatrix.to(dev)), _f32c(rs.projmatrix.to(dev)), _f32c(rs.campos.to(dev))
+
+
+def _pass_outputs(P, Cn, H, W, dev, G=1):
+    """(color, depth, alpha, radii) of a pass, in _fwd_args' order; a grouped pass has one image per group.
+    P > 0: the kernels write every pixel of every tile and every radius, so no fill pass is needed; P == 0: zero images.
+    Three separate image tensors (not views of one allocation): callers may modify an output in place."""
+    alloc = torch.zeros if P == 0 else torch.empty
+    lead = (G,) if G > 1 else ()
+    return (alloc(*lead, Cn, H, W, dtype=torch.float32, device=dev), alloc(*lead, 1, H, W, dtype=torch.float32, device=dev),
+            alloc(*lead, 1, H, W, dtype=torch.float32, device=dev), alloc(P, dtype=torch.int32, device=dev))
+
+
 # Binning mode of the passes issued from this process (OgsRasterFwdArgs.full_binning, include/ogs_raster.h).  False (default): the
 # (Gaussian, tile) pairs that cannot reach a pixel of their tile leave the list in the first pass of the tile sort.  True: the
 # reference's full list is kept -- what tests/helpers.py::hip_export_binning compares with the oracle's binning entry by entry.
@@ -221,9 +257,13 @@ def _pose_like(cam):
     return tuple((t.shape, t.dtype, t.device) for t in cam)
 
 
-def _pose_grads(need3, grads, like):
-    """the gradients autograd gets for the three camera inputs: in their shapes, dtypes and devices, None where not needed"""
-    return tuple(g.reshape(shape).to(device=dev, dtype=dtype) if n else None for n, g, (shape, dtype, dev) in zip(need3, grads, like))
+def _pose_grads(need3, pose_out, like):
+    """the gradients autograd gets for the three camera inputs: in their shapes, dtypes and devices, None where not needed.
+    pose_out: what _pose_outputs returned, None for a pass whose camera is a constant"""
+    if pose_out is None:
+        return None, None, None
+    return tuple(g.reshape(shape).to(device=dev, dtype=dtype) if n else None
+                 for n, g, (shape, dtype, dev) in zip(need3, pose_out[:3], like))
 
 
 def _fwd_args(rs, P, Cn, m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, color, depth, alpha, radii, group_ids, G):
@@ -240,6 +280,38 @@ def _fwd_args(rs, P, Cn, m3, shs, cols, opac, scl, rot, cov, bg, view, proj, cam
     a.group_ids, a.num_groups = ptr(group_ids), G
     a.full_binning = int(FULL_BINNING)
     return a
+
+
+def _bwd_args(ctx, lib, m3, cols, bg, view, proj, campos, radii, alpha, kept, upstream, g_m3, g_m2, g_col, record):
+    """The OgsRasterBwdArgs fields the backwards of _RasterizeGaussians and _RasterizeModel share; the callers add sh_coeffs and
+    their own inputs and gradients.  kept: (geom, image, point_list, sorted_rec, quad_list); upstream: backward()'s (grad_color,
+    grad_depth, grad_alpha); record: _take_record's (bwd_tmp, is_clear).  Returns (b, hold): `b` carries raw pointers only, the
+    caller keeps `hold` until its launch is queued -- the contiguous fp32 upstream gradients and, last, what _pose_outputs
+    allocated when the camera trains (else None)."""
+    rs, P, Cn = ctx.raster_settings, ctx.P, ctx.Cn
+    W, H = int(rs.image_width), int(rs.image_height)
+    geom, image, point_list, sorted_rec, quad_list = kept
+    # depth and alpha stay None when no loss touched them (the kernels compile their terms out); the colour gradient is what
+    # the backward launches over: zeros in its place
+    gc, gd, ga = _f32c(upstream[0]), _f32c(upstream[1]), _f32c(upstream[2])
+    if gc is None:
+        gc = torch.zeros(*((ctx.num_groups,) if ctx.num_groups > 1 else ()), Cn, H, W, dtype=torch.float32, device=m3.device)
+    b = OgsRasterBwdArgs()
+    b.P, b.W, b.H, b.C = P, W, H, Cn
+    b.sh_degree = int(rs.sh_degree)
+    b.tanfovx, b.tanfovy, b.scale_modifier = float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier)
+    b.debug = int(bool(rs.debug))
+    b.num_rendered, b.geom_channels, b.num_groups = int(ctx.num_rendered), int(ctx.geom_channels), int(ctx.num_groups)
+    b.geom_buffer, b.image_buffer, b.point_list = ptr(geom), ptr(image), ptr(point_list)
+    b.sorted_rec, b.quad_list = ptr(sorted_rec), ptr(quad_list)
+    b.bg, b.means3D, b.colors_precomp = ptr(bg), ptr(m3), ptr(cols)
+    b.viewmatrix, b.projmatrix, b.campos = ptr(view), ptr(proj), ptr(campos)
+    b.radii, b.out_alpha = ptr(radii), ptr(alpha)
+    b.dL_dcolor, b.dL_ddepth, b.dL_dalpha = ptr(gc), ptr(gd), ptr(ga)
+    b.dL_dmeans2D, b.dL_dcolors, b.dL_dmeans3D = ptr(g_m2), ptr(g_col), ptr(g_m3)
+    b.bwd_tmp, b.bwd_tmp_is_clear = ptr(record[0]), int(record[1])
+    pose_out = _pose_outputs(lib, b, P, m3.device) if ctx.pose_like is not None else None
+    return b, (gc, gd, ga, pose_out)
 
 
 # scratch sizes are pure functions of the shape: asked once per shape, not six ctypes calls per pass (a 100 k-Gaussian step is
@@ -326,6 +398,83 @@ def _streaming_render(a: OgsRasterFwdArgs, dev, lib, debug: bool, raw: Optional[
     return geom, image, point_list, sorted_rec, quad_list, D
 
 
+# ---- the pass behind _RasterizeGaussians and _RasterizeModel: each keeps its own input checks, argument positions and
+# save_for_backward layout (code outside this file reads them); what runs between is here, once ----------------------------
+def _init_ctx(ctx, rs, P, Cn, G):
+    """what a pass that launched nothing (P == 0) leaves on its autograd node; _forward_pass overwrites its part"""
+    ctx.raster_settings = rs
+    ctx.P, ctx.Cn, ctx.num_groups, ctx.num_rendered, ctx.tiny = P, Cn, G, 0, False
+    ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
+    ctx.full_binning = bool(FULL_BINNING)
+
+
+def _forward_pass(ctx, a: OgsRasterFwdArgs, raw: Optional[OgsRawModel], dev, G, force_streaming, wants_grad, record_bytes):
+    """Runs the forward `a` describes (raw: from the model's raw parameters) and leaves tiny / num_rendered / bwd_tmp /
+    bwd_clear_bytes on `ctx`.  Returns the state backward needs, (geom, image, point_list, sorted_rec, quad_list), or None for
+    a tiny pass, which keeps nothing.  record_bytes: the gradient record the backward of this pass will use, known from the
+    requires_grad flags (_grad_record_bytes)."""
+    lib = _lib.lib()
+    debug = bool(a.debug)
+    if G == 1 and not debug and int(a.P) <= _tiny_limit() and not force_streaming:
+        # tiny pass: two launches, no read-back, nothing kept -- backward() re-renders through the streaming path
+        stream = _stream()
+        geom, geom_tmp = _tiny_scratch(dev, stream, lib)
+        a.geom_buffer, a.geom_tmp = geom.data_ptr(), geom_tmp.data_ptr()
+        if raw is None:
+            check(lib.ogs_raster_forward_tiny(C.byref(a), stream), "ogs_raster_forward_tiny")
+        else:
+            check(lib.ogs_raster_forward_tiny_raw(C.byref(a), C.byref(raw), stream), "ogs_raster_forward_tiny_raw")
+        PASS_STATS["tiny"] += 1
+        ctx.tiny, ctx.num_rendered = True, -1
+        return None
+    bwd_tmp = None
+    if HOST_BWD_CLEAR and G == 1 and not debug and wants_grad:
+        # the gradient record of this pass' backward: allocated here, zeroed by the render phase on its way, held until the
+        # backward runs
+        bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(int(a.P))), dtype=torch.uint8, device=dev)
+        a.bwd_clear, a.bwd_clear_bytes = ptr(bwd_tmp), record_bytes
+    state = _streaming_render(a, dev, lib, debug, raw)
+    ctx.num_rendered = state[5]
+    if bwd_tmp is not None:
+        # every render call of _streaming_render carried the pointer: the range is zero in stream order
+        ctx.bwd_tmp, ctx.bwd_clear_bytes = bwd_tmp, record_bytes
+    return state[:5]
+
+
+def _backward_state(ctx, lib, saved, inputs, raw: Optional[OgsRawModel] = None):
+    """(kept, scratch) for a backward: kept = (geom, image, point_list, sorted_rec, quad_list), saved by a streaming pass and
+    rendered again for a tiny one.  saved: ctx.saved_tensors; inputs: _fwd_args' seven per-Gaussian tensors (means3D ..
+    cov3D_precomp) of that re-render; raw: it reads the model's raw parameters.  scratch: the re-render's outputs, which the
+    CALLER holds until its backward launch is queued (None for a streaming pass)."""
+    if not ctx.tiny:
+        return saved[13:], None
+    # a tiny pass keeps nothing: re-render through the streaming path (scratch outputs) to obtain the binning
+    # and blend state the backward kernels read.  Rare: the refiner's footprint renders never call backward.
+    rs, P, Cn = ctx.raster_settings, ctx.P, ctx.Cn
+    dev = saved[0].device
+    # scratch outputs: held by the caller until the re-render has been enqueued AND everything else of its
+    # backward has been allocated -- `a` only carries raw pointers, a tensor freed here would be handed out
+    # again by the caching allocator while the kernels still write through the old pointer
+    scratch = _pass_outputs(P, Cn, int(rs.image_height), int(rs.image_width), dev)
+    a = _fwd_args(rs, P, Cn, *inputs, *saved[7:11], *scratch, None, 1)          # saved[7:11]: bg, view, proj, campos
+    if raw is not None:
+        a.sh_coeffs = ctx.M
+    state = _streaming_render(a, dev, lib, False, raw)
+    ctx.num_rendered = state[5]
+    PASS_STATS["tiny_rerendered_for_backward"] += 1
+    return state[:5], scratch
+
+
+def _take_record(ctx, lib, needed_bytes, dev):
+    """(bwd_tmp, is_clear): the gradient record the forward left zeroed, once -- after this backward it is dirty, a second
+    backward over a retained graph takes a fresh buffer and the fill (as does a pass whose forward hosted no clear)"""
+    bwd_tmp, ctx.bwd_tmp = ctx.bwd_tmp, None
+    if bwd_tmp is None:
+        return torch.empty(int(lib.ogs_raster_backward_tmp_bytes(ctx.P)), dtype=torch.uint8, device=dev), False
+    is_clear, ctx.bwd_clear_bytes = ctx.bwd_clear_bytes >= needed_bytes, 0
+    return bwd_tmp, is_clear
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -343,7 +492,6 @@ class _RasterizeGaussians(torch.autograd.Function):
         # None, not as zero images: the kernels compile the corresponding terms out
         ctx.set_materialize_grads(False)
         G = max(int(num_groups), 1)
-        ctx.num_groups = G
         pose = any(ctx.needs_input_grad[15:18])
         ctx.pose_like = _pose_like((viewmatrix, projmatrix, campos)) if pose else None
         if pose and G > 1:
@@ -356,7 +504,6 @@ class _RasterizeGaussians(torch.autograd.Function):
             group_ids = None
         _require_gpu(means3D, "means3D")
         dev = means3D.device
-        lib = _lib.lib()
         P = int(means3D.shape[0])
         H, W = int(rs.image_height), int(rs.image_width)
         if means3D.dim() != 2 or means3D.shape[1] != 3:
@@ -375,102 +522,42 @@ class _RasterizeGaussians(torch.autograd.Function):
             Cn = 3 if cols is None else int(cols.shape[1])
         if Cn not in SUPPORTED_CHANNELS:
             raise RuntimeError(f"the blended channel count must be 3, 6, 9 or 12, got {Cn}")
-        if Cn not in BACKWARD_CHANNELS and (any(ctx.needs_input_grad[:8]) or pose):
-            # fail here, not in the middle of loss.backward()
-            raise RuntimeError(f"a {Cn}-channel pass is forward-only (backward supports {BACKWARD_CHANNELS} channels): "
-                               "detach the inputs or split the pass")
-        bg = _f32c(rs.bg.to(dev))
-        if bg is None or bg.numel() != Cn:
-            if bg is not None and bg.numel() == 3 and Cn > 3:
-                # the facade's bg is 3-wide and the reference applies it to EVERY 3-channel pass (RGB, feat[:, :3],
-                # feat[:, 3:6], gaussian_renderer/__init__.py:55-70,129-151): tile it over the fused channels
-                bg = _tiled_bg(bg, Cn)
-            else:
-                raise RuntimeError(f"bg must have {Cn} entries")
-        view = _f32c(rs.viewmatrix.to(dev))
-        proj = _f32c(rs.projmatrix.to(dev))
-        campos = _f32c(rs.campos.to(dev))
-
-        # P > 0: the kernels write every pixel of every tile and every radius, so no fill pass is needed
-        alloc = torch.zeros if P == 0 else torch.empty
-        lead = (G,) if G > 1 else ()           # grouped pass: one image per group
-        # three separate tensors (not views of one allocation): callers may modify an output in place
-        color = alloc(*lead, Cn, H, W, dtype=torch.float32, device=dev)
-        depth = alloc(*lead, 1, H, W, dtype=torch.float32, device=dev)
-        alpha = alloc(*lead, 1, H, W, dtype=torch.float32, device=dev)
-        radii = alloc(P, dtype=torch.int32, device=dev)
-        ctx.raster_settings = rs
-        ctx.P, ctx.Cn, ctx.num_rendered, ctx.tiny = P, Cn, 0, False
-        ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
-        ctx.full_binning = bool(FULL_BINNING)
+        need = ctx.needs_input_grad
+        wants_grad = any(need[:8]) or pose
+        _require_backward_channels(Cn, wants_grad)
+        bg = _pass_bg(rs, Cn, dev)
+        view, proj, campos = _pass_camera(rs, dev)
+        color, depth, alpha, radii = _pass_outputs(P, Cn, H, W, dev, G)
+        _init_ctx(ctx, rs, P, Cn, G)
+        ctx.mark_non_differentiable(radii)
         if P == 0:
             # reference behaviour: zero images, nothing launched (SURVEY.md section 8(b) "Errors")
             ctx.save_for_backward()
-            ctx.mark_non_differentiable(radii)
             return color, radii, depth, alpha
 
         a = _fwd_args(rs, P, Cn, m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, color, depth, alpha, radii,
                       group_ids, G)
-
-        if G == 1 and not rs.debug and P <= _tiny_limit() and not force_streaming:
-            # tiny pass: two launches, no read-back, nothing kept -- backward() re-renders through the streaming path
-            stream = _stream()
-            geom, geom_tmp = _tiny_scratch(dev, stream, lib)
-            a.geom_buffer, a.geom_tmp = geom.data_ptr(), geom_tmp.data_ptr()
-            check(lib.ogs_raster_forward_tiny(C.byref(a), stream), "ogs_raster_forward_tiny")
-            PASS_STATS["tiny"] += 1
-            ctx.tiny, ctx.num_rendered = True, -1
-            ctx.save_for_backward(m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, radii, alpha)
-            ctx.mark_non_differentiable(radii)
-            return color, radii, depth, alpha
-
-        need = ctx.needs_input_grad
-        if HOST_BWD_CLEAR and G == 1 and not rs.debug and (any(need[:8]) or pose):
-            # the gradient record of this pass' backward: allocated here, zeroed by the render phase on its way, held until the
-            # backward runs.  How much of it the backward uses is known from the requires_grad flags
-            bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
-            a.bwd_clear, a.bwd_clear_bytes = ptr(bwd_tmp), _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov, pose)
-        geom, image, point_list, sorted_rec, quad_list, D = _streaming_render(a, dev, lib, rs.debug)
-        ctx.num_rendered = D
-        if a.bwd_clear:
-            # every render call of _streaming_render carried the pointer: the range is zero in stream order
-            ctx.bwd_tmp, ctx.bwd_clear_bytes = bwd_tmp, int(a.bwd_clear_bytes)
-        ctx.save_for_backward(m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, radii, alpha, geom, image,
-                              point_list, sorted_rec, quad_list)
-        ctx.mark_non_differentiable(radii)
-        if keep_sink is not None and G == 1 and D > 0:
+        kept = _forward_pass(ctx, a, None, dev, G, force_streaming, wants_grad,
+                             _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov, pose))
+        # the layout is read from outside: 13 inputs and outputs, then the kept state (absent after a tiny pass)
+        ctx.save_for_backward(m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, radii, alpha, *(kept or ()))
+        if keep_sink is not None and G == 1 and kept is not None and ctx.num_rendered > 0:
             # frozen-geometry cache (KeptPasses below): what a re-blend of this pass needs
-            keep_sink.append({"P": P, "W": W, "H": H, "Cn": Cn, "fused": shs is not None and cols is not None, "D": D,
-                              "image": image, "sorted_rec": sorted_rec, "quad_list": quad_list, "radii": radii,
-                              "full_binning": bool(FULL_BINNING)})
+            _, image, _, sorted_rec, quad_list = kept
+            keep_sink.append({"P": P, "W": W, "H": H, "Cn": Cn, "fused": shs is not None and cols is not None,
+                              "D": ctx.num_rendered, "image": image, "sorted_rec": sorted_rec, "quad_list": quad_list,
+                              "radii": radii, "full_binning": bool(FULL_BINNING)})
         return color, radii, depth, alpha
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
-        rs = ctx.raster_settings
         P, Cn = ctx.P, ctx.Cn
         if P == 0:
             return (None,) * 18
         lib = _lib.lib()
-        H, W = int(rs.image_height), int(rs.image_width)
-        scratch = None
-        if ctx.tiny:
-            # a tiny pass keeps nothing: re-render through the streaming path (scratch outputs) to obtain the binning
-            # and blend state the backward kernels read.  Rare: the refiner's footprint renders never call backward.
-            (m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, radii, alpha) = ctx.saved_tensors
-            dev = m3.device
-            e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
-            # scratch outputs: held in `scratch` until the re-render has been enqueued AND everything else of this
-            # backward has been allocated -- `a` only carries raw pointers, a tensor freed here would be handed out
-            # again by the caching allocator while the kernels still write through the old pointer
-            scratch = (e(Cn, H, W), e(1, H, W), e(1, H, W), torch.empty(P, dtype=torch.int32, device=dev))
-            a = _fwd_args(rs, P, Cn, m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, *scratch, None, 1)
-            geom, image, point_list, sorted_rec, quad_list, D = _streaming_render(a, dev, lib, False)
-            ctx.num_rendered = D
-            PASS_STATS["tiny_rerendered_for_backward"] += 1
-        else:
-            (m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, radii, alpha, geom, image,
-             point_list, sorted_rec, quad_list) = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        m3, shs, cols, opac, scl, rot, cov, bg, view, proj, campos, radii, alpha = saved[:13]
+        kept, scratch = _backward_state(ctx, lib, saved, (m3, shs, cols, opac, scl, rot, cov))
         dev = m3.device
         need = ctx.needs_input_grad   # means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3D
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -487,49 +574,21 @@ class _RasterizeGaussians(torch.autograd.Function):
         g_rot = z(P, 4) if (need[6] and rot is not None) else None
         g_cov = z(P, 6) if (need[7] and cov is not None) else None
 
-        gc = _f32c(grad_color)
-        if gc is None:
-            gc = torch.zeros(*((ctx.num_groups,) if ctx.num_groups > 1 else ()), Cn, H, W, dtype=torch.float32, device=dev)
-        gd = _f32c(grad_depth)
-        ga = _f32c(grad_alpha)
-        # the record the forward left zeroed, once: after this backward it is dirty, a second backward over a retained graph
-        # takes a fresh buffer and the fill
-        bwd_tmp, is_clear = ctx.bwd_tmp, False
-        if bwd_tmp is not None:
-            is_clear = ctx.bwd_clear_bytes >= _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov, ctx.pose_like is not None)
-            ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
-        else:
-            bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
-
-        b = OgsRasterBwdArgs()
-        pose_out = _pose_outputs(lib, b, P, dev) if ctx.pose_like is not None else None
-        b.bwd_tmp_is_clear = int(is_clear)
-        b.P, b.W, b.H, b.C = P, W, H, Cn
-        b.sh_degree = int(rs.sh_degree)
+        record = _take_record(ctx, lib, _grad_record_bytes(need, P, Cn, shs, cols, scl, rot, cov, ctx.pose_like is not None), dev)
+        b, hold = _bwd_args(ctx, lib, m3, cols, bg, view, proj, campos, radii, alpha, kept, (grad_color, grad_depth, grad_alpha),
+                            g_m3, g_m2, g_col, record)
         b.sh_coeffs = 0 if shs is None else int(shs.shape[1])
-        b.tanfovx, b.tanfovy, b.scale_modifier = float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier)
-        b.debug = int(bool(rs.debug))
-        b.num_rendered = int(ctx.num_rendered)
-        b.geom_channels = int(ctx.geom_channels)
-        b.num_groups = int(ctx.num_groups)
-        b.sorted_rec, b.quad_list = ptr(sorted_rec), ptr(quad_list)
-        b.bg, b.means3D, b.colors_precomp, b.shs, b.opacities = ptr(bg), ptr(m3), ptr(cols), ptr(shs), ptr(opac)
-        b.scales, b.rotations, b.cov3D_precomp = ptr(scl), ptr(rot), ptr(cov)
-        b.viewmatrix, b.projmatrix, b.campos = ptr(view), ptr(proj), ptr(campos)
-        b.radii, b.out_alpha = ptr(radii), ptr(alpha)
-        b.dL_dcolor, b.dL_ddepth, b.dL_dalpha = ptr(gc), ptr(gd), ptr(ga)
-        b.geom_buffer, b.image_buffer, b.point_list, b.bwd_tmp = ptr(geom), ptr(image), ptr(point_list), ptr(bwd_tmp)
-        b.dL_dmeans2D, b.dL_dcolors, b.dL_dopacity, b.dL_dmeans3D = ptr(g_m2), ptr(g_col), ptr(g_op), ptr(g_m3)
-        b.dL_dcov3D, b.dL_dsh, b.dL_dscales, b.dL_drotations = ptr(g_cov), ptr(g_sh), ptr(g_scl), ptr(g_rot)
+        b.shs, b.opacities, b.scales, b.rotations, b.cov3D_precomp = ptr(shs), ptr(opac), ptr(scl), ptr(rot), ptr(cov)
+        b.dL_dsh, b.dL_dopacity, b.dL_dscales, b.dL_drotations, b.dL_dcov3D = ptr(g_sh), ptr(g_op), ptr(g_scl), ptr(g_rot), ptr(g_cov)
         b.dL_dsh_rgb = ptr(g_sh_rgb)
         check(lib.ogs_raster_backward(C.byref(b), _stream()), "ogs_raster_backward")
         scratch = None          # (tiny pass re-render) stream-ordered: safe to recycle once the launches are queued
         if _DEBUG_KEEP_BWD_TMP is not None:
-            _DEBUG_KEEP_BWD_TMP.append(bwd_tmp)
+            _DEBUG_KEEP_BWD_TMP.append(record[0])
         if sink is not None:
             sink.append(g_sh_rgb)
-        g_cam = (None, None, None) if pose_out is None else _pose_grads(need[15:18], pose_out[:3], ctx.pose_like)
-        return (g_m3, g_m2, g_sh, g_col, g_op, g_scl, g_rot, g_cov, None, None, None, None, None, None, None) + g_cam
+        return (g_m3, g_m2, g_sh, g_col, g_op, g_scl, g_rot, g_cov, None, None, None, None, None, None, None) + \
+            _pose_grads(need[15:18], hold[3], ctx.pose_like)
 
 
 # ---- kept passes: the frozen-geometry cache ------------------------------------------------------------------------------
@@ -741,26 +800,16 @@ class _ReblendKept(torch.autograd.Function):
         cols = _f32c(extra_feats)
         if cols is None or tuple(cols.shape) != (P, entry.E):
             raise RuntimeError(f"the kept pass blends {entry.E} caller channels of {P} Gaussians, got {tuple(extra_feats.shape)}")
-        if Cn not in BACKWARD_CHANNELS and ctx.needs_input_grad[0]:
-            # as _RasterizeGaussians.forward: fail here, not in the middle of loss.backward()
-            raise RuntimeError(f"a {Cn}-channel pass is forward-only (backward supports {BACKWARD_CHANNELS} channels): "
-                               "detach the inputs or split the pass")
-        bg = _f32c(rs.bg.to(dev))
-        if bg is None or bg.numel() != Cn:
-            if bg is not None and bg.numel() == 3 and Cn > 3:
-                bg = _tiled_bg(bg, Cn)
-            else:
-                raise RuntimeError(f"bg must have {Cn} entries")
+        _require_backward_channels(Cn, ctx.needs_input_grad[0])
+        bg = _pass_bg(rs, Cn, dev)
         color = torch.empty(Cn, H, W, dtype=torch.float32, device=dev)
         depth = torch.empty(1, H, W, dtype=torch.float32, device=dev)
         alpha = torch.empty(1, H, W, dtype=torch.float32, device=dev)
-        a = OgsRasterFwdArgs()
-        a.P, a.W, a.H, a.C = P, W, H, Cn
+        a = _kept_args((P, W, H, Cn, entry.image, entry.sorted_rec, entry.quad_list))
         a.sh_coeffs = 1 if entry.fused else 0          # flag only: channels 0..2 of the kept records stay (header)
         a.debug = int(bool(rs.debug))
         a.bg, a.colors_precomp = ptr(bg), ptr(cols)
         a.out_color, a.out_depth, a.out_alpha = ptr(color), ptr(depth), ptr(alpha)
-        a.image_buffer, a.sorted_rec, a.quad_list = ptr(entry.image), ptr(entry.sorted_rec), ptr(entry.quad_list)
         check(lib.ogs_raster_forward_reblend(C.byref(a), _stream()), "ogs_raster_forward_reblend")
         PASS_STATS["reblend"] += 1
         ctx.entry, ctx.raster_settings = entry, rs
@@ -1115,7 +1164,6 @@ class _RasterizeModel(torch.autograd.Function):
                         (scaling_raw, "scaling_raw"), (rotation_raw, "rotation_raw")):
             _require_gpu(t, name)
         dev = means3D.device
-        lib = _lib.lib()
         P = int(means3D.shape[0])
         H, W = int(rs.image_height), int(rs.image_width)
         if means3D.dim() != 2 or means3D.shape[1] != 3:
@@ -1137,54 +1185,25 @@ class _RasterizeModel(torch.autograd.Function):
         Cn = 3 + (0 if cols is None else int(cols.shape[1]))
         if Cn not in SUPPORTED_CHANNELS:
             raise RuntimeError(f"the blended channel count must be 3, 6, 9 or 12, got {Cn}")
-        if Cn not in BACKWARD_CHANNELS and (any(ctx.needs_input_grad[:8]) or pose):
-            raise RuntimeError(f"a {Cn}-channel pass is forward-only (backward supports {BACKWARD_CHANNELS} channels): "
-                               "detach the inputs or split the pass")
-        bg = _f32c(rs.bg.to(dev))
-        if bg is None or bg.numel() != Cn:
-            if bg is not None and bg.numel() == 3 and Cn > 3:
-                bg = _tiled_bg(bg, Cn)
-            else:
-                raise RuntimeError(f"bg must have {Cn} entries")
-        view, proj, campos = _f32c(rs.viewmatrix.to(dev)), _f32c(rs.projmatrix.to(dev)), _f32c(rs.campos.to(dev))
-        alloc = torch.zeros if P == 0 else torch.empty
-        color = alloc(Cn, H, W, dtype=torch.float32, device=dev)
-        depth = alloc(1, H, W, dtype=torch.float32, device=dev)
-        alpha = alloc(1, H, W, dtype=torch.float32, device=dev)
-        radii = alloc(P, dtype=torch.int32, device=dev)
-        ctx.raster_settings = rs
-        ctx.P, ctx.Cn, ctx.M, ctx.num_rendered, ctx.tiny = P, Cn, M, 0, False
-        ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
-        ctx.full_binning, ctx.num_groups = bool(FULL_BINNING), 1
+        need = ctx.needs_input_grad
+        wants_grad = any(need[:8]) or pose
+        _require_backward_channels(Cn, wants_grad)
+        bg = _pass_bg(rs, Cn, dev)
+        view, proj, campos = _pass_camera(rs, dev)
+        color, depth, alpha, radii = _pass_outputs(P, Cn, H, W, dev)
+        _init_ctx(ctx, rs, P, Cn, 1)
+        ctx.M = M
+        ctx.mark_non_differentiable(radii)
         if P == 0:
             ctx.save_for_backward()
-            ctx.mark_non_differentiable(radii)
             return color, radii, depth, alpha
         PASS_STATS["raw_model"] += 1
         a = _fwd_args(rs, P, Cn, m3, None, cols, None, None, None, None, bg, view, proj, campos, color, depth, alpha, radii, None, 1)
         a.sh_coeffs = M
-        raw = _raw_model_struct(dc, rest, opac, scl, rot)
-        if not rs.debug and P <= _tiny_limit():
-            stream = _stream()
-            geom, geom_tmp = _tiny_scratch(dev, stream, lib)
-            a.geom_buffer, a.geom_tmp = geom.data_ptr(), geom_tmp.data_ptr()
-            check(lib.ogs_raster_forward_tiny_raw(C.byref(a), C.byref(raw), stream), "ogs_raster_forward_tiny_raw")
-            PASS_STATS["tiny"] += 1
-            ctx.tiny, ctx.num_rendered = True, -1
-            ctx.save_for_backward(m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha)
-            ctx.mark_non_differentiable(radii)
-            return color, radii, depth, alpha
-        need = ctx.needs_input_grad
-        if HOST_BWD_CLEAR and not rs.debug and (any(need[:8]) or pose):
-            bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
-            a.bwd_clear, a.bwd_clear_bytes = ptr(bwd_tmp), _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot, pose)
-        geom, image, point_list, sorted_rec, quad_list, D = _streaming_render(a, dev, lib, rs.debug, raw)
-        ctx.num_rendered = D
-        if a.bwd_clear:
-            ctx.bwd_tmp, ctx.bwd_clear_bytes = bwd_tmp, int(a.bwd_clear_bytes)
-        ctx.save_for_backward(m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha, geom, image, point_list,
-                              sorted_rec, quad_list)
-        ctx.mark_non_differentiable(radii)
+        kept = _forward_pass(ctx, a, _raw_model_struct(dc, rest, opac, scl, rot), dev, 1, False, wants_grad,
+                             _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot, pose))
+        # the layout is read from outside: _RasterizeGaussians' with (dc, rest) for (shs, cols) and cols for cov
+        ctx.save_for_backward(m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha, *(kept or ()))
         return color, radii, depth, alpha
 
     @staticmethod
@@ -1195,28 +1214,14 @@ class _RasterizeModel(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
-        rs = ctx.raster_settings
         P, Cn, M = ctx.P, ctx.Cn, ctx.M
         if P == 0:
             return (None,) * 13
         lib = _lib.lib()
-        H, W = int(rs.image_height), int(rs.image_width)
-        scratch = None
-        if ctx.tiny:
-            # as _RasterizeGaussians: a tiny pass keeps nothing, the backward re-renders through the streaming path
-            (m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha) = ctx.saved_tensors
-            dev = m3.device
-            e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
-            scratch = (e(Cn, H, W), e(1, H, W), e(1, H, W), torch.empty(P, dtype=torch.int32, device=dev))
-            a = _fwd_args(rs, P, Cn, m3, None, cols, None, None, None, None, bg, view, proj, campos, *scratch, None, 1)
-            a.sh_coeffs = M
-            geom, image, point_list, sorted_rec, quad_list, D = _streaming_render(
-                a, dev, lib, False, _raw_model_struct(dc, rest, opac, scl, rot))
-            ctx.num_rendered = D
-            PASS_STATS["tiny_rerendered_for_backward"] += 1
-        else:
-            (m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha, geom, image, point_list, sorted_rec,
-             quad_list) = ctx.saved_tensors
+        saved = ctx.saved_tensors
+        m3, dc, rest, opac, scl, rot, cols, bg, view, proj, campos, radii, alpha = saved[:13]
+        raw = _raw_model_struct(dc, rest, opac, scl, rot)
+        kept, scratch = _backward_state(ctx, lib, saved, (m3, None, cols, None, None, None, None), raw)
         dev = m3.device
         need = ctx.needs_input_grad   # means3D, means2D, features_dc, features_rest, opacity, scaling, rotation, extra_feats
         z = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -1228,39 +1233,16 @@ class _RasterizeModel(torch.autograd.Function):
         g_scl = z(P, 3) if need[5] else None
         g_rot = z(P, 4) if need[6] else None
         g_col = z(*cols.shape) if (need[7] and cols is not None) else None
-        gc = _f32c(grad_color)
-        if gc is None:
-            gc = torch.zeros(Cn, H, W, dtype=torch.float32, device=dev)
-        gd, ga = _f32c(grad_depth), _f32c(grad_alpha)
-        bwd_tmp, is_clear = ctx.bwd_tmp, False
-        if bwd_tmp is not None:
-            is_clear = ctx.bwd_clear_bytes >= _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot, ctx.pose_like is not None)
-            ctx.bwd_tmp, ctx.bwd_clear_bytes = None, 0
-        else:
-            bwd_tmp = torch.empty(int(lib.ogs_raster_backward_tmp_bytes(P)), dtype=torch.uint8, device=dev)
-        b = OgsRasterBwdArgs()
-        b.bwd_tmp_is_clear = int(is_clear)
-        b.P, b.W, b.H, b.C = P, W, H, Cn
-        b.sh_degree, b.sh_coeffs = int(rs.sh_degree), M
-        b.tanfovx, b.tanfovy, b.scale_modifier = float(rs.tanfovx), float(rs.tanfovy), float(rs.scale_modifier)
-        b.debug = int(bool(rs.debug))
-        b.num_rendered, b.geom_channels, b.num_groups = int(ctx.num_rendered), int(ctx.geom_channels), 1
-        b.sorted_rec, b.quad_list = ptr(sorted_rec), ptr(quad_list)
-        b.bg, b.means3D, b.colors_precomp = ptr(bg), ptr(m3), ptr(cols)
-        b.viewmatrix, b.projmatrix, b.campos = ptr(view), ptr(proj), ptr(campos)
-        b.radii, b.out_alpha = ptr(radii), ptr(alpha)
-        b.dL_dcolor, b.dL_ddepth, b.dL_dalpha = ptr(gc), ptr(gd), ptr(ga)
-        b.geom_buffer, b.image_buffer, b.point_list, b.bwd_tmp = ptr(geom), ptr(image), ptr(point_list), ptr(bwd_tmp)
-        b.dL_dmeans2D, b.dL_dcolors, b.dL_dmeans3D = ptr(g_m2), ptr(g_col), ptr(g_m3)
-        raw = _raw_model_struct(dc, rest, opac, scl, rot)
+        record = _take_record(ctx, lib, _RasterizeModel._record_bytes(need, P, Cn, dc, cols, scl, rot, ctx.pose_like is not None), dev)
+        b, hold = _bwd_args(ctx, lib, m3, cols, bg, view, proj, campos, radii, alpha, kept, (grad_color, grad_depth, grad_alpha),
+                            g_m3, g_m2, g_col, record)
+        b.sh_coeffs = M
         grads = OgsRawModelGrads()
         grads.features_dc, grads.features_rest, grads.scaling, grads.rotation, grads.opacity = \
             ptr(g_dc), ptr(g_rest), ptr(g_scl), ptr(g_rot), ptr(g_op)
-        pose_out = _pose_outputs(lib, b, P, dev) if ctx.pose_like is not None else None
         check(lib.ogs_raster_backward_raw(C.byref(b), C.byref(raw), C.byref(grads), _stream()), "ogs_raster_backward_raw")
-        scratch = None
-        g_cam = (None, None, None) if pose_out is None else _pose_grads(need[10:13], pose_out[:3], ctx.pose_like)
-        return (g_m3, g_m2, g_dc, g_rest, g_op, g_scl, g_rot, g_col, None, None) + g_cam
+        scratch = None          # (tiny pass re-render) stream-ordered: safe to recycle once the launches are queued
+        return (g_m3, g_m2, g_dc, g_rest, g_op, g_scl, g_rot, g_col, None, None) + _pose_grads(need[10:13], hold[3], ctx.pose_like)
 
 
 def rasterize_model(means3D, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings,
@@ -1334,15 +1316,9 @@ def _stats_inputs(means3D, opacities, raster_settings, colors_precomp, scales, r
     Cn = int(colors_precomp.shape[-1])
     if Cn not in SUPPORTED_CHANNELS:
         raise RuntimeError(f"the blended channel count must be 3, 6, 9 or 12, got {Cn}")
-    rs = raster_settings
-    bg = _f32c(rs.bg.to(dev))
-    if bg is None or bg.numel() != Cn:
-        if bg is not None and bg.numel() == 3 and Cn > 3:
-            bg = _tiled_bg(bg, Cn)         # as every other pass of the facade: the 3-wide background over all channels
-        else:
-            raise RuntimeError(f"bg must have {Cn} entries")
+    bg = _pass_bg(raster_settings, Cn, dev)         # as every other pass of the facade: the 3-wide background over all channels
     return (Cn, _f32c(means3D), _f32c(opacities), cols, _f32c(scales), _f32c(rotations), _f32c(cov3D_precomp), bg,
-            _f32c(rs.viewmatrix.to(dev)), _f32c(rs.projmatrix.to(dev)), _f32c(rs.campos.to(dev)))
+            *_pass_camera(raster_settings, dev))
 
 
 def visible_radii(means3D, opacities, raster_settings, colors_precomp, scales=None, rotations=None, cov3D_precomp=None):
